@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): 1 s-strain segments/s through the whisper-tiny
 encoder forward at batch 256 x (80 x 3000) log-mel, bf16 MFMA, on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch: [256, 80, 3000] fp32 log-mel
@@ -77,6 +77,27 @@ def csrc_hash():
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
     return h.hexdigest()[:16]
+
+
+DUMP_BUDGET = 64 << 20               # --dump-outputs: bytes written in all
+DUMP_SEED = 0
+
+
+def dump_outputs(path, hidden, last):
+    """--dump-outputs: what one step of the timed path returned, as float32 .npy files under `path` -- last_token
+    [B, d] whole, and last_hidden_state [B, 1500, d] (590 MB at the default shape) as a fixed, seeded sample of rows
+    whose (segment, token) positions are written beside it as float64.  The sample depends on the shape only."""
+    os.makedirs(path, exist_ok=True)
+    B, Tn, d = hidden.shape
+    last = last.cpu().numpy()
+    n = int(min(B * Tn, 16384, (DUMP_BUDGET - last.nbytes) // (d * 4 + 16)))
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B * Tn, size=n, replace=False))
+    sample = hidden.reshape(B * Tn, d).index_select(0, torch.from_numpy(rows).to(hidden.device)).cpu().numpy()
+    arrays = {"last_token": last, "last_hidden_state_sample": sample,
+              "last_hidden_state_sample_rows": np.stack(np.divmod(rows, Tn), axis=1).astype(np.float64)}
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_BUDGET
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def flops_per_segment(d, L, H, ffn, n_mels=80):
@@ -334,7 +355,14 @@ def main():
     ap.add_argument("--train-batch", type=int, default=32, help="per-GPU batch of the DoRA step (reference default 32)")
     ap.add_argument("--isolated", action="store_true", help="also time each kernel class in isolation")
     ap.add_argument("--no-extra", action="store_true", help="skip the whisper-base forward / whisper-small DoRA step extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned on rank 0 "
+                    "as DIR/<name>.npy: last_token whole, last_hidden_state as a fixed, seeded sample of rows (64 MB at most)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    from gw_whisper_amd import synth as _synth   # numpy only: nothing has touched the GPU yet
+    if args.dump_outputs and args.batch * _synth.ENCODER_SIZES[args.encoder][0] * 4 > DUMP_BUDGET // 2:
+        ap.error(f"--dump-outputs: last_token of batch {args.batch} exceeds {DUMP_BUDGET // 2 >> 20} MB")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -451,6 +479,8 @@ def main():
             out = step()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, *out)
         traced = {}
         if trace:
             # Per-kernel durations for the roofline: a SEPARATE pass of the same K steps on ONE stream

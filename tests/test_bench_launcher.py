@@ -66,3 +66,37 @@ def test_real_two_rank_launch_round_trip(tmp_path):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     assert subprocess.run(b.launcher_command([], 2, b.free_port(), script=str(ok)), env=env, timeout=300).returncode == 0
     assert subprocess.run(b.launcher_command([], 2, b.free_port(), script=str(bad)), env=env, timeout=300).returncode != 0
+
+
+def test_dump_outputs_is_a_fixed_bounded_sample_of_what_the_step_returned(tmp_path, monkeypatch):
+    """--dump-outputs: last_token whole, a seeded sample of last_hidden_state rows with their (segment, token) positions,
+    float32 / float64 only, the same rows on every call, and never more than the budget."""
+    import numpy as np
+    b = _bench()
+    g = b.torch.Generator().manual_seed(0)
+    hidden, last = b.torch.randn(16, 1500, 64, generator=g), b.torch.randn(16, 64, generator=g)
+    b.dump_outputs(str(tmp_path / "a"), hidden, last)
+    b.dump_outputs(str(tmp_path / "b"), hidden.clone(), last.clone())
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["last_hidden_state_sample.npy", "last_hidden_state_sample_rows.npy", "last_token.npy"]
+    for n in names:
+        assert np.array_equal(np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)), n
+    d = {n[:-4]: np.load(tmp_path / "a" / n) for n in names}
+    assert d["last_token"].dtype == np.float32 and np.array_equal(d["last_token"], last.numpy())
+    rows = d["last_hidden_state_sample_rows"]
+    assert rows.dtype == np.float64 and len(rows) == 16384 < 16 * 1500
+    r = rows.astype(np.int64)
+    assert np.array_equal(d["last_hidden_state_sample"], hidden.numpy()[r[:, 0], r[:, 1]])
+    monkeypatch.setattr(b, "DUMP_BUDGET", 1 << 20)
+    b.dump_outputs(str(tmp_path / "c"), hidden, last)
+    assert sum(os.path.getsize(tmp_path / "c" / n) for n in names) <= (1 << 20) + 3 * 128    # + the .npy headers
+
+
+def test_steps_below_one_are_refused(monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    try:
+        b.main()
+        raise AssertionError("main() returned")
+    except SystemExit as e:
+        assert e.code == 2

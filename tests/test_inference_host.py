@@ -120,7 +120,7 @@ def test_slicer_time_stamps_are_bit_identical_to_the_reference_iterator(golden):
 def test_search_loop_equals_the_reference_loop_on_its_fixture(golden):
     """Windows, scores, triggers ([time, score] pairs) and clusters of a 40 s two-detector segment: the reference's
     TorchSegmentSlicer + DataLoader(256) + evaluate_slices + get_clusters against this build's strided views +
-    on-device threshold, same deterministic network, CPU fp32: everything bit-identical."""
+    on-device threshold, same deterministic network, CPU, fp32 scores: everything bit-identical."""
     from gw_whisper_amd import synth
     from tests.helpers import search_toy_network
     g = golden("inference_host.npz")
@@ -190,7 +190,7 @@ def test_resample_matrix_is_scipy_resample():
     np.testing.assert_allclose(x @ R.T, resample(x, 16000, axis=1), atol=5e-6)
 
 
-def test_run_inference_harness_host_side(tmp_path):
+def test_run_inference_harness_host_side(tmp_path, monkeypatch):
     """harness/run_inference.py without a GPU: the reference's argument surface, the segment file layout
     (``/<detector>/<key>`` + start_time / delta_t), the result writer, and the two refusals that need no device."""
     import importlib.util
@@ -220,6 +220,7 @@ def test_run_inference_harness_host_side(tmp_path):
     ri.write_result(out, {"time": np.array([1.5]), "stat": np.array([0.9]), "var": np.array([0.2])})
     z = np.load(out)
     assert z["time"][0] == 1.5 and z["var"][0] == 0.2
+    monkeypatch.setattr(ri.torch.cuda, "is_available", lambda: False)   # the refusal is checked on GPU machines too
     with pytest.raises(SystemExit, match="no GPU"):
         ri.main([src, str(tmp_path / "o.npz")])                       # un-whitened input is accepted; no GPU here
     with pytest.raises(RuntimeError):
