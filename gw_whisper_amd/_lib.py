@@ -41,6 +41,16 @@ class DoraTarget(C.Structure):
                 ("dA", C.c_void_p), ("dB", C.c_void_p), ("dm", C.c_void_p)]
 
 
+class EncLayerGrads(C.Structure):
+    _fields_ = [(f[0], C.c_void_p) for f in EncLayer._fields_]
+
+
+class EncGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in
+                ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "pos", "ln_w", "ln_b")] + \
+               [("layers", C.POINTER(EncLayerGrads))]
+
+
 class DoraMergeItem(C.Structure):
     _fields_ = [("w0", C.c_void_p), ("a", C.c_void_p), ("b", C.c_void_p), ("m", C.c_void_p), ("w_eff", C.c_void_p),
                 ("norm_out", C.c_void_p), ("scaling", C.c_float), ("d_out", C.c_int), ("d_in", C.c_int), ("r", C.c_int)]
@@ -76,6 +86,16 @@ SIGNATURES = {
     "gww_encoder_train_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                              C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p]),
+    "gww_train_workspace_bytes_full": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "gww_encoder_train_backward_full": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                  C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
+                                                  C.c_int, C.POINTER(EncGrads), C.c_void_p]),
+    "gww_gemm_wgrad_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
+    "gww_gemm_wgrad_bf16": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_float,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gww_layernorm_param_grads_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int]),
+    "gww_layernorm_param_grads": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_long, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]),
     "gww_attention_bwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gww_attention_bwd_log2q_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -18,6 +18,7 @@
 #include "epilogue.h"
 
 #include <stdlib.h>
+#include <algorithm>
 #include <vector>
 
 namespace gww {
@@ -61,6 +62,13 @@ size_t dora_grads_scratch_bytes(int np, int d);
 int launch_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse, float* D,
                               void* dqkv, int B, int T, int H, hipStream_t s, bool q_log2);
 int launch_mel_to_tokens(const float* mel, void* out, int out_bf16, int B, int C, int T, hipStream_t s);
+int launch_wgrad(const void* dY, long ldy, const void* X, long ldx, long M, int N, int K, float alpha, float* dW,
+                 float* db, int conv_cin, void* workspace, size_t ws_bytes, hipStream_t s);
+size_t wgrad_workspace_bytes(long M, int N, int K);
+int launch_ln_param_grads(const float* x, const void* dy, int dy_f32, long M, int d, float* dgamma, float* dbeta,
+                          void* workspace, size_t ws_bytes, hipStream_t s);
+size_t ln_param_grads_workspace_bytes(long M, int d);
+int launch_pos_grad(const float* dx0, float* dpos, int B, int T, int d, hipStream_t s);
 }
 
 using namespace gww;
@@ -783,6 +791,26 @@ static bool train_fused(const gww_enc_cfg& c) {
   return !off && c.d_model == 384 && c.ffn % 128 == 0 && c.ffn <= 1536;
 }
 
+// full fine-tuning: behind the backward's workspace, the partial slabs of the weight-gradient GEMMs and of the LayerNorm
+// gain / bias sums (one region, reused by every launch in stream order)
+static size_t train_param_scratch_bytes(const gww_enc_cfg& c, int B) {
+  const long d = c.d_model, F = c.ffn, T = c.t_in / 2, M = (long)B * T;
+  size_t mx = 0;
+  for (long m : {M, (long)B}) {
+    mx = std::max(mx, wgrad_workspace_bytes(m, (int)d, (int)d));
+    mx = std::max(mx, wgrad_workspace_bytes(m, (int)F, (int)d));
+    mx = std::max(mx, wgrad_workspace_bytes(m, (int)d, (int)F));
+    mx = std::max(mx, ln_param_grads_workspace_bytes(m, (int)d));
+  }
+  mx = std::max(mx, wgrad_workspace_bytes((long)B * (T + 1), (int)d, 3 * (int)d));
+  mx = std::max(mx, wgrad_workspace_bytes((long)B * (c.t_in + 2), (int)d, kConv1Kpad));
+  return align_up(mx);
+}
+
+extern "C" size_t gww_train_workspace_bytes_full(const gww_encoder* e, int batch) {
+  return (e && batch > 0) ? train_ws(e->cfg, batch).total + train_param_scratch_bytes(e->cfg, batch) : 0;
+}
+
 extern "C" size_t gww_train_saved_bytes(const gww_encoder* e, int batch) {
   return (e && batch > 0) ? saved_layout(e->cfg, batch).total : 0;
 }
@@ -937,17 +965,26 @@ extern "C" int gww_encoder_train_forward(gww_encoder* e, const float* mel, int b
 // residual stream entering layer 0 (the conv stem output).  d_mel (optional, fp32 [B, n_mels, t_in]): gradient
 // w.r.t. the input features, through the conv stem (MLGWSC-1/train.py:494-504 trains its Q-adapter through
 // the frozen encoder).
-extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* workspace, size_t workspace_bytes,
-                                          const void* saved, size_t saved_bytes, const float* d_last_hidden,
-                                          const gww_dora_target* targets, int n_targets, float* d_x0,
-                                          float* d_mel, int pooled, void* stream) {
+//
+// grads (full fine-tuning, may be NULL): fp32 gradients of the base parameters, accumulated into.  Each weight gradient
+// is a weight-gradient GEMM (wgrad.hip) of a gradient / activation pair this backward already has in hand:
+//   fc2: d(x_out) x gelu(fc1(LN2 x_mid))    fc1: d(fc1 pre-act) x LN2(x_mid)    out_proj: d(x_mid) x ctx
+//   q / k / v: dqkv x LN1(x_in) (q with the q_ysc of the stored q)     conv2 / conv1: dz2 / dz1 x im2col views
+// and the LayerNorm gains / biases and the positions are fixed-order column sums.
+static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_t workspace_bytes, const void* saved,
+                               size_t saved_bytes, const float* d_last_hidden, const gww_dora_target* targets,
+                               int n_targets, float* d_x0, float* d_mel, int pooled, const gww_enc_grads* grads,
+                               hipStream_t s) {
   GWW_REQUIRE(e && workspace && saved && d_last_hidden, "gww_encoder_train_backward: NULL argument");
   GWW_REQUIRE(batch > 0 && n_targets >= 0 && (n_targets == 0 || targets), "gww_encoder_train_backward: bad argument");
   const SavedLayout sl = saved_layout(e->cfg, batch);
   const TrainWs w = train_ws(e->cfg, batch);
   if (workspace_bytes < w.total || saved_bytes < sl.total)
     return fail(GWW_ERR_WORKSPACE, "gww_encoder_train_backward: workspace / saved arena too small");
-  hipStream_t s = (hipStream_t)stream;
+  const size_t pscr_bytes = grads ? train_param_scratch_bytes(e->cfg, batch) : 0;
+  if (grads && workspace_bytes < w.total + pscr_bytes)
+    return fail(GWW_ERR_WORKSPACE, "gww_encoder_train_backward_full: workspace %zu bytes < required %zu (base gradients)",
+                workspace_bytes, w.total + pscr_bytes);
   const int d = e->cfg.d_model, F = e->cfg.ffn, T = e->cfg.t_in / 2, H = e->cfg.n_heads;
   const int B = batch, L = e->cfg.n_layers;
   const long M = (long)B * T;
@@ -961,6 +998,27 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
   void* dqkv = base + w.dqkv;
   float* Dv = (float*)(base + w.Dv);
   auto x_in = [&](int l) -> const float* { return (const float*)(sv + (l < L ? (size_t)l * sl.layer_stride + sl.x_in : (size_t)L * sl.layer_stride)); };
+  // ---- base-parameter gradients (full fine-tuning)
+  void* pscr = base + w.total;
+  void* f1 = base + w.f1;   // gelu(fc1) recomputed for the fc2 weight gradient (idle in the backward otherwise)
+  void* ln2o = base + w.d2; // LN2(x_mid) recomputed for the fc1 weight gradient (per-op and pooled paths)
+  auto wg = [&](const void* dY, long ldy, const void* X, long ldx, long rows, int N, int K, float alpha, float* dW,
+                float* db, int cin) -> int {
+    if (!dW && !db) return GWW_OK;
+    return launch_wgrad(dY, ldy, X, ldx, rows, N, K, alpha, dW, db, cin, pscr, pscr_bytes, s);
+  };
+  auto lng = [&](const float* x, const void* dy, int dy_f32, long rows, float* dg, float* db) -> int {
+    if (!dg && !db) return GWW_OK;
+    return launch_ln_param_grads(x, dy, dy_f32, rows, d, dg, db, pscr, pscr_bytes, s);
+  };
+  static const gww_enc_layer_grads no_layer_grads{};
+  auto LGf = [&](int l) -> const gww_enc_layer_grads& {
+    return (grads && grads->layers) ? grads->layers[l] : no_layer_grads;
+  };
+  const bool want_conv2 = grads && (grads->conv2_w || grads->conv2_b);
+  const bool want_conv1 = grads && (grads->conv1_w || grads->conv1_b);
+  const bool want_stem = want_conv1 || want_conv2 || (grads && grads->pos);
+  const bool want_ln1_0 = L > 0 && (LGf(0).ln1_w || LGf(0).ln1_b);
   for (int i = 0; i < n_targets; ++i) {
     const gww_dora_target& t = targets[i];
     GWW_REQUIRE(t.layer >= 0 && t.layer < L && t.proj >= 0 && t.proj <= 3, "gww_encoder_train_backward: bad target %d", i);
@@ -987,9 +1045,11 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
   bool multi_ok = (d == 384 || d == 512) && lab_int("GWW_DORA_OLD", 0) == 0;
   for (int i = 0; i < n_targets; ++i) multi_ok = multi_ok && targets[i].r == 8;
   // final LayerNorm backward -> dx (grad w.r.t. x_in[L]); pooled: on the B last-token rows only
+  if (grads) GWW_TRY(lng(x_in(L), d_last_hidden, 1, pooled ? B : M, grads->ln_w, grads->ln_b));
   GWW_TRY(launch_ln_bwd(x_in(L), e->lnw, d_last_hidden, 1, dx, 0, dxb, pooled ? B : M, d, s));
   for (int l = L - 1; l >= 0; --l) {
     const LayerW& W = e->layers[l];
+    const gww_enc_layer_grads& LG = LGf(l);
     const char* lb = sv + (size_t)l * sl.layer_stride;
     const void* h1 = lb + sl.h1;
     const void* qkv = lb + sl.qkv;
@@ -1009,8 +1069,17 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
       // (x_mid, z, x_in[L] were saved compact by the pooled forward); the attention backward then sees a dctx
       // that is zero except for row T-1 of every segment and skips the dead query tiles.
       GWW_TRY(launch_gemm_bf16(dxb, d, W.w2T, nullptr, nullptr, nullptr, dbig, B, F, d, EPI_BIAS, 0, s, 0));
+      if (LG.fc2_w || LG.fc2_b) {   // z was saved compact by the pooled forward (both paths)
+        GWW_TRY(launch_gelu_bf16(z, nullptr, f1, (((long)B * F + 7) / 8) * 8, s));
+        GWW_TRY(wg(dxb, d, f1, F, B, d, F, 1.0f, LG.fc2_w, LG.fc2_b, 0));
+      }
       GWW_TRY(launch_gelu_bf16(z, dbig, dbig, (((long)B * F + 7) / 8) * 8, s));
+      if (LG.fc1_w || LG.fc1_b) {
+        GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, ln2o, 1, B, d, s));
+        GWW_TRY(wg(dbig, F, ln2o, d, B, F, d, 1.0f, LG.fc1_w, LG.fc1_b, 0));
+      }
       GWW_TRY(launch_gemm_bf16(dbig, F, W.w1T, nullptr, nullptr, nullptr, dh, B, d, F, EPI_BIAS, 0, s, 0));
+      GWW_TRY(lng(x_mid, dh, 0, B, LG.ln2_w, LG.ln2_b));
       GWW_TRY(launch_ln_bwd(x_mid, W.ln2w, dh, 0, dx, 1, dxb, B, d, s));
       const unsigned short* ctx_last = (const unsigned short*)ctx + (size_t)(T - 1) * d;
       bool have_y = false;
@@ -1027,6 +1096,7 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
         GWW_TRY(launch_dora_grads(ctx_last, (long)T * d, dxb, dh, d, W.bo, 1.0f, t.scaling, t.A, t.B, t.mag, t.nrm,
                                   t.dA, t.dB, t.dm, B, d, t.r, s, base + w.dgs, w.dgs_bytes));
       }
+      GWW_TRY(wg(dxb, d, ctx_last, (long)T * d, B, d, d, 1.0f, LG.o_w, LG.o_b, 0));
       // d(ctx) rows (b, T-1) -> the dense, otherwise zero dctx
       GWW_TRY(launch_gemm_bf16(dxb, d, W.woT, nullptr, nullptr, nullptr, dh, B, d, d, EPI_BIAS, 0, s, 0));
       GWW_HIP(hipMemsetAsync(dctx, 0, (size_t)M * d * 2, s));
@@ -1040,16 +1110,32 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
     } else {
     // fc2 / GELU / fc1 / LN2   (x_out = x_mid + fc2(gelu(fc1(LN2(x_mid)))))
     GWW_TRY(gemm_dx(dxb, d, W.w2T, dbig, F, d));
+    const bool want_fc2 = LG.fc2_w || LG.fc2_b;
+    const void* ln2_out = nullptr;   // LN2(x_mid), when a weight gradient needs it
     if (fused) {
       // recompute: LN2(x_mid) (LayerNorm kernel, into the idle dctx buffer) -> fc1 as a plain A-stationary GEMM whose
       // epilogue applies gelu'(pre-activation) to the gradient in place: neither the pre-activation nor a separate
       // GELU-backward pass touches HBM
       GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, dctx, 1, M, d, s));
+      ln2_out = dctx;
+      // full fine-tuning: gelu(fc1(LN2 x_mid)), the fc2 weight gradient's X operand, is not kept by the fused forward
+      if (want_fc2)
+        GWW_TRY(launch_gemm_astat(dctx, d, nullptr, nullptr, nullptr, nullptr, W.w1, W.b1, f1, M, F, d, EPI_GELU, 0, s));
       GWW_TRY(launch_gemm_astat(dctx, d, dbig, nullptr, nullptr, nullptr, W.w1, W.b1, dbig, M, F, d, EPI_DGELU, 0, s));
     } else {
+      if (want_fc2) GWW_TRY(launch_gelu_bf16(z, nullptr, f1, ((M * F + 7) / 8) * 8, s));
       GWW_TRY(launch_gelu_bf16(z, dbig, dbig, ((M * F + 7) / 8) * 8, s));
     }
+    GWW_TRY(wg(dxb, d, f1, F, M, d, F, 1.0f, LG.fc2_w, LG.fc2_b, 0));
+    if (LG.fc1_w || LG.fc1_b) {
+      if (!ln2_out) {
+        GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, ln2o, 1, M, d, s));
+        ln2_out = ln2o;
+      }
+      GWW_TRY(wg(dbig, F, ln2_out, d, M, F, d, 1.0f, LG.fc1_w, LG.fc1_b, 0));
+    }
     GWW_TRY(gemm_dx(dbig, F, W.w1T, dh, d, F));
+    GWW_TRY(lng(x_mid, dh, 0, M, LG.ln2_w, LG.ln2_b));
     GWW_TRY(launch_ln_bwd(x_mid, W.ln2w, dh, 0, dx, 1, dxb, M, d, s));
     // out_proj / attention / QKV / LN1   (x_mid = x_in + out_proj(attn(qkv(LN1(x_in)))))
     {   // out_proj DoRA targets: x = ctx, dy = d(x_mid) (= dxb), y = x_mid - x_in (rebuilt into dh, free here)
@@ -1065,6 +1151,7 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
                                   M, d, t.r, s, base + w.dgs, w.dgs_bytes));
       }
     }
+    GWW_TRY(wg(dxb, d, ctx, d, M, d, d, 1.0f, LG.o_w, LG.o_b, 0));
     GWW_TRY(gemm_dx(dxb, d, W.woT, dctx, d, d));
     }
     GWW_TRY(launch_attention_bwd_bf16(qkv, ctx, dctx, lse, Dv, dqkv, B, T, H, s, attention_log2q_enabled()));
@@ -1099,17 +1186,24 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
                                   t.dB, t.dm, M, d, t.r, s, base + w.dgs, w.dgs_bytes));
       }
     }
-    // below layer 0 the gradient only continues into the conv stem: skip it when nobody asked for d_x0 / d_mel
-    if (l == 0 && !d_x0 && !d_mel) break;
+    // q / k / v weight gradients: dqkv is the gradient of the STORED q (q_ysc (W x + b)), k has no bias
+    GWW_TRY(wg(dqkv, 3L * d, h1, d, M, d, d, q_ysc, LG.q_w, LG.q_b, 0));
+    GWW_TRY(wg((const unsigned short*)dqkv + d, 3L * d, h1, d, M, d, d, 1.0f, LG.k_w, nullptr, 0));
+    GWW_TRY(wg((const unsigned short*)dqkv + 2 * d, 3L * d, h1, d, M, d, d, 1.0f, LG.v_w, LG.v_b, 0));
+    // below layer 0 the gradient only continues into LN1 of layer 0 and the conv stem: skip it when nobody asked for
+    // d_x0 / d_mel or one of their parameter gradients
+    if (l == 0 && !d_x0 && !d_mel && !want_stem && !want_ln1_0) break;
     GWW_TRY(gemm_dx(dqkv, 3L * d, W.wqkvT, dh, d, 3 * d));
+    GWW_TRY(lng(x_in(l), dh, 0, M, LG.ln1_w, LG.ln1_b));
     GWW_TRY(launch_ln_bwd(x_in(l), W.ln1w, dh, 0, dx, 1, dxb, M, d, s));
   }
   if (d_x0) GWW_HIP(hipMemcpyAsync(d_x0, dx, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
-  if (d_mel) {
+  if (grads && grads->pos) GWW_TRY(launch_pos_grad(dx, grads->pos, B, T, d, s));   // x0 = gelu(conv2) + pos
+  if (d_mel || want_conv1 || want_conv2) {
     // ---- conv stem backward: x0 = gelu(conv2(gelu(conv1(mel)))) + pos (melT and c1 of the forward are still
     // in the workspace); the pre-activations are recomputed by the same GEMMs with a plain bias epilogue
     const int Tin = e->cfg.t_in, C = e->cfg.n_mels;
-    GWW_REQUIRE(B <= 512, "gww_encoder_train_backward: d_mel supports batch <= 512");
+    GWW_REQUIRE(B <= 512, "gww_encoder_train_backward: d_mel and the conv-stem gradients support batch <= 512");
     const void* melT = base + w.melT;
     const void* c1 = base + w.c1;
     void* z1 = base + w.z1;
@@ -1117,11 +1211,36 @@ extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* works
     const long M2 = (long)B * (T + 1), M1 = (long)B * (Tin + 2);
     GWW_TRY(launch_gemm_bf16(c1, 2L * d, e->c2w, e->c2b, nullptr, nullptr, dh, M2, d, 3 * d, EPI_BIAS, 0, s, 0));       // z2
     GWW_TRY(launch_stem_dz2(dxb, dh, dctx, B, T, d, s));                                                              // dz2
-    GWW_TRY(launch_gemm_bf16(dctx, d, e->c2wT, nullptr, nullptr, nullptr, dqkv, M2, 3 * d, d, EPI_BIAS, 0, s, 0));     // col
-    GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, z1, M1, d, kConv1Kpad, EPI_BIAS, 0, s, 0));    // z1
-    GWW_TRY(launch_stem_dz1(dqkv, z1, z1, B, T, Tin, d, s));                                                          // dz1
-    GWW_TRY(launch_gemm_bf16(z1, d, e->c1wT, nullptr, nullptr, nullptr, col1, M1, kConv1Kpad, d, EPI_BIAS, 0, s, 0));  // col1
-    GWW_TRY(launch_stem_dmel(col1, d_mel, B, Tin, C, kConv1Kpad, s));
+    // conv2 weight gradient on the forward's im2col view of c1 (row m: padded rows 2 t .. 2 t + 2); the junk row
+    // t = T of every segment has dz2 = 0
+    if (want_conv2) GWW_TRY(wg(dctx, d, c1, 2L * d, M2, d, 3 * d, 1.0f, grads->conv2_w, grads->conv2_b, d));
+    if (d_mel || want_conv1) {
+      GWW_TRY(launch_gemm_bf16(dctx, d, e->c2wT, nullptr, nullptr, nullptr, dqkv, M2, 3 * d, d, EPI_BIAS, 0, s, 0));   // col
+      GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, z1, M1, d, kConv1Kpad, EPI_BIAS, 0, s, 0));  // z1
+      GWW_TRY(launch_stem_dz1(dqkv, z1, z1, B, T, Tin, d, s));                                                        // dz1
+      // conv1 weight gradient on the im2col view of melT (K = kConv1Kpad: taps 0..2 of C channels + padding, dropped)
+      if (want_conv1) GWW_TRY(wg(z1, d, melT, C, M1, d, kConv1Kpad, 1.0f, grads->conv1_w, grads->conv1_b, C));
+    }
+    if (d_mel) {
+      GWW_TRY(launch_gemm_bf16(z1, d, e->c1wT, nullptr, nullptr, nullptr, col1, M1, kConv1Kpad, d, EPI_BIAS, 0, s, 0));  // col1
+      GWW_TRY(launch_stem_dmel(col1, d_mel, B, Tin, C, kConv1Kpad, s));
+    }
   }
   return GWW_OK;
+}
+
+extern "C" int gww_encoder_train_backward(gww_encoder* e, int batch, void* workspace, size_t workspace_bytes,
+                                          const void* saved, size_t saved_bytes, const float* d_last_hidden,
+                                          const gww_dora_target* targets, int n_targets, float* d_x0,
+                                          float* d_mel, int pooled, void* stream) {
+  return train_backward_impl(e, batch, workspace, workspace_bytes, saved, saved_bytes, d_last_hidden, targets, n_targets,
+                             d_x0, d_mel, pooled, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int gww_encoder_train_backward_full(gww_encoder* e, int batch, void* workspace, size_t workspace_bytes,
+                                               const void* saved, size_t saved_bytes, const float* d_last_hidden,
+                                               const gww_dora_target* targets, int n_targets, float* d_x0,
+                                               float* d_mel, int pooled, const gww_enc_grads* grads, void* stream) {
+  return train_backward_impl(e, batch, workspace, workspace_bytes, saved, saved_bytes, d_last_hidden, targets, n_targets,
+                             d_x0, d_mel, pooled, grads, (hipStream_t)stream);
 }

@@ -95,6 +95,132 @@ int launch_ln_bwd(const float* x, const float* gamma, const void* dy, int dy_f32
   return GWW_OK;
 }
 
+// ---------------------------------------------------------------- LayerNorm gain / bias gradients
+// dgamma += sum_m dy * xhat, dbeta += sum_m dy (full fine-tuning).  One wave per row as in k_ln_bwd; workgroup b takes
+// rows 4 b + w + 4 P i (P workgroups) and writes its column sums to part[b] = [dgamma | dbeta] (the four waves combined
+// through LDS in wave order); k_ln_gb_reduce sums the P partials in workgroup order: no atomics, deterministic.
+template <int NV, bool DY_F32>
+__global__ __launch_bounds__(256) void k_ln_gb_partial(const float* __restrict__ x, const void* __restrict__ dy, long M,
+                                                       float* __restrict__ part) {
+  constexpr int d = NV * 128;
+  __shared__ float2 red[4][2][NV * 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long P = gridDim.x;
+  float2 sg[NV], sb[NV];
+#pragma unroll
+  for (int j = 0; j < NV; ++j) sg[j] = sb[j] = make_float2(0.f, 0.f);
+  for (long row = (long)blockIdx.x * 4 + w; row < M; row += 4 * P) {
+    const float2* xr = reinterpret_cast<const float2*>(x + row * d);
+    float2 v[NV];
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      v[j] = xr[lane + 64 * j];
+      s += v[j].x + v[j].y;
+    }
+    const float mean = wave_sum(s) * (1.0f / d);
+    float q = 0.f;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      v[j].x -= mean;
+      v[j].y -= mean;
+      q += v[j].x * v[j].x + v[j].y * v[j].y;
+    }
+    const float rstd = rsqrtf(wave_sum(q) * (1.0f / d) + 1e-5f);
+#pragma unroll
+    for (int j = 0; j < NV; ++j) {
+      float d0, d1;
+      if constexpr (DY_F32) {
+        const float2 t = reinterpret_cast<const float2*>(reinterpret_cast<const float*>(dy) + row * d)[lane + 64 * j];
+        d0 = t.x; d1 = t.y;
+      } else {
+        const unsigned int t = reinterpret_cast<const unsigned int*>(reinterpret_cast<const unsigned short*>(dy) + row * d)[lane + 64 * j];
+        d0 = bf2f((unsigned short)(t & 0xffff)); d1 = bf2f((unsigned short)(t >> 16));
+      }
+      sg[j].x += d0 * v[j].x * rstd; sg[j].y += d1 * v[j].y * rstd;
+      sb[j].x += d0; sb[j].y += d1;
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    red[w][0][lane + 64 * j] = sg[j];
+    red[w][1][lane + 64 * j] = sb[j];
+  }
+  __syncthreads();
+  float2* out = reinterpret_cast<float2*>(part + (size_t)blockIdx.x * 2 * d);
+  for (int i = threadIdx.x; i < 2 * NV * 64; i += 256) {
+    const int which = i / (NV * 64), c = i - which * NV * 64;
+    float2 a = red[0][which][c];
+#pragma unroll
+    for (int ww = 1; ww < 4; ++ww) {
+      a.x += red[ww][which][c].x;
+      a.y += red[ww][which][c].y;
+    }
+    out[which * NV * 64 + c] = a;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_ln_gb_reduce(const float* __restrict__ part, int P, int d, float* dgamma,
+                                                      float* dbeta) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= 2 * d) return;
+  float s = 0.f;
+  for (int b = 0; b < P; ++b) s += part[(size_t)b * 2 * d + i];
+  if (i < d) {
+    if (dgamma) dgamma[i] += s;
+  } else if (dbeta) {
+    dbeta[i - d] += s;
+  }
+}
+
+static int ln_gb_blocks(long M) {
+  long P = cdiv(M, 64);
+  if (P > 512) P = 512;
+  return (int)(P < 1 ? 1 : P);
+}
+
+size_t ln_param_grads_workspace_bytes(long M, int d) { return (size_t)ln_gb_blocks(M) * 2 * d * 4 + 256; }
+
+int launch_ln_param_grads(const float* x, const void* dy, int dy_f32, long M, int d, float* dgamma, float* dbeta,
+                          void* workspace, size_t ws_bytes, hipStream_t s) {
+  GWW_REQUIRE(d % 128 == 0 && d >= 128 && d <= 1280, "ln_param_grads: d=%d must be a multiple of 128 <= 1280", d);
+  if (M <= 0 || (!dgamma && !dbeta)) return GWW_OK;
+  const int P = ln_gb_blocks(M);
+  if (!workspace || ws_bytes < ln_param_grads_workspace_bytes(M, d))
+    return fail(GWW_ERR_WORKSPACE, "ln_param_grads: workspace %zu bytes < required %zu", ws_bytes,
+                ln_param_grads_workspace_bytes(M, d));
+  float* part = (float*)workspace;
+#define GWW_LNG(NV)                                                                                                       \
+  case NV:                                                                                                                \
+    if (dy_f32) hipLaunchKernelGGL((k_ln_gb_partial<NV, true>), dim3(P), dim3(256), 0, s, x, dy, M, part);              \
+    else hipLaunchKernelGGL((k_ln_gb_partial<NV, false>), dim3(P), dim3(256), 0, s, x, dy, M, part);                    \
+    break;
+  switch (d / 128) {
+    GWW_LNG(1) GWW_LNG(2) GWW_LNG(3) GWW_LNG(4) GWW_LNG(5) GWW_LNG(6) GWW_LNG(7) GWW_LNG(8) GWW_LNG(9) GWW_LNG(10)
+  }
+#undef GWW_LNG
+  GWW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_ln_gb_reduce, dim3((unsigned)cdiv(2 * d, 256)), dim3(256), 0, s, part, P, d, dgamma, dbeta);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// d embed_positions[t] += sum_b dx0[b, t]  (fp32 [B, T, d]; batch order fixed)
+__global__ __launch_bounds__(256) void k_pos_grad(const float* __restrict__ dx0, float* dpos, int B, long Td) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= Td) return;
+  float s = 0.f;
+  for (int b = 0; b < B; ++b) s += dx0[(size_t)b * Td + i];
+  dpos[i] += s;
+}
+
+int launch_pos_grad(const float* dx0, float* dpos, int B, int T, int d, hipStream_t s) {
+  const long Td = (long)T * d;
+  hipLaunchKernelGGL(k_pos_grad, dim3((unsigned)cdiv(Td, 256)), dim3(256), 0, s, dx0, dpos, B, Td);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
 // ---------------------------------------------------------------- GELU forward / backward (bf16, 8 per lane)
 template <bool BWD>
 __global__ __launch_bounds__(256) void k_gelu_bf16(const unsigned short* __restrict__ z,
@@ -662,6 +788,16 @@ extern "C" int gww_layernorm_bwd(const float* x, const float* gamma, const void*
                                  int accumulate, void* dx_bf16, long M, int d, void* stream) {
   GWW_REQUIRE(x && gamma && dy && dx, "gww_layernorm_bwd: NULL argument");
   return launch_ln_bwd(x, gamma, dy, dy_is_f32, dx, accumulate, dx_bf16, M, d, (hipStream_t)stream);
+}
+
+extern "C" size_t gww_layernorm_param_grads_workspace_bytes(long M, int d) {
+  return (M >= 0 && d > 0) ? ln_param_grads_workspace_bytes(M, d) : 0;
+}
+
+extern "C" int gww_layernorm_param_grads(const float* x, const void* dy, int dy_is_f32, long M, int d, float* dgamma,
+                                         float* dbeta, void* workspace, size_t ws_bytes, void* stream) {
+  GWW_REQUIRE(x && dy && (dgamma || dbeta), "gww_layernorm_param_grads: NULL argument");
+  return launch_ln_param_grads(x, dy, dy_is_f32, M, d, dgamma, dbeta, workspace, ws_bytes, (hipStream_t)stream);
 }
 
 extern "C" int gww_gelu_bf16(const void* z, const void* dgelu_or_null, void* out, long n, void* stream) {

@@ -122,7 +122,7 @@ _HOOKED = False
 def _post_step_sync(*_args, **_kw):
     for enc in list(_TRAINED):
         try:
-            if enc._handle is None or not enc._has_trainable_adapters():
+            if enc._handle is None or not (enc._has_trainable_adapters() or enc.full_finetune):
                 continue
             dev = enc._param_cache()[1][0][1].device
             if dev.type != "cuda":
@@ -173,6 +173,7 @@ class WhisperEncoder(_Tracked):
         # encoder runs inference with or without torch.no_grad(); only an explicit un-freeze (the reference's
         # full_finetune, Signal_vs_Noise/src/train.py:244-250) meets the refusal in _wants_grad.
         self._freeze_parameters()
+        self.full_finetune = False   # enable_full_finetune(): the HIP base-weight backward
         self.precision = precision
         self.gradient_checkpointing = False
         self._handle = None
@@ -182,6 +183,45 @@ class WhisperEncoder(_Tracked):
     # ---- HF surface the reference touches
     def gradient_checkpointing_enable(self, *a, **k):
         self.gradient_checkpointing = True   # activations are recomputed-by-design in the HIP backward
+
+    def enable_full_finetune(self) -> "WhisperEncoder":
+        """Opt in to full fine-tuning (Signal_vs_Noise/src/train.py:243-247 ``--method full_finetune``,
+        Glitch_classification/src/train_full_finetune.py): afterwards the base parameters that require grad get their
+        gradients from the HIP base-weight backward (gww_encoder_train_backward_full); the others stay frozen.  Without
+        this call an un-frozen base parameter is refused (_wants_grad).  DoRA / LoRA adapters cannot be combined with it
+        -- the reference never mixes them -- and only precision='bf16' has a training step."""
+        if self.precision != "bf16":
+            raise _lib.GwwError("full fine-tuning is implemented for precision='bf16'")
+        if self._has_adapters():
+            raise _lib.GwwError("enable_full_finetune(): the encoder carries DoRA / LoRA adapters; full fine-tuning "
+                                "trains the base weights and does not combine with adapters")
+        self.full_finetune = True
+        return self
+
+    def _has_adapters(self) -> bool:
+        return any("lora_" in n for n, _ in self._param_cache()[1])
+
+    def save_pretrained(self, save_directory: str):
+        """HF ``WhisperEncoder.save_pretrained`` layout (Signal_vs_Noise/src/train.py:196 saves a fully fine-tuned
+        encoder this way): ``config.json`` with WhisperConfig field names and ``model.safetensors`` whose keys are the
+        HF encoder ``state_dict`` keys (what ``--encoder-weights`` / ``load_state_dict`` read back)."""
+        import json
+        import os
+
+        from safetensors.torch import save_file
+        if self._has_adapters():
+            raise _lib.GwwError("save_pretrained() of an adapted encoder: save the adapter through the PeftModel")
+        os.makedirs(save_directory, exist_ok=True)
+        c = self.config
+        cfg = {"model_type": "whisper", "architectures": ["WhisperEncoder"], "d_model": c.d_model,
+               "encoder_layers": c.encoder_layers, "encoder_attention_heads": c.encoder_attention_heads,
+               "encoder_ffn_dim": c.encoder_ffn_dim, "num_mel_bins": c.num_mel_bins,
+               "max_source_positions": c.max_source_positions, "dropout": c.dropout, "activation_function": "gelu",
+               "scale_embedding": False, "torch_dtype": "float32"}
+        with open(os.path.join(save_directory, "config.json"), "w") as f:
+            json.dump(cfg, f, indent=2, sort_keys=True)
+        sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}
+        save_file(sd, os.path.join(save_directory, "model.safetensors"), metadata={"format": "pt"})
 
     def _freeze_parameters(self):
         for p in self.parameters():
@@ -378,6 +418,11 @@ class WhisperEncoder(_Tracked):
         if not any(p.requires_grad for _, p in named):
             return torch.is_tensor(input_features) and input_features.requires_grad
         base_trainable = [n for n, p in named if p.requires_grad and "lora_" not in n]
+        if self.full_finetune:
+            if self._has_adapters():
+                raise _lib.GwwError("WhisperEncoder: full fine-tuning is enabled and DoRA / LoRA adapters are attached: "
+                                    "the two do not combine")
+            return bool(base_trainable) or (torch.is_tensor(input_features) and input_features.requires_grad)
         if base_trainable:
             raise _lib.GwwError(
                 "WhisperEncoder: autograd is on and base parameters require grad (e.g. " + base_trainable[0] + "): only "

@@ -465,6 +465,47 @@ def layernorm_bwd(x, gamma, dy, dx=None, want_bf16: bool = False):
     return dx, dxb
 
 
+def gemm_wgrad(dy, x, dw=None, db=None, alpha: float = 1.0, rows: int | None = None, k: int | None = None):
+    """Weight-gradient GEMM: dw[N, K] += alpha dy[:rows]^T x[:rows, :K] (fp32, created as zeros when None) and, with
+    ``db`` (a tensor, or True for a fresh one), db[N] += alpha sum_m dy[m].  dy / x are bf16 2-D tensors whose rows may
+    be strided (``x`` may be an overlapping im2col view made with ``as_strided``: then pass ``k``).  Deterministic:
+    the M reduction runs in a fixed order.  Returns (dw, db | None)."""
+    if dy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or not dy.is_cuda or not x.is_cuda:
+        raise _lib.GwwError("gemm_wgrad: dy and x must be bf16 GPU tensors")
+    if dy.stride(1) != 1 or x.stride(1) != 1:
+        raise _lib.GwwError("gemm_wgrad: rows must be contiguous")
+    M = dy.shape[0] if rows is None else int(rows)
+    N = dy.shape[1]
+    K = x.shape[1] if k is None else int(k)
+    if dw is None:
+        dw = torch.zeros((N, K), dtype=torch.float32, device=dy.device)
+    if db is True:
+        db = torch.zeros((N,), dtype=torch.float32, device=dy.device)
+    need = lib().gww_gemm_wgrad_workspace_bytes(M, N, K)
+    ws = torch.empty((max(need, 1),), dtype=torch.uint8, device=dy.device)
+    with torch.cuda.device(dy.device):
+        check(lib().gww_gemm_wgrad_bf16(dy.data_ptr(), dy.stride(0), x.data_ptr(), x.stride(0), M, N, K, float(alpha),
+                                        dw.data_ptr(), db.data_ptr() if db is not None else None, ws.data_ptr(),
+                                        ws.numel(), _stream()), "gww_gemm_wgrad_bf16")
+    return dw, db
+
+
+def layernorm_param_grads(x, dy, dgamma=None, dbeta=None):
+    """dgamma += sum_m dy * LayerNorm-normalised x, dbeta += sum_m dy (eps 1e-5; fp32, zeros when None; dy fp32 or
+    bf16).  Deterministic fixed-order reduction.  Returns (dgamma, dbeta)."""
+    x = _dev(x, torch.float32, "x")
+    M, d = x.shape
+    dy = _dev(dy)
+    dgamma = torch.zeros(d, dtype=torch.float32, device=x.device) if dgamma is None else dgamma
+    dbeta = torch.zeros(d, dtype=torch.float32, device=x.device) if dbeta is None else dbeta
+    ws = torch.empty((lib().gww_layernorm_param_grads_workspace_bytes(M, d),), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().gww_layernorm_param_grads(x.data_ptr(), dy.data_ptr(), int(dy.dtype == torch.float32), M, d,
+                                              dgamma.data_ptr(), dbeta.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "gww_layernorm_param_grads")
+    return dgamma, dbeta
+
+
 def gelu_bf16(z, dgelu=None):
     z = _dev(z, torch.bfloat16, "z")
     out = torch.empty_like(z)

@@ -10,6 +10,9 @@ DoRA-wrapped q / k / v projection to autograd, so the reference's step
 
 works with the MLP head, the loss and AdamW in plain torch on the GPU and everything inside the
 encoder in libgww.  The DoRA weight norm is detached exactly like peft 0.12.0 ``dora.py``.
+
+With ``WhisperEncoder.enable_full_finetune()`` the base parameters that require grad are inputs of the same autograd
+node, and the backward is ``gww_encoder_train_backward_full`` with their fp32 gradient buffers.
 """
 
 from __future__ import annotations
@@ -24,6 +27,36 @@ from ._lib import check, lib
 from .peft import DoraLinear
 
 _PROJ = {"q_proj": 0, "k_proj": 1, "v_proj": 2, "out_proj": 3}
+
+
+# base parameters in the order of gww_enc_grads / gww_enc_layer_grads (include/gww.h)
+_GLOBAL_GRADS = (("conv1_w", "conv1.weight"), ("conv1_b", "conv1.bias"), ("conv2_w", "conv2.weight"),
+                 ("conv2_b", "conv2.bias"), ("pos", "embed_positions.weight"), ("ln_w", "layer_norm.weight"),
+                 ("ln_b", "layer_norm.bias"))
+_LAYER_GRADS = (("ln1_w", "self_attn_layer_norm.weight"), ("ln1_b", "self_attn_layer_norm.bias"),
+                ("q_w", "self_attn.q_proj.weight"), ("q_b", "self_attn.q_proj.bias"), ("k_w", "self_attn.k_proj.weight"),
+                ("v_w", "self_attn.v_proj.weight"), ("v_b", "self_attn.v_proj.bias"),
+                ("o_w", "self_attn.out_proj.weight"), ("o_b", "self_attn.out_proj.bias"),
+                ("ln2_w", "final_layer_norm.weight"), ("ln2_b", "final_layer_norm.bias"),
+                ("fc1_w", "fc1.weight"), ("fc1_b", "fc1.bias"), ("fc2_w", "fc2.weight"), ("fc2_b", "fc2.bias"))
+
+
+def base_targets(encoder):
+    """[(field, layer index or None, parameter)] of the trainable base parameters (full fine-tuning only)."""
+    if not encoder.full_finetune:
+        return []
+    out = []
+    get = lambda mod, path: mod.get_parameter(path)
+    for field, path in _GLOBAL_GRADS:
+        p = get(encoder, path)
+        if p.requires_grad:
+            out.append((field, None, p))
+    for li, layer in enumerate(encoder.layers):
+        for field, path in _LAYER_GRADS:
+            p = get(layer, path)
+            if p.requires_grad:
+                out.append((field, li, p))
+    return out
 
 
 def dora_targets(encoder):
@@ -49,7 +82,9 @@ class _EncoderTrain(torch.autograd.Function):
             enc._sync_weights()
             _encoder._note_training(enc)   # from now on the packed weights follow every optimizer step at once
             h = enc._ensure_handle()
-            ws = torch.empty((lib().gww_train_workspace_bytes(h, B),), dtype=torch.uint8, device=dev)
+            full = bool(base_targets(enc))
+            ws_bytes = lib().gww_train_workspace_bytes_full(h, B) if full else lib().gww_train_workspace_bytes(h, B)
+            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
             saved = torch.empty((lib().gww_train_saved_bytes(h, B),), dtype=torch.uint8, device=dev)
             shape = (B, c.d_model) if pooled else (B, c.max_source_positions, c.d_model)
             hidden = torch.empty(shape, dtype=torch.float32, device=dev)
@@ -103,15 +138,30 @@ class _EncoderTrain(torch.autograd.Function):
                                      nrm.data_ptr(), dA.data_ptr(), dB.data_ptr(), dm.data_ptr())
         # gradient w.r.t. the input features (conv stem backward) only when autograd asks for it
         d_mel = torch.empty(ctx.mel_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+        base = base_targets(enc)
+        base_ret = []
+        if base:
+            gl = _lib.EncGrads()
+            layers = (_lib.EncLayerGrads * len(enc.layers))()
+            gl.layers = layers
+            for field, li, p in base:
+                buf, ret = grad_buffer(p, p.detach())
+                keep.append(buf)
+                base_ret.append(ret)
+                setattr(gl if li is None else layers[li], field, buf.data_ptr())
         with torch.cuda.device(dev):
-            check(lib().gww_encoder_train_backward(enc._ensure_handle(), B, ctx.ws.data_ptr(), ctx.ws.numel(),
-                                                   ctx.saved.data_ptr(), ctx.saved.numel(), d_hidden.data_ptr(), arr,
-                                                   len(targets), None, d_mel.data_ptr() if d_mel is not None else None,
-                                                   int(ctx.pooled), torch.cuda.current_stream().cuda_stream),
-                  "gww_encoder_train_backward")
+            args = (enc._ensure_handle(), B, ctx.ws.data_ptr(), ctx.ws.numel(), ctx.saved.data_ptr(), ctx.saved.numel(),
+                    d_hidden.data_ptr(), arr, len(targets), None, d_mel.data_ptr() if d_mel is not None else None,
+                    int(ctx.pooled))
+            stream = torch.cuda.current_stream().cuda_stream
+            if base:
+                check(lib().gww_encoder_train_backward_full(*args, C.byref(gl), stream), "gww_encoder_train_backward_full")
+            else:
+                check(lib().gww_encoder_train_backward(*args, stream), "gww_encoder_train_backward")
         flat = []
         for g in grads:
             flat += list(g)
+        flat += base_ret
         assert len(flat) == ctx.n_params
         ctx.ws = ctx.saved = None
         return (None, d_mel, None, *flat)
@@ -129,4 +179,5 @@ def encoder_train_forward(encoder, mel: torch.Tensor, pooled: bool = False) -> t
         params += [mod.lora_A[mod.adapter].weight, mod.lora_B[mod.adapter].weight]
         if mod.use_dora:
             params.append(mod.lora_magnitude_vector[mod.adapter].weight)
+    params += [p for _, _, p in base_targets(encoder)]   # full fine-tuning (enable_full_finetune)
     return _EncoderTrain.apply(encoder, mel, bool(pooled), *params)

@@ -19,7 +19,11 @@ Differences that come with the hardware path:
   * scalars go to ``<log-dir>/train_log.jsonl`` (TensorBoard is not installed);
   * under ``torchrun`` every rank trains on its shard of each epoch and the trainable gradients are all-reduced
     in ONE flat bucket (RCCL).
-``--method DoRA`` (the reference default) and ``--method LoRA`` have a HIP backward; ``full_finetune`` raises.
+``--method DoRA`` (the reference default), ``--method LoRA`` and ``--method full_finetune`` have a HIP backward.
+``full_finetune`` follows ``src/train.py:243-247``: no adapters, ``requires_grad = True`` on every encoder and head
+parameter (``embed_positions`` included), AdamW over them, and the encoder saved by ``WhisperEncoder.save_pretrained``
+(``config.json`` + ``model.safetensors``, HF key names) under the reference's ``[best_]lora_weights_<r>_<alpha>`` name;
+``--encoder-weights <dir>/model.safetensors`` loads it back.
 """
 import argparse
 import fnmatch
@@ -109,11 +113,16 @@ def main(args):
     patterns = ["layers.*.self_attn.q_proj", "layers.*.self_attn.k_proj", "layers.*.self_attn.v_proj",
                 "layers.*.self_attn.o_proj"]                          # src/train.py:232 (o_proj matches nothing in HF Whisper)
     matched = [m for p in patterns for m in fnmatch.filter(module_names, p)]
-    if args.method not in ("DoRA", "LoRA"):
-        # src/train.py:244-250: full_finetune trains every base weight -- that needs weight-gradient GEMMs for all 40
-        # dense panels and the stem, which this hot path (frozen base) does not build
-        raise NotImplementedError("--method DoRA and LoRA have a HIP backward; full_finetune is out of scope (DESIGN.md section 6)")
-    if args.load_model_path:
+    if args.method not in ("DoRA", "LoRA", "full_finetune"):
+        raise ValueError(f"--method {args.method}: expected DoRA, LoRA or full_finetune")
+    if args.method == "full_finetune":
+        # src/train.py:243-247: the bare encoder, every parameter trainable (embed_positions included); the HIP
+        # base-weight backward is an explicit opt-in of the encoder
+        if args.load_model_path:
+            raise ValueError("--load_model_path resumes an adapter; a fully fine-tuned encoder is loaded with "
+                             "--encoder-weights <dir>/model.safetensors")
+        peft = encoder.enable_full_finetune().to(device)
+    elif args.load_model_path:
         # resume (src/train.py:44-60): the saved adapter is loaded onto the BARE encoder -- PeftModel.from_pretrained
         # wraps the nn.Linear targets itself -- and stays trainable
         from gw_whisper_amd.peft import PeftModel
@@ -127,9 +136,13 @@ def main(args):
     else:
         peft = get_peft_model(encoder, LoraConfig(use_dora=args.method == "DoRA", r=args.lora_rank,   # src/train.py:253, :263
                                                   lora_alpha=args.lora_alpha, target_modules=matched)).to(device)
-    for name, p in peft.named_parameters():
-        p.requires_grad = "lora" in name
+    if args.method != "full_finetune":
+        for name, p in peft.named_parameters():
+            p.requires_grad = "lora" in name
     model = two_channel_ligo_binary_classifier(peft).to(device)
+    if args.method == "full_finetune":
+        for p in model.parameters():   # src/train.py:246-247
+            p.requires_grad = True
     if args.load_model_path:
         model.classifier.load_state_dict(torch.load(_resume_path(args.load_model_path, args.load_dense_weights),
                                                     map_location=device))

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7: + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -219,6 +219,52 @@ int gww_encoder_train_backward(gww_encoder* enc, int batch, void* workspace, siz
  * [batch, n_mels, t_in] gradient w.r.t. the input features through the conv stem -- the encoder call is
  * differentiable w.r.t. its input, as MLGWSC-1/train.py:494-504 (trainable Q-adapter in front of the frozen
  * encoder) requires. */
+
+/* --------------------------------------------------------------------------
+ * Full fine-tuning (bf16): the same backward, plus the gradients of the base parameters
+ * (Signal_vs_Noise/src/train.py:243-247 `--method full_finetune`, Glitch_classification/src/
+ * train_full_finetune.py).  Every pointer is an fp32 buffer in the parameter's HF layout
+ * (conv weights [out, in, 3]); NULL = gradient not wanted.  Gradients are ACCUMULATED into.
+ * -------------------------------------------------------------------------- */
+typedef struct {
+  float* ln1_w; float* ln1_b;
+  float* q_w; float* q_b;
+  float* k_w;
+  float* v_w; float* v_b;
+  float* o_w; float* o_b;
+  float* ln2_w; float* ln2_b;
+  float* fc1_w; float* fc1_b;
+  float* fc2_w; float* fc2_b;
+} gww_enc_layer_grads;
+typedef struct {
+  float* conv1_w; float* conv1_b;
+  float* conv2_w; float* conv2_b;
+  float* pos;
+  float* ln_w; float* ln_b;
+  const gww_enc_layer_grads* layers;   /* n_layers entries, or NULL: no per-layer gradient */
+} gww_enc_grads;
+/* workspace of a backward with base gradients (>= gww_train_workspace_bytes; the saved arena is unchanged) */
+size_t gww_train_workspace_bytes_full(const gww_encoder* enc, int batch);
+/* gww_encoder_train_backward + base-parameter gradients (grads may be NULL: then identical to it).  The workspace must
+ * hold gww_train_workspace_bytes_full bytes whenever grads requests anything. */
+int gww_encoder_train_backward_full(gww_encoder* enc, int batch, void* workspace, size_t workspace_bytes,
+                                    const void* saved, size_t saved_bytes, const float* d_last_hidden,
+                                    const gww_dora_target* targets, int n_targets, float* d_x0, float* d_mel,
+                                    int pooled, const gww_enc_grads* grads, void* stream);
+
+/* Weight-gradient GEMM (csrc/wgrad.hip): dW[N,K] += alpha * sum_m dY[m,n] X[m,k], db[N] += alpha * sum_m dY[m,n]
+ * (db may be NULL).  dY [M, ldy] and X [M, ldx] bf16 row-major, 16-byte aligned; dW, db fp32.  The reduction over M
+ * is split across workgroups into fp32 partial slabs summed in a fixed order: two identical calls give identical
+ * bits.  N % 64 == 0, K % 16 == 0, ldy and ldx multiples of 8; X may be a strided (overlapping) view, e.g. the
+ * im2col view of a conv input (ldx < K).  workspace: gww_gemm_wgrad_workspace_bytes(M, N, K) bytes. */
+size_t gww_gemm_wgrad_workspace_bytes(long M, int N, int K);
+int gww_gemm_wgrad_bf16(const void* dY, long ldy, const void* X, long ldx, long M, int N, int K, float alpha,
+                        float* dW, float* db_or_null, void* workspace, size_t ws_bytes, void* stream);
+/* LayerNorm gain / bias gradients: dgamma += sum_m dy * xhat, dbeta += sum_m dy (x fp32 [M, d], dy fp32 or bf16;
+ * eps 1e-5; either output may be NULL; fixed-order reduction).  d % 128 == 0, d <= 1280. */
+size_t gww_layernorm_param_grads_workspace_bytes(long M, int d);
+int gww_layernorm_param_grads(const float* x, const void* dy, int dy_is_f32, long M, int d, float* dgamma,
+                              float* dbeta, void* workspace, size_t ws_bytes, void* stream);
 
 /* --------------------------------------------------------------------------
  * Kernel-level entry points (used by the parity tests and by the Python
