@@ -61,10 +61,12 @@ SIGNATURES = {
     "gww_version": (C.c_int, []),
     "gww_last_error": (C.c_char_p, []),
     "gww_frontend_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "gww_frontend_create_nmel": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "gww_frontend_destroy": (None, [C.c_void_p]),
     "gww_logmel_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p,
                                  C.c_void_p, C.c_void_p]),
     "gww_logmel_host_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]),
+    "gww_logmel_host_nmel_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p]),
     "gww_encoder_create": (C.c_int, [C.POINTER(EncCfg), C.POINTER(C.c_void_p)]),
     "gww_encoder_destroy": (None, [C.c_void_p]),
     "gww_encoder_set_weights": (C.c_int, [C.c_void_p, C.POINTER(EncGlobals), C.POINTER(EncLayer),

@@ -92,7 +92,8 @@ struct LayerW {
   unsigned short *wqkvT, *woT, *w1T, *w2T;
 };
 
-constexpr int kConv1Kpad = 256;   // 3 * 80 = 240 padded to a multiple of 64
+// conv1's K (3 taps x n_mels) padded to a multiple of 64: 256 for 80 mels, 384 for 128 (whisper-large-v3)
+constexpr int conv1_kpad(int n_mels) { return (3 * n_mels + 63) / 64 * 64; }
 
 size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
@@ -129,18 +130,18 @@ extern "C" int gww_encoder_create(const gww_enc_cfg* cfg, gww_encoder** out) {
   GWW_REQUIRE(d > 0 && d % 128 == 0 && d <= 1280, "gww_encoder_create: d_model=%d must be a multiple of 128 <= 1280", d);
   GWW_REQUIRE(H * 64 == d, "gww_encoder_create: n_heads=%d * 64 != d_model=%d (Whisper head_dim is 64)", H, d);
   GWW_REQUIRE(L > 0 && F > 0 && F % 64 == 0, "gww_encoder_create: bad n_layers=%d / ffn=%d", L, F);
-  GWW_REQUIRE(C == 80, "gww_encoder_create: n_mels=%d (only 80 is supported)", C);
+  GWW_REQUIRE(C == 80 || C == 128, "gww_encoder_create: n_mels=%d (80, or 128 for large-v3)", C);
   GWW_REQUIRE(cfg->t_in > 0 && cfg->t_in % 2 == 0, "gww_encoder_create: t_in=%d must be even", cfg->t_in);
-  const int T = cfg->t_in / 2;
+  const int T = cfg->t_in / 2, Kc1 = conv1_kpad(C);
 
   gww_encoder* e = new gww_encoder();
   e->cfg = *cfg;
   // carve one allocation
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-  const size_t o_c1w = take((size_t)d * kConv1Kpad * 2), o_c2w = take((size_t)((d + 255) / 256 * 256) * 3 * d * 2);   // rows d .. : zero padding (k_gemm_bf16_v4 takes N % 256 == 0)
-  const size_t o_c1w32 = take((size_t)d * kConv1Kpad * 4), o_c2w32 = take((size_t)d * 3 * d * 4);
-  const size_t o_c1wT = take((size_t)d * kConv1Kpad * 2), o_c2wT = take((size_t)d * 3 * d * 2);
+  const size_t o_c1w = take((size_t)d * Kc1 * 2), o_c2w = take((size_t)((d + 255) / 256 * 256) * 3 * d * 2);   // rows d .. : zero padding (k_gemm_bf16_v4 takes N % 256 == 0)
+  const size_t o_c1w32 = take((size_t)d * Kc1 * 4), o_c2w32 = take((size_t)d * 3 * d * 4);
+  const size_t o_c1wT = take((size_t)d * Kc1 * 2), o_c2wT = take((size_t)d * 3 * d * 2);
   const size_t o_c1b = take(d * 4), o_c2b = take(d * 4), o_pos = take((size_t)T * d * 4);
   const size_t o_lnw = take(d * 4), o_lnb = take(d * 4);
   struct LO { size_t wqkv, wo, w1, w2, wqkv32, wo32, w132, w232, bqkv, bqkv16, bo, b1, b2, ln1w, ln1b, ln2w, ln2b,
@@ -285,7 +286,7 @@ extern "C" void gww_encoder_destroy(gww_encoder* e) {
 //   2 = out_proj          4 = fc1 + final_layer_norm          8 = fc2
 static int pack_weights(gww_encoder* e, const gww_enc_globals* g, const gww_enc_layer* layers, int n_layers,
                         const unsigned* dirty, hipStream_t s) {
-  const int d = e->cfg.d_model, F = e->cfg.ffn, C = e->cfg.n_mels, T = e->cfg.t_in / 2;
+  const int d = e->cfg.d_model, F = e->cfg.ffn, C = e->cfg.n_mels, T = e->cfg.t_in / 2, Kc1 = conv1_kpad(C);
   const float qs = 0.125f;   // head_dim^-0.5 = 64^-0.5, exact power of two (HF:modeling_whisper.py:309)
   // Two dependency phases, one k_prep_batch launch each (per 40 ops): `pb` reads only the caller's fp32 tensors, `pt` (the
   // transposes for the backward's dX GEMMs) reads panels `pb` wrote.  A DoRA step on whisper-tiny used to enqueue ~75 launches
@@ -300,10 +301,10 @@ static int pack_weights(gww_encoder* e, const gww_enc_globals* g, const gww_enc_
   if (g) {
     GWW_REQUIRE(g->conv1_w && g->conv1_b && g->conv2_w && g->conv2_b && g->pos && g->ln_w && g->ln_b,
                 "gww_encoder_set_weights: NULL global weight");
-    GWW_TRY(pack(g->conv1_w, e->c1w, e->c1w32, d, C, 3, kConv1Kpad, 1.f));
+    GWW_TRY(pack(g->conv1_w, e->c1w, e->c1w32, d, C, 3, Kc1, 1.f));
     GWW_TRY(pack(g->conv2_w, e->c2w, e->c2w32, d, d, 3, 3 * d, 1.f));
     if (d % 256 != 0) GWW_HIP(hipMemsetAsync(e->c2w + (size_t)d * 3 * d, 0, (size_t)((d + 255) / 256 * 256 - d) * 3 * d * 2, s));
-    GWW_TRY(pt.transpose(e->c1w, e->c1wT, d, kConv1Kpad));
+    GWW_TRY(pt.transpose(e->c1w, e->c1wT, d, Kc1));
     GWW_TRY(pt.transpose(e->c2w, e->c2wT, d, 3 * d));
     GWW_TRY(pb.copy(g->conv1_b, e->c1b, d, 1.f));
     GWW_TRY(pb.copy(g->conv2_b, e->c2b, d, 1.f));
@@ -418,14 +419,14 @@ struct WsLayout {
 };
 WsLayout ws_layout(const gww_enc_cfg& c, int B, int precision) {
   const size_t es = precision == GWW_PREC_BF16 ? 2 : 4;
-  const size_t d = c.d_model, F = c.ffn, Tin = c.t_in, T = c.t_in / 2, C = c.n_mels;
+  const size_t d = c.d_model, F = c.ffn, Tin = c.t_in, T = c.t_in / 2, C = c.n_mels, Kc1 = conv1_kpad(c.n_mels);
   WsLayout w{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
   // row-indexed activations are padded so the large-M GEMM can store whole 256-row panels
   // unconditionally (rows past B*T are scratch); +512 covers conv2's remapped garbage rows
   const size_t Mp = ((size_t)B * T + 255) / 256 * 256 + 512;
-  w.melT = take(((size_t)B * (Tin + 2) * C + kConv1Kpad) * es);
+  w.melT = take(((size_t)B * (Tin + 2) * C + Kc1) * es);
   w.c1 = take((((size_t)B * (Tin + 2) + 255) / 256 * 256 + 520) * d * es);   // (+ 520: conv2's 256-row panels read 2 * 255 + 3 rows past the last segment)
   w.x = take(Mp * d * 4);
   w.x2 = take(Mp * d * 4);      // ping-pong partner of x for the fused residual-add prologue
@@ -486,6 +487,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   const bool bf = precision == GWW_PREC_BF16;
   const size_t es = bf ? 2 : 4;
   const int d = e->cfg.d_model, F = e->cfg.ffn, Tin = e->cfg.t_in, T = Tin / 2, C = e->cfg.n_mels, H = e->cfg.n_heads;
+  const int Kc1 = conv1_kpad(C);
   const int B = batch;
   char* base = (char*)workspace;
   void* melT = base + w.melT;
@@ -530,13 +532,13 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   };
 
   // ---- stem
-  // bf16, the widths of whisper-tiny / -base / -small / -medium: conv1 reads the [B, 80, T] features itself (conv1_mel.hip:
+  // bf16, 80 mels at the widths of whisper-tiny / -base / -small / -medium: conv1 reads the [B, 80, T] features itself (conv1_mel.hip:
   // no token-major copy of the input, W-stationary, one launch); otherwise the transposition kernel + a GEMM over its rows
   static const int generic_mask = (int)lab_int("GWW_GENERIC_PATH", 0);   // (0 in the product build)
-  const bool conv1_direct = bf && conv1_mel_supported(C, d, kConv1Kpad) && !(generic_mask & 2);
+  const bool conv1_direct = bf && conv1_mel_supported(C, d, Kc1) && !(generic_mask & 2);
   if (!conv1_direct) {
     TR(TR_MEL, launch_mel_to_tokens(mel, melT, bf ? 1 : 0, B, C, Tin, s));
-    GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * es, 0, kConv1Kpad * es, s));
+    GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * es, 0, Kc1 * es, s));
     GWW_HIP(hipMemsetAsync(c1, 0, (size_t)d * es, s));   // zero row 0 of batch 0 (token -1)
   }
   // A-stationary kernels (A panel in registers, fused residual-add + LayerNorm prologue) for K = d <= 512
@@ -554,9 +556,9 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
     TR(TR_CONV1, launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s));
   else if (bf && d % 128 == 0 && !(generic_mask & 2))
     TR(TR_CONV1, launch_gemm_astat(melT, C, nullptr, nullptr, nullptr, nullptr, e->c1w, e->c1b, c1,
-                                   (long)B * (Tin + 2), d, kConv1Kpad, EPI_CONV1, Tin + 2, s));
+                                   (long)B * (Tin + 2), d, Kc1, EPI_CONV1, Tin + 2, s));
   else
-    TR(TR_CONV1, gemm(melT, C, e->c1w, e->c1w32, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, kConv1Kpad,
+    TR(TR_CONV1, gemm(melT, C, e->c1w, e->c1w32, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, Kc1,
                       EPI_CONV1, Tin + 2));
   if (bf && d % 128 == 0 && d <= 3072 && !(generic_mask & 4))   // the eight-phase 256 x 256 GEMM over overlapping rows (gemm_v4.hip)
     TR(TR_CONV2, launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), (d + 255) / 256 * 256, 3 * d,
@@ -759,11 +761,12 @@ struct TrainWs {
 };
 TrainWs train_ws(const gww_enc_cfg& c, int B) {
   const size_t d = c.d_model, F = c.ffn, Tin = c.t_in, T = c.t_in / 2, C = c.n_mels, H = c.n_heads;
+  const size_t Kc1 = conv1_kpad(c.n_mels);
   const size_t Mp = ((size_t)B * T + 255) / 256 * 256 + 512;
   TrainWs w{};
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-  w.melT = take(((size_t)B * (Tin + 2) * C + kConv1Kpad) * 2);
+  w.melT = take(((size_t)B * (Tin + 2) * C + Kc1) * 2);
   w.c1 = take((((size_t)B * (Tin + 2) + 255) / 256 * 256 + 520) * d * 2);
   w.h2 = take(Mp * d * 2);      // per-op path: LN2 output; fused path: out_proj delta (fwd), recomputed LN1 output (bwd)
   w.f1 = take(Mp * F * 2);      // per-op path: gelu(fc1); fused path: recomputed pre-GELU fc1 output (bwd)
@@ -776,7 +779,7 @@ TrainWs train_ws(const gww_enc_cfg& c, int B) {
   w.dqkv = take(Mp * 3 * d * 2);
   w.Dv = take((size_t)B * H * (T + (T + 63) / 64) * 4);   // row dots + live-tile flags
   w.z1 = take(((size_t)B * (Tin + 2) + 256) * d * 2);            // stem backward: conv1 pre-activation / its gradient
-  w.col1 = take(((size_t)B * (Tin + 2) + 256) * kConv1Kpad * 2); // stem backward: conv1 taps side by side
+  w.col1 = take(((size_t)B * (Tin + 2) + 256) * Kc1 * 2); // stem backward: conv1 taps side by side
   w.dgs_bytes = (d == 384 || d == 512) ? dora_grads_scratch_bytes(3, (int)d)        // DoRA-gradient partial sums
                 : d == 768 ? dora_grads_scratch_bytes(1, (int)d) : 0;
   w.dgs = take(w.dgs_bytes);
@@ -803,7 +806,7 @@ static size_t train_param_scratch_bytes(const gww_enc_cfg& c, int B) {
     mx = std::max(mx, ln_param_grads_workspace_bytes(m, (int)d));
   }
   mx = std::max(mx, wgrad_workspace_bytes((long)B * (T + 1), (int)d, 3 * (int)d));
-  mx = std::max(mx, wgrad_workspace_bytes((long)B * (c.t_in + 2), (int)d, kConv1Kpad));
+  mx = std::max(mx, wgrad_workspace_bytes((long)B * (c.t_in + 2), (int)d, conv1_kpad(c.n_mels)));
   return align_up(mx);
 }
 
@@ -831,6 +834,7 @@ extern "C" int gww_encoder_train_forward(gww_encoder* e, const float* mel, int b
                 workspace_bytes, saved_bytes, w.total, sl.total);
   hipStream_t s = (hipStream_t)stream;
   const int d = e->cfg.d_model, F = e->cfg.ffn, Tin = e->cfg.t_in, T = Tin / 2, C = e->cfg.n_mels, H = e->cfg.n_heads;
+  const int Kc1 = conv1_kpad(C);
   const int B = batch, L = e->cfg.n_layers;
   const long M = (long)B * T;
   char* base = (char*)workspace;
@@ -842,15 +846,15 @@ extern "C" int gww_encoder_train_forward(gww_encoder* e, const float* mel, int b
   auto x_in = [&](int l) -> float* { return (float*)(sv + (l < L ? (size_t)l * sl.layer_stride + sl.x_in : (size_t)L * sl.layer_stride)); };
   // ---- stem (same kernels as inference) -> x_in[0]
   GWW_TRY(launch_mel_to_tokens(mel, melT, 1, B, C, Tin, s));
-  GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * 2, 0, kConv1Kpad * 2, s));
+  GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * 2, 0, Kc1 * 2, s));
   GWW_HIP(hipMemsetAsync(c1, 0, (size_t)d * 2, s));
   if (train_fused(e->cfg)) {   // the inference stem kernels (A-stationary conv1, full-N conv2)
     GWW_TRY(launch_gemm_astat(melT, C, nullptr, nullptr, nullptr, nullptr, e->c1w, e->c1b, c1, (long)B * (Tin + 2), d,
-                              kConv1Kpad, EPI_CONV1, Tin + 2, s));
+                              Kc1, EPI_CONV1, Tin + 2, s));
     GWW_TRY(launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x_in(0), (long)B * (T + 1), (d + 255) / 256 * 256, 3 * d,
                                 EPI_CONV2, s, 0, e->pos, T + 1, d, (float*)h2));   // (h2 is idle here: the scratch row of the garbage rows)
   } else {
-    GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, kConv1Kpad, EPI_CONV1,
+    GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, Kc1, EPI_CONV1,
                              Tin + 2, s, 0));
     GWW_TRY(launch_gemm_bf16(c1, 2L * d, e->c2w, e->c2b, nullptr, e->pos, x_in(0), (long)B * (T + 1), d, 3 * d, EPI_CONV2,
                              T + 1, s, 1));
@@ -1202,7 +1206,7 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
   if (d_mel || want_conv1 || want_conv2) {
     // ---- conv stem backward: x0 = gelu(conv2(gelu(conv1(mel)))) + pos (melT and c1 of the forward are still
     // in the workspace); the pre-activations are recomputed by the same GEMMs with a plain bias epilogue
-    const int Tin = e->cfg.t_in, C = e->cfg.n_mels;
+    const int Tin = e->cfg.t_in, C = e->cfg.n_mels, Kc1 = conv1_kpad(C);
     GWW_REQUIRE(B <= 512, "gww_encoder_train_backward: d_mel and the conv-stem gradients support batch <= 512");
     const void* melT = base + w.melT;
     const void* c1 = base + w.c1;
@@ -1216,14 +1220,14 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
     if (want_conv2) GWW_TRY(wg(dctx, d, c1, 2L * d, M2, d, 3 * d, 1.0f, grads->conv2_w, grads->conv2_b, d));
     if (d_mel || want_conv1) {
       GWW_TRY(launch_gemm_bf16(dctx, d, e->c2wT, nullptr, nullptr, nullptr, dqkv, M2, 3 * d, d, EPI_BIAS, 0, s, 0));   // col
-      GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, z1, M1, d, kConv1Kpad, EPI_BIAS, 0, s, 0));  // z1
+      GWW_TRY(launch_gemm_bf16(melT, C, e->c1w, e->c1b, nullptr, nullptr, z1, M1, d, Kc1, EPI_BIAS, 0, s, 0));  // z1
       GWW_TRY(launch_stem_dz1(dqkv, z1, z1, B, T, Tin, d, s));                                                        // dz1
-      // conv1 weight gradient on the im2col view of melT (K = kConv1Kpad: taps 0..2 of C channels + padding, dropped)
-      if (want_conv1) GWW_TRY(wg(z1, d, melT, C, M1, d, kConv1Kpad, 1.0f, grads->conv1_w, grads->conv1_b, C));
+      // conv1 weight gradient on the im2col view of melT (K = Kc1: taps 0..2 of C channels + padding, dropped)
+      if (want_conv1) GWW_TRY(wg(z1, d, melT, C, M1, d, Kc1, 1.0f, grads->conv1_w, grads->conv1_b, C));
     }
     if (d_mel) {
-      GWW_TRY(launch_gemm_bf16(z1, d, e->c1wT, nullptr, nullptr, nullptr, col1, M1, kConv1Kpad, d, EPI_BIAS, 0, s, 0));  // col1
-      GWW_TRY(launch_stem_dmel(col1, d_mel, B, Tin, C, kConv1Kpad, s));
+      GWW_TRY(launch_gemm_bf16(z1, d, e->c1wT, nullptr, nullptr, nullptr, col1, M1, Kc1, d, EPI_BIAS, 0, s, 0));  // col1
+      GWW_TRY(launch_stem_dmel(col1, d_mel, B, Tin, C, Kc1, s));
     }
   }
   return GWW_OK;

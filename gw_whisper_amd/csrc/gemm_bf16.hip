@@ -589,12 +589,12 @@ int launch_gemm_bf16(const void* A, long lda, const void* W, const float* bias, 
 }
 
 // ---------------------------------------------------------------- mel transpose
-// [B, C=80, T=3000] fp32 (HF input_features layout) -> token-major [B, T + 2, C]
-// with zero rows 0 and T+1 (the Conv1d padding), bf16 or fp32.
-template <typename OutT>
+// [B, C=80 or 128, T=3000] fp32 (HF input_features layout) -> token-major [B, T + 2, C]
+// with zero rows 0 and T+1 (the Conv1d padding), bf16 or fp32.  CW: LDS row stride, C + 4.
+template <typename OutT, int CW>
 __global__ __launch_bounds__(256) void k_mel_to_tokens(const float* __restrict__ mel, OutT* __restrict__ out,
                                                        int C, int T) {
-  __shared__ __attribute__((aligned(16))) float tile[64][84];   // 84: rows stay 16-byte aligned, 4-way-free column walks
+  __shared__ __attribute__((aligned(16))) float tile[64][CW];   // C + 4: rows stay 16-byte aligned, 4-way-free column walks
   const int b = blockIdx.y, t0 = blockIdx.x * 64;
   const float* src = mel + (long)b * C * T;
   // 16 bytes per lane on both sides when the shapes allow it (T % 4 == 0, C % 8 == 0: the Whisper front end's 3000 x 80):
@@ -642,13 +642,20 @@ __global__ __launch_bounds__(256) void k_mel_to_tokens(const float* __restrict__
 }
 
 int launch_mel_to_tokens(const float* mel, void* out, int out_bf16, int B, int C, int T, hipStream_t s) {
-  GWW_REQUIRE(C <= 80, "mel_to_tokens: n_mels=%d > 80 unsupported", C);
+  GWW_REQUIRE(C <= 128, "mel_to_tokens: n_mels=%d > 128 unsupported", C);
   if (B == 0) return GWW_OK;
   dim3 grid((unsigned)cdiv(T, 64), (unsigned)B), block(256);
-  if (out_bf16)
-    hipLaunchKernelGGL(k_mel_to_tokens<unsigned short>, grid, block, 0, s, mel, (unsigned short*)out, C, T);
-  else
-    hipLaunchKernelGGL(k_mel_to_tokens<float>, grid, block, 0, s, mel, (float*)out, C, T);
+  if (C <= 80) {
+    if (out_bf16)
+      hipLaunchKernelGGL((k_mel_to_tokens<unsigned short, 84>), grid, block, 0, s, mel, (unsigned short*)out, C, T);
+    else
+      hipLaunchKernelGGL((k_mel_to_tokens<float, 84>), grid, block, 0, s, mel, (float*)out, C, T);
+  } else {
+    if (out_bf16)
+      hipLaunchKernelGGL((k_mel_to_tokens<unsigned short, 132>), grid, block, 0, s, mel, (unsigned short*)out, C, T);
+    else
+      hipLaunchKernelGGL((k_mel_to_tokens<float, 132>), grid, block, 0, s, mel, (float*)out, C, T);
+  }
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }

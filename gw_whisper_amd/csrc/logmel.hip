@@ -3,14 +3,16 @@
 // Replaces WhisperFeatureExtractor.__call__ (reference call sites
 // Signal_vs_Noise/src/dataset.py:20-21; HF:feature_extraction_whisper.py:135-168):
 //   zero-pad to 480000 -> reflect-pad 200 -> 400-pt periodic-Hann DFT, hop 160 ->
-//   |X|^2 (frames 0..2999) -> mel[80,201] @ P -> log10(max(.,1e-10)) ->
+//   |X|^2 (frames 0..2999) -> mel[n_mels,201] @ P -> log10(max(.,1e-10)) ->
 //   per-segment max -> max(x, max-8) -> (x+4)/4.
+// n_mels is 80 (every Whisper size up to large-v2) or 128 (large-v3, large-v3-turbo); the kernels are
+// templates on it, one instantiation each.
 //
 // HBM-bound: 64 KB in + 960 KB out per segment.  Two kernels:
 //   k_logmel_frames    DFT + mel + log10 for the LIVE frames only (frames that can
 //                      see a non-zero sample: ceil((n+200)/160), 102 for 1 s), raw
 //                      log-mel written in place, per-segment max via atomicMax
-//   k_logmel_finalize  streams the whole [80,3000] row: clamp to max-8, affine,
+//   k_logmel_finalize  streams the whole [n_mels,3000] row: clamp to max-8, affine,
 //                      constant fill of the dead frames (float4 stores)
 // The DFT uses the real-input symmetry x[n] +- x[400-n] (half the MACs) with the
 // 400-entry twiddle table and the windowed frames in LDS; fp32 throughout.
@@ -26,7 +28,6 @@ namespace gww {
 constexpr int kNfft = 400;
 constexpr int kHop = 160;
 constexpr int kNfreq = 201;
-constexpr int kNmel = 80;
 constexpr int kFrames = 3000;
 constexpr int kChunk = 480000;
 constexpr int kFT = 8;                      // frames per workgroup
@@ -36,7 +37,7 @@ struct Tables {
   float* win;      // [400]
   float* cost;     // [400] cos(2 pi k / 400)
   float* sint;     // [400]
-  float* fbT;      // [201][80] filterbank, transposed so consecutive mels are contiguous
+  float* fbT;      // [201][n_mels] filterbank, transposed so consecutive mels are contiguous
 };
 
 __device__ __forceinline__ unsigned int fkey(float f) {
@@ -49,6 +50,7 @@ __device__ __forceinline__ float fkey_inv(unsigned int k) {
 }
 
 // grid (tiles, n_seg), 256 threads
+template <int kNmel>
 __global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__ wave, long stride,
                                                        int n_eff, int live, Tables tb,
                                                        float* __restrict__ out,
@@ -170,10 +172,12 @@ constexpr int kMThreads = 512;                    // 8 waves: 7 DFT bin blocks +
 constexpr int kMSpan = kHop * (kMT - 1) + kNfft;  // 5360 samples per tile
 constexpr int kEvS = 205;                         // row stride of ev / od / pw: odd -> conflict-free column reads
 
+template <int kNmel>
 __global__ __launch_bounds__(kMThreads) void k_logmel_frames_mfma(const float* __restrict__ wav, long stride, int n_eff,
                                                             int live, Tables tb, float* __restrict__ out,
                                                             unsigned int* __restrict__ seg_max) {
-  __shared__ __attribute__((aligned(16))) float xs[kMSpan];       // 21.4 KB; reused as the [80][33] output tile
+  static_assert(kNmel * 33 <= kMSpan, "the output tile must fit in xs");
+  __shared__ __attribute__((aligned(16))) float xs[kMSpan];       // 21.4 KB; reused as the [n_mels][33] output tile
   __shared__ float ev[kMT * kEvS];                               // 26.2 KB; reused as the power tile
   __shared__ float od[kMT * kEvS];
   __shared__ float ct[kNfft];
@@ -261,10 +265,13 @@ __global__ __launch_bounds__(kMThreads) void k_logmel_frames_mfma(const float* _
   }
   __syncthreads();
 
-  // ---- mel projection: 3 blocks of 32 mels on waves 0..2; acc[4 c + e] <-> frame 8 c + 4 hh + e, mel on the lane
-  float* tile = xs;                            // [80][33] raw log-mel of this tile
+  // ---- mel projection: n_mels / 32 blocks of 32 mels (3 for 80, 4 for 128) on the first waves;
+  // acc[4 c + e] <-> frame 8 c + 4 hh + e, mel on the lane
+  constexpr int MBLK = (kNmel + 31) / 32;
+  static_assert(MBLK <= kMThreads / 64, "one wave per mel block");
+  float* tile = xs;                            // [n_mels][33] raw log-mel of this tile
   float lmax = -INFINITY;
-  if (wave < 3) {
+  if (wave < MBLK) {
     f32x16 acc;
 #pragma unroll
     for (int j = 0; j < 16; ++j) acc[j] = 0.f;
@@ -318,7 +325,8 @@ __global__ __launch_bounds__(kMThreads) void k_logmel_frames_mfma(const float* _
   }
 }
 
-// grid (80, n_seg), 256 threads: one [3000] row per workgroup
+// grid (n_mels, n_seg), 256 threads: one [3000] row per workgroup
+template <int kNmel>
 __global__ __launch_bounds__(256) void k_logmel_finalize(float* __restrict__ out, int live,
                                                          const unsigned int* __restrict__ seg_max) {
   const int seg = blockIdx.y, m = blockIdx.x;
@@ -364,10 +372,13 @@ using namespace gww;
 struct gww_frontend {
   Tables tb{};
   float* blob = nullptr;
+  int n_mels = 80;
 };
 
-extern "C" int gww_frontend_create(gww_frontend** out) {
-  GWW_REQUIRE(out != nullptr, "gww_frontend_create: out is NULL");
+extern "C" int gww_frontend_create_nmel(int n_mels, gww_frontend** out) {
+  GWW_REQUIRE(out != nullptr, "gww_frontend_create_nmel: out is NULL");
+  GWW_REQUIRE(n_mels == 80 || n_mels == 128, "gww_frontend_create_nmel: n_mels=%d (80 or 128)", n_mels);
+  const int kNmel = n_mels;
   std::vector<float> h(3 * kNfft + kNfreq * kNmel);
   const double pi = 3.14159265358979323846;
   for (int k = 0; k < kNfft; ++k) {
@@ -375,7 +386,7 @@ extern "C" int gww_frontend_create(gww_frontend** out) {
     h[kNfft + k] = (float)cos(2.0 * pi * k / kNfft);
     h[2 * kNfft + k] = (float)sin(2.0 * pi * k / kNfft);
   }
-  // filterbank [201][80] (already "transposed" relative to mel.T @ P)
+  // filterbank [201][n_mels] (already "transposed" relative to mel.T @ P)
   const double mel_min = hz2mel(0.0), mel_max = hz2mel(8000.0);
   std::vector<double> ff(kNmel + 2);
   for (int i = 0; i < kNmel + 2; ++i) ff[i] = mel2hz(mel_min + (mel_max - mel_min) * i / (kNmel + 1));
@@ -391,6 +402,7 @@ extern "C" int gww_frontend_create(gww_frontend** out) {
     }
   }
   gww_frontend* fe = new gww_frontend();
+  fe->n_mels = n_mels;
   hipError_t e = hipMalloc(&fe->blob, h.size() * sizeof(float));
   if (e != hipSuccess) {
     delete fe;
@@ -410,10 +422,33 @@ extern "C" int gww_frontend_create(gww_frontend** out) {
   return GWW_OK;
 }
 
+extern "C" int gww_frontend_create(gww_frontend** out) { return gww_frontend_create_nmel(80, out); }
+
 extern "C" void gww_frontend_destroy(gww_frontend* fe) {
   if (!fe) return;
   if (fe->blob) (void)hipFree(fe->blob);
   delete fe;
+}
+
+template <int kNmel>
+static int launch_logmel(gww_frontend* fe, const float* wave, int n_seg, int n_eff, int live, long wave_stride, float* out,
+                         float* seg_max, hipStream_t s) {
+  static const bool valu_kernel = lab_int("GWW_LOGMEL_VALU", 0) != 0;   // comparison aid (lab build)
+  if (valu_kernel) {
+    dim3 g1((unsigned)cdiv(live, kFT), (unsigned)n_seg);
+    hipLaunchKernelGGL(k_logmel_frames<kNmel>, g1, dim3(256), 0, s, wave, wave_stride, n_eff, live, fe->tb, out,
+                       reinterpret_cast<unsigned int*>(seg_max));
+  } else {
+    dim3 g1((unsigned)cdiv(live, kMT), (unsigned)n_seg);
+    hipLaunchKernelGGL(k_logmel_frames_mfma<kNmel>, g1, dim3(kMThreads), 0, s, wave, wave_stride, n_eff, live, fe->tb, out,
+                       reinterpret_cast<unsigned int*>(seg_max));
+  }
+  GWW_LAUNCH_CHECK();
+  dim3 g2(kNmel, (unsigned)n_seg);
+  hipLaunchKernelGGL(k_logmel_finalize<kNmel>, g2, dim3(256), 0, s, out, live,
+                     reinterpret_cast<const unsigned int*>(seg_max));
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
 }
 
 extern "C" int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, int n_samples,
@@ -432,20 +467,6 @@ extern "C" int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, in
     if (live < 1) live = 1;
   }
   GWW_HIP(hipMemsetAsync(seg_max, 0, sizeof(float) * (size_t)n_seg, s));
-  static const bool valu_kernel = lab_int("GWW_LOGMEL_VALU", 0) != 0;   // comparison aid (lab build)
-  if (valu_kernel) {
-    dim3 g1((unsigned)cdiv(live, kFT), (unsigned)n_seg);
-    hipLaunchKernelGGL(k_logmel_frames, g1, dim3(256), 0, s, wave, wave_stride, n_eff, live, fe->tb, out,
-                       reinterpret_cast<unsigned int*>(seg_max));
-  } else {
-    dim3 g1((unsigned)cdiv(live, kMT), (unsigned)n_seg);
-    hipLaunchKernelGGL(k_logmel_frames_mfma, g1, dim3(kMThreads), 0, s, wave, wave_stride, n_eff, live, fe->tb, out,
-                       reinterpret_cast<unsigned int*>(seg_max));
-  }
-  GWW_LAUNCH_CHECK();
-  dim3 g2(kNmel, (unsigned)n_seg);
-  hipLaunchKernelGGL(k_logmel_finalize, g2, dim3(256), 0, s, out, live,
-                     reinterpret_cast<const unsigned int*>(seg_max));
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return fe->n_mels == 128 ? launch_logmel<128>(fe, wave, n_seg, n_eff, live, wave_stride, out, seg_max, s)
+                           : launch_logmel<80>(fe, wave, n_seg, n_eff, live, wave_stride, out, seg_max, s);
 }

@@ -5,9 +5,9 @@
 // the GPU, so this entry point is plain C++ -- no HIP call, no device memory, no global mutable state (the tables
 // are function-local statics, built once, thread safe since C++11).  Same arithmetic as
 // HF:models/whisper/feature_extraction_whisper.py:135-168: zero-pad to 480000 -> reflect-pad 200 -> 400-point
-// periodic-Hann DFT, hop 160 -> |X|^2 (frames 0..2999) -> mel[80,201] @ P -> log10(max(., 1e-10)) -> per-segment
+// periodic-Hann DFT, hop 160 -> |X|^2 (frames 0..2999) -> mel[n_mels,201] @ P -> log10(max(., 1e-10)) -> per-segment
 // max -> max(x, max - 8) -> (x + 4) / 4, with the same exact shortcut as the device kernel: frames that only see
-// zero padding are the one constant HF produces for them.
+// zero padding are the one constant HF produces for them.  n_mels is 80 or 128 (whisper-large-v3), one table set each.
 //
 // The DFT is a 200-point complex mixed-radix FFT (5 x 5 x 4 x 2, decimation in time) of the even / odd samples of
 // the windowed frame followed by the real-input untangling step; double precision, rounded to fp32 once per mel.
@@ -26,7 +26,7 @@ int fail(int code, const char* fmt, ...);   // elementwise.hip (per-thread error
 
 namespace {
 
-constexpr int kNfft = 400, kHalf = 200, kHop = 160, kNfreq = 201, kNmel = 80, kFrames = 3000, kChunk = 480000;
+constexpr int kNfft = 400, kHalf = 200, kHop = 160, kNfreq = 201, kMaxMel = 128, kFrames = 3000, kChunk = 480000;
 constexpr double kPi = 3.14159265358979323846;
 
 struct Cpx {
@@ -37,7 +37,8 @@ struct HostTables {
   double win[kNfft];
   Cpx w200[kHalf];        // exp(-2 pi i k / 200)
   Cpx w400[kHalf + 1];    // exp(-2 pi i k / 400), k = 0..200
-  // sparse filterbank: HF's dense [201, 80] slaney triangles touch at most a few mels per bin
+  int n_mels;
+  // sparse filterbank: HF's dense [201, n_mels] slaney triangles touch at most a few mels per bin
   int fb_first[kNfreq], fb_count[kNfreq];
   std::vector<float> fb_val;   // the fp32-cast weights HF multiplies with
   std::vector<int> fb_ofs;
@@ -45,7 +46,8 @@ struct HostTables {
   static double hz2mel(double f) { return f >= 1000.0 ? 15.0 + log(f / 1000.0) * (27.0 / log(6.4)) : 3.0 * f / 200.0; }
   static double mel2hz(double m) { return m >= 15.0 ? 1000.0 * exp((log(6.4) / 27.0) * (m - 15.0)) : 200.0 * m / 3.0; }
 
-  HostTables() {
+  explicit HostTables(int nm) : n_mels(nm) {
+    const int kNmel = nm;
     for (int k = 0; k < kNfft; ++k) win[k] = (double)(float)(0.5 - 0.5 * cos(2.0 * kPi * k / kNfft));
     for (int k = 0; k < kHalf; ++k) w200[k] = {cos(2.0 * kPi * k / kHalf), -sin(2.0 * kPi * k / kHalf)};
     for (int k = 0; k <= kHalf; ++k) w400[k] = {cos(2.0 * kPi * k / kNfft), -sin(2.0 * kPi * k / kNfft)};
@@ -60,7 +62,7 @@ struct HostTables {
       fb_count[k] = 0;
       fb_ofs[k] = (int)fb_val.size();
       int last = -1;
-      float row[kNmel];
+      float row[kMaxMel];
       for (int m = 0; m < kNmel; ++m) {
         const double down = (fk - ff[m]) / (ff[m + 1] - ff[m]);
         const double up = (ff[m + 2] - fk) / (ff[m + 2] - ff[m + 1]);
@@ -81,9 +83,9 @@ struct HostTables {
   }
 };
 
-const HostTables& tables() {
-  static const HostTables t;
-  return t;
+const HostTables& tables(int n_mels) {
+  static const HostTables t80(80), t128(128);
+  return n_mels == 128 ? t128 : t80;
 }
 
 // out[0..n) = DFT_n(in[0], in[stride], ...); n divides 200, twiddles from the 200-entry table.
@@ -134,13 +136,16 @@ void frame_power(const double* frame, double* power, const HostTables& tb) {
 
 }  // namespace
 
-extern "C" int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out) {
+extern "C" int gww_logmel_host_nmel_f32(const float* wave, int n_seg, int n_samples, long wave_stride, int n_mels,
+                                        float* out) {
   if (!wave || !out) return gww::fail(GWW_ERR_ARG, "gww_logmel_host_f32: NULL argument");
   if (n_seg < 0 || n_samples < 0) return gww::fail(GWW_ERR_ARG, "gww_logmel_host_f32: negative size");
+  if (n_mels != 80 && n_mels != 128) return gww::fail(GWW_ERR_ARG, "gww_logmel_host_f32: n_mels=%d (80 or 128)", n_mels);
   const int n_eff = n_samples < kChunk ? n_samples : kChunk;   // HF truncates at 30 s
   if (wave_stride < n_eff)
     return gww::fail(GWW_ERR_ARG, "gww_logmel_host_f32: wave_stride %ld < n_samples %d", wave_stride, n_samples);
-  const HostTables& tb = tables();
+  const HostTables& tb = tables(n_mels);
+  const int kNmel = n_mels;
   int live = kFrames;
   if (n_eff < kChunk - kNfft) {
     live = (n_eff + kNfft / 2 + kHop - 1) / kHop;
@@ -160,7 +165,7 @@ extern "C" int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, 
     };
     float seg_max = -INFINITY;
     for (int t = 0; t < live; ++t) {
-      double frame[kNfft], power[kNfreq], mel[kNmel];
+      double frame[kNfft], power[kNfreq], mel[kMaxMel];
       for (int n = 0; n < kNfft; ++n) frame[n] = sample((long)t * kHop + n) * tb.win[n];
       frame_power(frame, power, tb);
       for (int m = 0; m < kNmel; ++m) mel[m] = 0.0;
@@ -188,4 +193,8 @@ extern "C" int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, 
     }
   }
   return GWW_OK;
+}
+
+extern "C" int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out) {
+  return gww_logmel_host_nmel_f32(wave, n_seg, n_samples, wave_stride, 80, out);
 }

@@ -11,7 +11,7 @@ Mirrors the HuggingFace surface the reference uses:
   ``layers.N.final_layer_norm``, ``layer_norm``);
 * ``named_modules()`` yields the names the reference's ``fnmatch`` target search
   consumes (``src/train.py:230-237``);
-* ``encoder(mel)`` takes ``[B, 80, 3000]`` fp32 on the GPU and returns an object
+* ``encoder(mel)`` takes ``[B, num_mel_bins, 3000]`` fp32 (80 mels, 128 for large-v3) on the GPU and returns an object
   with ``.last_hidden_state [B, 1500, d]`` (``src/model.py:25-26``);
   ``encoder.config.d_model`` exists (``src/model.py:11``);
 * ``gradient_checkpointing_enable()`` is accepted (``MLGWSC-1/train.py:662``).
@@ -47,7 +47,18 @@ class WhisperConfig:
     @staticmethod
     def named(name: str) -> "WhisperConfig":
         d, L, H, F = synth.ENCODER_SIZES[name]
-        return WhisperConfig(d, L, H, F)
+        return WhisperConfig(d, L, H, F, num_mel_bins=synth.encoder_mels(name))
+
+    @staticmethod
+    def from_json_file(path: str) -> "WhisperConfig":
+        """The encoder fields of an HF Whisper ``config.json`` (what ``save_pretrained`` writes); a missing
+        ``num_mel_bins`` means 80, as in HF."""
+        import json
+        with open(path) as f:
+            j = json.load(f)
+        return WhisperConfig(j["d_model"], j["encoder_layers"], j["encoder_attention_heads"], j["encoder_ffn_dim"],
+                             num_mel_bins=j.get("num_mel_bins", 80),
+                             max_source_positions=j.get("max_source_positions", 1500))
 
 
 @dataclass
@@ -226,6 +237,17 @@ class WhisperEncoder(_Tracked):
     def _freeze_parameters(self):
         for p in self.parameters():
             p.requires_grad = False
+
+    @staticmethod
+    def from_pretrained(save_directory: str, **kw) -> "WhisperEncoder":
+        """Load what :meth:`save_pretrained` wrote: ``config.json`` (geometry and ``num_mel_bins``) and
+        ``model.safetensors``."""
+        import os
+
+        from safetensors.torch import load_file
+        enc = WhisperEncoder(WhisperConfig.from_json_file(os.path.join(save_directory, "config.json")), **kw)
+        enc.load_state_dict(load_file(os.path.join(save_directory, "model.safetensors")))
+        return enc
 
     @staticmethod
     def from_numpy_state_dict(sd: dict, config: WhisperConfig, **kw) -> "WhisperEncoder":

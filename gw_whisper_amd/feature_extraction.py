@@ -45,9 +45,9 @@ class WhisperFeatureExtractor:
 
     def __init__(self, feature_size=80, sampling_rate=16000, hop_length=160, chunk_length=30, n_fft=400,
                  padding_value=0.0, device="cpu", **kwargs):
-        if (feature_size, sampling_rate, hop_length, chunk_length, n_fft) != (80, 16000, 160, 30, 400):
+        if feature_size not in (80, 128) or (sampling_rate, hop_length, chunk_length, n_fft) != (16000, 160, 30, 400):
             raise ValueError("gw_whisper_amd implements the Whisper front end only for its published "
-                             "configuration (80 mels, 16 kHz, hop 160, 30 s chunks, n_fft 400)")
+                             "configurations (80 or 128 mels, 16 kHz, hop 160, 30 s chunks, n_fft 400)")
         self.feature_size = feature_size
         self.sampling_rate = sampling_rate
         self.hop_length = hop_length
@@ -60,7 +60,20 @@ class WhisperFeatureExtractor:
 
     @classmethod
     def from_pretrained(cls, name_or_path=None, **kwargs):
-        # every openai/whisper-{tiny,base,small,...} preprocessor_config.json is this default
+        """Every published ``openai/whisper-*`` preprocessor_config.json is this class's default except those of
+        large-v3 and large-v3-turbo, which set ``feature_size`` 128.  A local directory's (or file's)
+        ``preprocessor_config.json`` is read for its ``feature_size``.  Nothing is downloaded; keyword arguments
+        override, as in HF."""
+        import json
+        import os
+        if name_or_path is not None and "feature_size" not in kwargs:
+            path = os.fspath(name_or_path)
+            cfg = os.path.join(path, "preprocessor_config.json") if os.path.isdir(path) else path
+            if os.path.isfile(cfg):
+                with open(cfg) as f:
+                    kwargs["feature_size"] = json.load(f).get("feature_size", 80)
+            elif path.rstrip("/").split("/")[-1] in ("whisper-large-v3", "whisper-large-v3-turbo"):
+                kwargs["feature_size"] = 128
         return cls(**kwargs)
 
     def __call__(self, raw_speech, truncation=True, pad_to_multiple_of=None, return_tensors=None,
@@ -96,7 +109,8 @@ class WhisperFeatureExtractor:
                 m = min(len(r), n)
                 host[i, :m] = r[:m]
             wave = torch.from_numpy(host).to(dev)
-        feats = ops.logmel(wave) if dev.type == "cuda" else ops.logmel_host(wave)
+        feats = (ops.logmel(wave, n_mels=self.feature_size) if dev.type == "cuda"
+                 else ops.logmel_host(wave, n_mels=self.feature_size))
         if return_device == "cpu":
             feats = feats.cpu()
         if return_tensors == "np":

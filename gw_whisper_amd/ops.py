@@ -27,56 +27,66 @@ def _dev(t: torch.Tensor, dtype=None, name="tensor") -> torch.Tensor:
 _frontend = {}
 
 
-def _fe(device) -> int:
+def _fe(device, n_mels: int = 80) -> int:
     idx = torch.device(device).index or 0
-    if idx not in _frontend:
+    if (idx, n_mels) not in _frontend:
         import ctypes as C
         h = C.c_void_p()
         with torch.cuda.device(idx):
-            check(lib().gww_frontend_create(C.byref(h)), "gww_frontend_create")
-        _frontend[idx] = h
-    return _frontend[idx]
+            if n_mels == 80:
+                check(lib().gww_frontend_create(C.byref(h)), "gww_frontend_create")
+            else:
+                check(lib().gww_frontend_create_nmel(n_mels, C.byref(h)), "gww_frontend_create_nmel")
+        _frontend[(idx, n_mels)] = h
+    return _frontend[(idx, n_mels)]
 
 
-def logmel(wave: torch.Tensor, n_samples: int | None = None) -> torch.Tensor:
-    """[n, L] fp32 GPU waveform (16 kHz) -> [n, 80, 3000] fp32 ``input_features``.
+def _check_n_mels(n_mels: int) -> None:
+    if n_mels not in (80, 128):
+        raise _lib.GwwError(f"n_mels={n_mels}: the Whisper front end has 80 or 128 (large-v3) mel bins")
 
-    Same arithmetic as ``WhisperFeatureExtractor(...)`` (reference call site
+
+def logmel(wave: torch.Tensor, n_samples: int | None = None, n_mels: int = 80) -> torch.Tensor:
+    """[n, L] fp32 GPU waveform (16 kHz) -> [n, n_mels, 3000] fp32 ``input_features``.
+
+    Same arithmetic as ``WhisperFeatureExtractor(feature_size=n_mels)(...)`` (reference call site
     Signal_vs_Noise/src/dataset.py:20-21): zero-pad/truncate to 30 s, STFT, mel, log10,
-    per-segment dynamic-range clamp, affine.
+    per-segment dynamic-range clamp, affine.  ``n_mels`` is 80, or 128 for whisper-large-v3.
     """
+    _check_n_mels(n_mels)
     if wave.dim() == 1:
         wave = wave[None]
     wave = _dev(wave, torch.float32, "wave")
     n, L = wave.shape
     n_samples = L if n_samples is None else n_samples
-    out = torch.empty((n, 80, 3000), dtype=torch.float32, device=wave.device)
+    out = torch.empty((n, n_mels, 3000), dtype=torch.float32, device=wave.device)
     seg_max = torch.empty((max(n, 1),), dtype=torch.float32, device=wave.device)
     with torch.cuda.device(wave.device):
         step = 32768   # gridDim.y limit
         for i in range(0, n, step):
             m = min(step, n - i)
-            check(lib().gww_logmel_f32(_fe(wave.device), wave[i:].data_ptr(), m, n_samples, wave.stride(0),
+            check(lib().gww_logmel_f32(_fe(wave.device, n_mels), wave[i:].data_ptr(), m, n_samples, wave.stride(0),
                                        out[i:].data_ptr(), seg_max[i:].data_ptr(), _stream()), "gww_logmel_f32")
     return out
 
 
-def logmel_host(wave, n_samples: int | None = None) -> torch.Tensor:
-    """CPU twin of :func:`logmel`: [n, L] fp32 host waveform -> [n, 80, 3000] fp32 CPU tensor.
+def logmel_host(wave, n_samples: int | None = None, n_mels: int = 80) -> torch.Tensor:
+    """CPU twin of :func:`logmel`: [n, L] fp32 host waveform -> [n, n_mels, 3000] fp32 CPU tensor.
 
-    Runs ``gww_logmel_host_f32`` (plain C++ inside libgww.so, no HIP call), so it works inside forked DataLoader
+    Runs ``gww_logmel_host_nmel_f32`` (plain C++ inside libgww.so, no HIP call), so it works inside forked DataLoader
     workers, where the reference calls the extractor (Signal_vs_Noise/src/dataset.py:20-21 under
     src/train.py:224-225).  Not a fallback of the GPU path: callers pick it by handing over host data.
     """
     import numpy as np
+    _check_n_mels(n_mels)
     w = np.ascontiguousarray(wave.numpy() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32)
     if w.ndim == 1:
         w = w[None]
     n, L = w.shape
     n_samples = L if n_samples is None else n_samples
-    out = torch.empty((n, 80, 3000), dtype=torch.float32)
-    check(lib().gww_logmel_host_f32(w.ctypes.data, n, n_samples, max(L, 1) if n else 1, out.data_ptr()),
-          "gww_logmel_host_f32")
+    out = torch.empty((n, n_mels, 3000), dtype=torch.float32)
+    check(lib().gww_logmel_host_nmel_f32(w.ctypes.data, n, n_samples, max(L, 1) if n else 1, n_mels, out.data_ptr()),
+          "gww_logmel_host_nmel_f32")
     return out
 
 

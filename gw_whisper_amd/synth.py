@@ -19,7 +19,22 @@ ENCODER_SIZES = {
     "base": (512, 6, 8, 2048),
     "small": (768, 12, 12, 3072),
     "micro": (128, 2, 2, 512),      # not a Whisper size: the reduced geometry the parity tests use
+    "medium": (1024, 24, 16, 4096),
+    "large": (1280, 32, 20, 5120),
+    "large-v2": (1280, 32, 20, 5120),
+    "large-v3": (1280, 32, 20, 5120),
+    "large-v3-turbo": (1280, 32, 20, 5120),   # the turbo model shrinks the decoder only
 }
+
+# input mel bins of the sizes that do not use Whisper's 80 (HF config.json "num_mel_bins")
+ENCODER_MELS = {"large-v3": 128, "large-v3-turbo": 128}
+
+
+def encoder_mels(name: str) -> int:
+    """Mel bins the named encoder reads (and its feature extractor's ``feature_size``)."""
+    if name not in ENCODER_SIZES:
+        raise KeyError(name)
+    return ENCODER_MELS.get(name, 80)
 
 
 def sinusoid_table(length: int = 1500, channels: int = 384) -> np.ndarray:
@@ -76,7 +91,7 @@ def encoder_state_dict(d_model: int, layers: int, heads: int, ffn: int, seed: in
 
 
 def named_encoder_state_dict(name: str, seed: int = 0) -> dict:
-    return encoder_state_dict(*ENCODER_SIZES[name], seed=seed)
+    return encoder_state_dict(*ENCODER_SIZES[name], seed=seed, n_mels=encoder_mels(name))
 
 
 def head_state_dict(sizes, seed: int = 0, sequential_stride: int = 2) -> dict:

@@ -84,6 +84,7 @@ def load_arrays(args):
 def main(args):
     from gw_whisper_amd import dist as gdist, ops, synth
     from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    from gw_whisper_amd.feature_extraction import WhisperFeatureExtractor
     from gw_whisper_amd.models import two_channel_ligo_binary_classifier
     from gw_whisper_amd.peft import LoraConfig, get_peft_model
     rank, world, local = gdist.init()
@@ -99,7 +100,11 @@ def main(args):
     val_idx, train_idx = perm[:n_val], perm[n_val:]
 
     d, L, H, F = synth.ENCODER_SIZES[args.encoder]
-    encoder = WhisperEncoder(WhisperConfig(d, L, H, F), precision="bf16")
+    config = WhisperConfig.named(args.encoder)
+    # src/dataset.py:12 -- the extractor of the same size: 128 mel bins for large-v3 / large-v3-turbo, 80 otherwise
+    n_mels = WhisperFeatureExtractor.from_pretrained(f"openai/whisper-{args.encoder}").feature_size
+    assert n_mels == config.num_mel_bins
+    encoder = WhisperEncoder(config, precision="bf16")
     if args.encoder_weights:
         if args.encoder_weights.endswith(".safetensors"):
             from safetensors.torch import load_file
@@ -107,7 +112,7 @@ def main(args):
         else:
             encoder.load_state_dict(torch.load(args.encoder_weights, map_location="cpu"))
     else:
-        sd = synth.encoder_state_dict(d, L, H, F, seed=args.seed)
+        sd = synth.encoder_state_dict(d, L, H, F, seed=args.seed, n_mels=n_mels)
         encoder.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     module_names = [name for name, _ in encoder.named_modules()]
     patterns = ["layers.*.self_attn.q_proj", "layers.*.self_attn.k_proj", "layers.*.self_attn.v_proj",
@@ -157,7 +162,7 @@ def main(args):
 
     def features(idx):
         w = torch.from_numpy(np.concatenate((h1[idx], l1[idx]))).to(device)
-        mel = ops.logmel(w)
+        mel = ops.logmel(w, n_mels=n_mels)
         return mel[: len(idx)], mel[len(idx):]
 
     def evaluate():

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -50,13 +50,15 @@ const char* gww_last_error(void);
  *   (impl HF:models/whisper/feature_extraction_whisper.py:135-168,193-346).
  * wave   [n_seg, wave_stride] fp32, the first n_samples of each row are the
  *        16 kHz samples (zero padded / truncated to 480000 like HF does)
- * out    [n_seg, 80, 3000] fp32  == input_features
+ * out    [n_seg, n_mels, 3000] fp32  == input_features (n_mels of the handle: 80, or 128 for large-v3)
  * seg_max[n_seg] fp32 scratch (per-segment max of the raw log10 mel)
  * Exact shortcut: frames that only see zero padding are filled with the one
  * constant HF would produce; only ceil((n_samples+200)/160) frames run a DFT.
  * -------------------------------------------------------------------------- */
 typedef struct gww_frontend gww_frontend;
-int gww_frontend_create(gww_frontend** out);          /* uploads window / twiddle / filterbank tables */
+int gww_frontend_create(gww_frontend** out);          /* uploads window / twiddle / filterbank tables; 80 mels */
+/* n_mels 80 or 128: HF's mel_filter_bank(201, n_mels, 0, 8000, 16000, slaney, slaney) */
+int gww_frontend_create_nmel(int n_mels, gww_frontend** out);
 void gww_frontend_destroy(gww_frontend* fe);
 int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, int n_samples,
                    long wave_stride, float* out, float* seg_max, void* stream);
@@ -64,7 +66,9 @@ int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, int n_samples
  * handle, no global mutable state), so it may be called from forked DataLoader worker processes -- where the
  * reference calls the extractor: Signal_vs_Noise/src/dataset.py:12,20-21 under src/train.py:224-225
  * (num_workers 12).  Same arithmetic and the same dead-frame shortcut; double-precision FFT, fp32 result. */
-int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out);
+int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out);   /* 80 mels */
+/* the same with n_mels 80 or 128; out [n_seg, n_mels, 3000] */
+int gww_logmel_host_nmel_f32(const float* wave, int n_seg, int n_samples, long wave_stride, int n_mels, float* out);
 
 /* --------------------------------------------------------------------------
  * Encoder.  Replaces WhisperEncoder.forward as built at
@@ -78,13 +82,13 @@ typedef struct {
   int n_layers;
   int n_heads;   /* d_model / 64 (head_dim is 64 for every Whisper size) */
   int ffn;       /* 4 * d_model */
-  int n_mels;    /* 80 */
+  int n_mels;    /* 80, or 128 (whisper-large-v3 / -large-v3-turbo) */
   int t_in;      /* 3000 mel frames  -> t_in/2 tokens */
 } gww_enc_cfg;
 
 /* fp32 master weights, HF layout ([out,in] linears, [out,in,3] convs). */
 typedef struct {
-  const float* conv1_w; const float* conv1_b;   /* [d,80,3] [d] */
+  const float* conv1_w; const float* conv1_b;   /* [d,n_mels,3] [d] */
   const float* conv2_w; const float* conv2_b;   /* [d,d,3]  [d] */
   const float* pos;                             /* [t_in/2, d] embed_positions.weight */
   const float* ln_w; const float* ln_b;         /* final layer_norm */
@@ -119,7 +123,7 @@ int gww_encoder_update_weights(gww_encoder* enc, const gww_enc_globals* globals_
                                void* stream);
 /* bytes of caller-owned scratch gww_encoder_forward needs for `batch` segments */
 size_t gww_encoder_workspace_bytes(const gww_encoder* enc, int batch, int precision);
-/* mel [batch,80,3000] fp32 (== input_features).  Either output may be NULL:
+/* mel [batch,n_mels,3000] fp32 (== input_features).  Either output may be NULL:
  *   last_hidden [batch, 1500, d] fp32 (== .last_hidden_state)
  *   last_token  [batch, d]       fp32 (== .last_hidden_state[:, -1, :],
  *                Signal_vs_Noise/src/model.py:25-26) */
@@ -159,7 +163,8 @@ int gww_dora_merge_f32(const float* w0, const float* a, const float* b, const fl
  * (reached from Signal_vs_Noise/src/model.py:25, Glitch_classification/src/model.py, MLGWSC-1/inference.py:353-392).
  *   mel [B, 80, T] fp32, conv1_w [d, 80, 3] fp32, conv1_b [d] fp32; w_scratch_bf16: d * 256 bf16 of scratch (packed
  *   taps); c1_out [B, T + 2, d] bf16 token-major, rows 0 and T + 1 of every segment zero (the padding conv2 reads).
- *   d in {384, 512, 768, 1024}.
+ *   d in {384, 512, 768, 1024}, 80 mels only.  The encoder runs other (n_mels, d) pairs -- 128 mels, d = 1280 -- on the
+ *   transposition kernel + a GEMM over overlapping rows with K = 3 n_mels padded to a multiple of 64 (256 / 384).
  * -------------------------------------------------------------------------- */
 int gww_conv1_gelu_bf16(const float* mel, const float* conv1_w, const float* conv1_b, void* w_scratch_bf16,
                         void* c1_out, int B, int T, int d, void* stream);

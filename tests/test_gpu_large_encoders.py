@@ -1,0 +1,283 @@
+"""The wide encoders on the GPU: the 128-bin log-mel kernel against HF ``WhisperFeatureExtractor(feature_size=128)``,
+the conv stem at 128 mels and d = 1024 / 1280 against a float64 torch restatement, the reduced two-layer medium and
+large-v3 encoders and the full 32-layer large-v3 against HF ``WhisperEncoder`` goldens (tools/make_golden_large.py),
+a DoRA step and a full-fine-tuning step of the 128-mel encoder against fp64 autograd, and ``run_train.py --encoder
+large-v3``.  Needs an MI355X."""
+
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from gw_whisper_amd import synth
+from tests.test_gpu_full_finetune import _encoder64
+
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INPUT_SEED = 21   # tools/make_golden_large.py: synth.strain_segments(2, seed=21)
+
+
+@pytest.fixture(scope="module")
+def T():
+    import torch
+    assert torch.cuda.is_available()
+    return torch
+
+
+def _mel(T, n_mels, n_seg=2):
+    from gw_whisper_amd import ops
+    return ops.logmel(T.from_numpy(synth.strain_segments(2, seed=INPUT_SEED)[:n_seg]).cuda(), n_mels=n_mels)
+
+
+# ------------------------------------------------------------------ 128-bin log-mel
+# The 80-bin device tests allow 2e-5 (fp32 DFT by direct summation against HF's fp64 FFT); the same bound holds here
+# for every element but a handful: measured on MI355X, one of the 57 344 checked values of the 1 s segments (the first,
+# reflect-padded frame, where the host twin's fp64 FFT also sees its largest error, 9.9e-6) is 2.85e-5 off.
+MEL_TOL = 2e-5
+MEL_TOL_MAX = 4e-5
+
+
+def test_logmel128_matches_hf_golden(T, gww, golden):
+    from gw_whisper_amd import ops
+    g = golden("logmel128.npz")
+    seg = synth.strain_segments(4, seed=11)
+    out = ops.logmel(T.from_numpy(seg).cuda(), n_mels=128).cpu().numpy()
+    assert out.shape == (4, 128, 3000)
+    err = float(np.abs(out[:, :, :112] - g["seg16000_frames0_112"]).max())
+    print(f"128-bin log-mel: max |device - HF| = {err:.2e}")
+    e = np.abs(out[:, :, :112] - g["seg16000_frames0_112"])
+    assert err < MEL_TOL_MAX and int((e > MEL_TOL).sum()) <= 4, (err, int((e > MEL_TOL).sum()))
+    for i in range(4):
+        assert np.all(out[i, :, 102:] == out[i, 0, 2999]), "dead frames must be one constant"
+        assert abs(out[i, 0, 2999] - g["seg16000_pad_value"][i]) < MEL_TOL
+    # the host twin and the device kernel agree with each other as closely as each agrees with HF
+    host = ops.logmel_host(seg, n_mels=128).numpy()
+    assert float(np.abs(out - host).max()) < MEL_TOL_MAX
+
+
+@pytest.mark.parametrize("n", [1, 159, 12345, 40000, 480000, 480321])
+def test_logmel128_ragged_lengths(T, gww, golden, n):
+    from gw_whisper_amd import ops
+    g = golden("logmel128.npz")
+    w = synth.strain_segments(1, seed=(200 if n >= 480000 else 100) + n, n_samples=n)
+    out = ops.logmel(T.from_numpy(w).cuda(), n_mels=128).cpu().numpy()[0]
+    if n >= 480000:
+        np.testing.assert_allclose(out[:, g[f"len{n}_cols"]], g[f"len{n}_frames"], atol=MEL_TOL, rtol=0)
+    else:
+        ref = g[f"len{n}_frames"]
+        np.testing.assert_allclose(out[:, :ref.shape[1]], ref, atol=MEL_TOL, rtol=0)
+        assert abs(out[0, 2999] - g[f"len{n}_pad_value"]) < MEL_TOL
+
+
+def test_logmel128_constant_collapse_and_80_unchanged(T, gww, golden):
+    from gw_whisper_amd import ops
+    g = golden("logmel128.npz")
+    z = ops.logmel(T.zeros(1, 16000).cuda(), n_mels=128).cpu().numpy()[0]
+    assert z.min() == z.max() == g["zeros_value"][0] == -1.5
+    r = ops.logmel(T.from_numpy((synth.strain_segments(1, seed=5) * 1e-21).astype(np.float32)).cuda(), n_mels=128)
+    r = r.cpu().numpy()[0]
+    assert r.min() == g["raw1e21_value"][0] and r.max() == g["raw1e21_value"][1]
+    seg = T.from_numpy(synth.strain_segments(3, seed=2)).cuda()
+    assert T.equal(ops.logmel(seg), ops.logmel(seg, n_mels=80))
+
+
+# ------------------------------------------------------------------ conv stem at 128 mels / d = 1280
+@pytest.mark.parametrize("C,d", [(80, 1024), (128, 1024), (80, 1280), (128, 1280)])
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_stem_and_one_layer_against_fp64(T, gww, C, d, precision):
+    """A one-layer encoder of each (n_mels, width) pair against the float64 restatement of HF's encoder.  At 80 mels
+    and d = 1024 the bf16 stem runs the direct conv1 kernel (conv1_mel.hip); the other pairs, and every fp32 run, take
+    the transposition kernel + the GEMM over overlapping rows with conv1's K padded to 256 (80 mels) or 384 (128)."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    H, F = d // 64, 4 * d
+    sd = synth.encoder_state_dict(d, 1, H, F, seed=C + d, n_mels=C)
+    mel = _mel(T, C)
+    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(d, 1, H, F, num_mel_bins=C), precision=precision).cuda()
+    with T.no_grad():
+        out = enc(mel).last_hidden_state.double().cpu()
+    ref = _encoder64(T, {k: T.from_numpy(v).double() for k, v in sd.items()}, mel.double().cpu(), (d, 1, H))
+    err = (out - ref).abs()
+    print(f"C={C} d={d} {precision}: max err {float(err.max()):.2e}, rms {float(err.pow(2).mean().sqrt()):.2e}")
+    if precision == "fp32":
+        assert float(err.max()) < 2e-4 + 1e-4 * float(ref.abs().max())
+    else:
+        assert float(err.max()) < 6e-2 and float(err.pow(2).mean().sqrt()) < 6e-3
+
+
+# ------------------------------------------------------------------ reduced encoders against HF
+@pytest.mark.parametrize("name", ["encoder_medium_reduced", "encoder_large_reduced"])
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+def test_reduced_encoder_matches_hf(T, gww, golden, name, precision):
+    """Two layers of medium's (80 mels) or large-v3's (128 mels) geometry, B = 2, against HF ``WhisperEncoder`` in fp32
+    on the CPU.  fp32 keeps the small encoder's bounds (atol 2e-4, rtol 1e-4); bf16 those of the small encoder's
+    bf16 test against the HF rows (max 6e-2)."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    g = golden(f"{name}.npz")
+    d, L, H, F, C, seed = (int(x) for x in g["config"])
+    sd = synth.encoder_state_dict(d, L, H, F, seed=seed, n_mels=C)
+    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(d, L, H, F, num_mel_bins=C), precision=precision).cuda()
+    mel = _mel(T, C)
+    with T.no_grad():
+        out = enc(mel).last_hidden_state.cpu().numpy()
+        last = enc.last_token(mel).cpu().numpy()
+    err = float(np.abs(out[:, g["rows"]] - g["final"]).max())
+    print(f"{name} {precision}: max |x - HF| on the golden rows {err:.2e}, last token "
+          f"{float(np.abs(last - g['last']).max()):.2e}")
+    if precision == "fp32":
+        np.testing.assert_allclose(out[:, g["rows"]], g["final"], atol=2e-4, rtol=1e-4)
+        np.testing.assert_allclose(last, g["last"], atol=2e-4, rtol=1e-4)
+        np.testing.assert_allclose(np.abs(out).mean(axis=(1, 2)), g["final_mean_abs"], rtol=1e-4)
+    else:
+        assert err < 6e-2 and float(np.abs(last - g["last"]).max()) < 6e-2
+        np.testing.assert_allclose(np.abs(out).mean(axis=(1, 2)), g["final_mean_abs"], rtol=1e-2)
+
+
+def test_last_token_is_the_last_row_at_d1280(T, gww):
+    """fp32: bit-identical.  bf16: the generic path runs the last layer on the B pooled rows only (encoder.hip,
+    pooled_g), on other GEMM kernels than the full forward's, so the two differ by bf16 rounding of one layer's
+    intermediates (measured on MI355X: 8.3e-6 at most), bounded at 1e-3."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    sd = synth.encoder_state_dict(1280, 2, 20, 5120, seed=5, n_mels=128)
+    mel = _mel(T, 128)
+    for precision in ("fp32", "bf16"):
+        enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(1280, 2, 20, 5120, num_mel_bins=128),
+                                                   precision=precision).cuda()
+        with T.no_grad():
+            full = enc(mel).last_hidden_state[:, -1]
+            last = enc.last_token(mel)
+        if precision == "fp32":
+            assert T.equal(full, last)
+        else:
+            diff = float((full - last).abs().max())
+            print(f"d=1280 bf16: max |last_token - last row| = {diff:.2e}")
+            assert diff < 1e-3
+
+
+def test_full_large_v3_last_token(T, gww, golden):
+    """whisper-large-v3's whole 32-layer geometry, 128 mels, B = 1, against HF: fp32 last token within 1e-3; the bf16
+    error is printed and bounded (32 layers of bf16 GEMM operands against an fp32 reference)."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    g = golden("large_v3_last_token.npz")
+    d, L, H, F, C, seed = (int(x) for x in g["config"])
+    assert (d, L, H, F) == synth.ENCODER_SIZES["large-v3"] and C == 128
+    sd = synth.encoder_state_dict(d, L, H, F, seed=seed, n_mels=C)
+    mel = _mel(T, C, n_seg=1)
+    errs = {}
+    for precision in ("fp32", "bf16"):
+        enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig.named("large-v3"), precision=precision).cuda()
+        with T.no_grad():
+            last = enc.last_token(mel).cpu().numpy()
+        errs[precision] = (float(np.abs(last - g["last"]).max()), float(np.abs(last - g["last"]).mean()))
+        del enc
+        T.cuda.empty_cache()
+    print(f"large-v3 last token, max / mean |x - HF|: fp32 {errs['fp32'][0]:.2e} / {errs['fp32'][1]:.2e}, "
+          f"bf16 {errs['bf16'][0]:.2e} / {errs['bf16'][1]:.2e} (|x| max {np.abs(g['last']).max():.2f})")
+    assert errs["fp32"][0] < 1e-3
+    assert errs["bf16"][0] < 0.25 and errs["bf16"][1] < 0.03
+
+
+# ------------------------------------------------------------------ training at 128 mels
+def _dora64(T, sd, theta, mel, cfg, scaling):
+    """fp64 forward with DoRA-merged q / k / v (peft: the weight norm enters detached)."""
+    p = {k: T.from_numpy(v).double() for k, v in sd.items()}
+    for name, (A, Bm, m) in theta.items():
+        W0 = p[name + ".weight"]
+        Wp = W0 + scaling * (Bm @ A)
+        p[name + ".weight"] = (m / T.linalg.norm(Wp, dim=1).detach())[:, None] * Wp
+    return _encoder64(T, p, mel, cfg)
+
+
+def test_dora_step_128_mels_matches_fp64_autograd(T, gww):
+    """DoRA (r 8, alpha 32) on q, k, v of both layers of the reduced large-v3 encoder (d 1280, 128 mels): adapter
+    gradients and the input-feature gradient d_mel against fp64 autograd, per-tensor relative Frobenius error <= 3 %
+    (5 % for the q / k adapters, whose gradients pass the bf16 softmax backward -- test_gpu_full_finetune.py)."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    from gw_whisper_amd.peft import LoraConfig, get_peft_model
+    d, L, H, F, C = 1280, 2, 20, 5120, 128
+    sd = synth.encoder_state_dict(d, L, H, F, seed=3, n_mels=C)
+    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(d, L, H, F, num_mel_bins=C), precision="bf16")
+    targets = [f"layers.{i}.self_attn.{p}" for i in range(L) for p in ("q_proj", "k_proj", "v_proj")]
+    peft = get_peft_model(enc, LoraConfig(use_dora=True, r=8, lora_alpha=32, target_modules=targets)).cuda()
+    theta = {}
+    with T.no_grad():
+        for j, name in enumerate(targets):
+            lin = peft.base_model.model.get_submodule(name)
+            A, Bm, m = synth.dora_adapter(d, d, 8, sd[name + ".weight"], seed=70 + j)
+            lin.lora_A["default"].weight.copy_(T.from_numpy(A))
+            lin.lora_B["default"].weight.copy_(T.from_numpy(Bm))
+            lin.lora_magnitude_vector["default"].weight.copy_(T.from_numpy(m))
+            theta[name] = [T.from_numpy(x).double().requires_grad_(True) for x in (A, Bm, m)]
+    mel = _mel(T, C)
+    wl = np.random.default_rng(7).standard_normal((2, d))
+    mel_t = mel.clone().requires_grad_(True)
+    out = peft(mel_t).last_hidden_state[:, -1, :]
+    (out * T.from_numpy(wl).cuda().float()).sum().backward()
+
+    mel64 = mel.double().cpu().requires_grad_(True)
+    h = _dora64(T, sd, theta, mel64, (d, L, H), 4.0)
+    (h[:, -1, :] * T.from_numpy(wl)).sum().backward()
+    worst = []
+    for name in targets:
+        lin = peft.base_model.model.get_submodule(name)
+        got = [lin.lora_A["default"].weight.grad, lin.lora_B["default"].weight.grad,
+               lin.lora_magnitude_vector["default"].weight.grad]
+        for part, g_, r_ in zip("ABm", got, theta[name]):
+            g_ = g_.double().cpu()
+            rel = float(T.linalg.norm(g_ - r_.grad) / (T.linalg.norm(r_.grad) + 1e-30))
+            worst.append((rel, f"{name}.{part}"))
+            assert rel <= (0.05 if ("q_proj" in name or "k_proj" in name) else 0.03), (name, part, rel)
+    rel_mel = float(T.linalg.norm(mel_t.grad.double().cpu() - mel64.grad) / T.linalg.norm(mel64.grad))
+    worst.sort(reverse=True)
+    print("DoRA 128 mels, worst relative errors:", [(round(r, 4), n) for r, n in worst[:4]], "d_mel", round(rel_mel, 4))
+    assert rel_mel <= 0.03
+
+
+def test_full_finetune_step_128_mels_matches_fp64_autograd(T, gww):
+    """Full fine-tuning of the reduced large-v3 encoder (d 1280, 128 mels, K of conv1 padded to 384): every base
+    gradient -- conv1.weight through the im2col view of the 128-channel token rows -- and d_mel against fp64
+    autograd, at the bounds of test_gpu_full_finetune.py (3 %, 5 % for q_proj / k_proj)."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    d, L, H, F, C = 1280, 2, 20, 5120, 128
+    sd = synth.encoder_state_dict(d, L, H, F, seed=3, n_mels=C)
+    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(d, L, H, F, num_mel_bins=C), precision="bf16").cuda()
+    enc.enable_full_finetune()
+    for p in enc.parameters():
+        p.requires_grad = True
+    mel = _mel(T, C)
+    wl = np.random.default_rng(7).standard_normal((2, d))
+    mel_t = mel.clone().requires_grad_(True)
+    (enc(mel_t).last_hidden_state[:, -1, :] * T.from_numpy(wl).cuda().float()).sum().backward()
+    p64 = {k: T.from_numpy(v).double().requires_grad_(True) for k, v in sd.items()}
+    mel64 = mel.double().cpu().requires_grad_(True)
+    (_encoder64(T, p64, mel64, (d, L, H))[:, -1, :] * T.from_numpy(wl)).sum().backward()
+    worst = []
+    for n, p in enc.named_parameters():
+        g_ = p.grad.double().cpu()
+        assert T.isfinite(g_).all(), n
+        rel = float(T.linalg.norm(g_ - p64[n].grad) / (T.linalg.norm(p64[n].grad) + 1e-30))
+        worst.append((rel, n))
+    worst.sort(reverse=True)
+    rel_mel = float(T.linalg.norm(mel_t.grad.double().cpu() - mel64.grad) / T.linalg.norm(mel64.grad))
+    print("full fine-tuning 128 mels, worst:", [(round(r, 4), n) for r, n in worst[:5]], "d_mel", round(rel_mel, 4))
+    for rel, n in worst:
+        assert rel <= (0.05 if ("q_proj" in n or "k_proj" in n) else 0.03), (n, rel)
+    assert rel_mel <= 0.03
+    assert dict((n, r) for r, n in worst)["conv1.weight"] <= 0.03
+
+
+def test_run_train_large_v3_one_epoch(T, gww, tmp_path):
+    """run_train.py --encoder large-v3 (DoRA, the reference's default method): one epoch on a tiny synthetic set
+    completes with finite losses and saves the adapter."""
+    models, logs = tmp_path / "models", tmp_path / "logs"
+    cmd = [sys.executable, os.path.join(ROOT, "harness", "run_train.py"), "--synthetic", "10", "--encoder", "large-v3",
+           "--num-epochs", "1", "--batch-size", "4", "--models-path", str(models), "--log-dir", str(logs)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    recs = [json.loads(x) for x in open(logs / "train_log.jsonl")]
+    assert len(recs) == 1 and np.isfinite(recs[0]["train_loss"]) and np.isfinite(recs[0]["val_loss"])
+    saved = [p for p in models.rglob("*") if p.is_file()]
+    assert saved, "nothing was saved"
