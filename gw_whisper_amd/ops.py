@@ -561,3 +561,91 @@ def dora_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
                                    float(scaling), f(A), f(B), f(mag), f(nrm), dA.data_ptr(), dB.data_ptr(),
                                    dm.data_ptr(), M, d, r, _stream()), "gww_dora_grads")
     return dA, dB, dm
+
+
+def info_nce_forward(z1, z2, temperature: float):
+    """InfoNCE of the reference's ContrastivePretrainer (``gww_info_nce_forward_f32``): z1, z2 fp32 [B, P] (P <= 1024) ->
+    (loss [1] device scalar, saved = (n [2B, P], nrm [2B], lse [2B], term [2B]) for ``info_nce_backward``)."""
+    z1 = _dev(z1, torch.float32, "z1")
+    z2 = _dev(z2, torch.float32, "z2")
+    if z1.dim() != 2 or z1.shape != z2.shape:
+        raise _lib.GwwError(f"info_nce: z1 {tuple(z1.shape)} and z2 {tuple(z2.shape)} must be the same [B, P]")
+    B, P = z1.shape
+    dev = z1.device
+    n = torch.empty((2 * B, P), dtype=torch.float32, device=dev)
+    rows = torch.empty((3, 2 * B), dtype=torch.float32, device=dev)          # nrm | lse | per-row term
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_info_nce_forward_f32(z1.data_ptr(), z2.data_ptr(), B, P, float(temperature), n.data_ptr(),
+                                             rows[0].data_ptr(), rows[1].data_ptr(), rows[2].data_ptr(), loss.data_ptr(),
+                                             _stream()), "gww_info_nce_forward_f32")
+    return loss, (n, rows[0], rows[1], rows[2])
+
+
+def info_nce_backward(saved, temperature: float, dloss):
+    """(dz1, dz2) [B, P] of ``info_nce_forward``'s loss times the device scalar ``dloss``."""
+    n, nrm, lse, term = saved
+    dloss = _dev(dloss.reshape(1), torch.float32, "dloss")
+    B, P = n.shape[0] // 2, n.shape[1]
+    dz = torch.empty((2, B, P), dtype=torch.float32, device=n.device)
+    with torch.cuda.device(n.device):
+        check(lib().gww_info_nce_backward_f32(n.data_ptr(), nrm.data_ptr(), lse.data_ptr(), term.data_ptr(), B, P,
+                                              float(temperature),
+                                              dloss.data_ptr(), dz[0].data_ptr(), dz[1].data_ptr(), _stream()),
+              "gww_info_nce_backward_f32")
+    return dz[0], dz[1]
+
+
+def qadapter_tail_backward(g, y, scale, bias, gamma_i, F: int, T: int):
+    """Backward of ``gww_qadapter_tail_f32`` for one detector (``gww_qadapter_tail_backward_f32``): g fp32 [B, F, T] (rows
+    contiguous; any batch stride, e.g. ``g_out[:, det]``), y fp32 [B, Hin, Win]; scale, bias, gamma_i device scalars.
+    Returns (d_y, d_scale [1], d_bias [1], d_gamma_i [1], d_beta_i [1])."""
+    if not g.is_cuda:
+        raise _lib.GwwError("qadapter_tail_backward: g must live on the GPU")
+    if g.dtype != torch.float32 or g.stride(-1) != 1 or g.stride(-2) != T:
+        g = g.to(torch.float32).contiguous()
+    y = _dev(y, torch.float32, "y")
+    B, Hin, Win = y.shape
+    dev = y.device
+    d_y = torch.empty_like(y)
+    d = torch.empty((4, 1), dtype=torch.float32, device=dev)
+    ws = torch.empty((lib().gww_qadapter_tail_backward_workspace_bytes(B, Hin),), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_qadapter_tail_backward_f32(g.data_ptr(), g.stride(0), y.data_ptr(), B, Hin, Win, F, T,
+                                                   _dev(scale, torch.float32, "scale").data_ptr(),
+                                                   _dev(bias, torch.float32, "bias").data_ptr(),
+                                                   _dev(gamma_i, torch.float32, "gamma_i").data_ptr(), d_y.data_ptr(),
+                                                   ws.data_ptr(), ws.numel(), d[0].data_ptr(), d[1].data_ptr(),
+                                                   d[2].data_ptr(), d[3].data_ptr(), _stream()),
+              "gww_qadapter_tail_backward_f32")
+    return d_y, d[0], d[1], d[2], d[3]
+
+
+def assemble_batch(noise, wave, idx_noise, idx_wave, snr):
+    """Rows ``noise[idx_noise[r]] + snr[r] * wave[idx_wave[r]]`` (``idx_wave[r] < 0``: the noise row alone) of device-resident
+    ``noise [N, ...]`` / ``wave [M, ...]`` fp32, bit for bit torch's fp32 arithmetic (``gww_assemble_batch_f32``).  The
+    plan (host int / float arrays of R entries) is checked against the array sizes here, then uploaded in one copy.
+    Returns [R, *noise.shape[1:]]."""
+    import numpy as np
+    noise = _dev(noise, torch.float32, "noise")
+    wave = _dev(wave, torch.float32, "wave")
+    if wave.shape[1:] != noise.shape[1:]:
+        raise _lib.GwwError(f"assemble_batch: noise rows {tuple(noise.shape[1:])} != wave rows {tuple(wave.shape[1:])}")
+    idx_noise = np.asarray(idx_noise, np.int64).reshape(-1)
+    idx_wave = np.asarray(idx_wave, np.int64).reshape(-1)
+    snr = np.asarray(snr, np.float32).reshape(-1)
+    R = len(idx_noise)
+    if len(idx_wave) != R or len(snr) != R or R < 1:
+        raise _lib.GwwError("assemble_batch: idx_noise, idx_wave and snr must have the same length >= 1")
+    if idx_noise.min() < 0 or idx_noise.max() >= noise.shape[0] or idx_wave.max() >= wave.shape[0]:
+        raise _lib.GwwError(f"assemble_batch: index out of range (noise {noise.shape[0]}, wave {wave.shape[0]})")
+    plan = np.empty((3, R), np.int32)
+    plan[0], plan[1] = idx_noise, idx_wave
+    plan[2] = snr.view(np.int32)
+    plan_d = torch.from_numpy(plan).to(noise.device, non_blocking=False)
+    out = torch.empty((R, *noise.shape[1:]), dtype=torch.float32, device=noise.device)
+    with torch.cuda.device(noise.device):
+        check(lib().gww_assemble_batch_f32(noise.data_ptr(), noise.shape[0], wave.data_ptr(), wave.shape[0],
+                                           noise[0].numel(), plan_d[0].data_ptr(), plan_d[1].data_ptr(),
+                                           plan_d[2].data_ptr(), R, out.data_ptr(), _stream()), "gww_assemble_batch_f32")
+    return out

@@ -159,8 +159,7 @@ class QScan(nn.Module):
 class _AdapterTail(torch.autograd.Function):
     """pool -> global affine -> FiLM of one detector as ONE HIP kernel that writes into the stacked feature tensor
     (``gww_qadapter_tail_f32``).  Backward (the adapter trains through the frozen encoder, MLGWSC-1/train.py:494-504):
-    PyTorch's own adaptive-pool backward on the incoming gradient plus four scalar reductions -- training-side only,
-    the inference path never runs it."""
+    ONE HIP pass as well (``gww_qadapter_tail_backward_f32``) -- training-side only, the inference path never runs it."""
 
     @staticmethod
     def forward(ctx, y, scale, bias, gamma, beta, out, det):
@@ -180,18 +179,18 @@ class _AdapterTail(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out):
+        from . import ops
         y, scale, bias, gamma = ctx.saved_tensors
         det = ctx.det
-        g = g_out[:, det].to(torch.float32)                                   # [B, F, T]
-        p = torch.nn.functional.adaptive_avg_pool2d(y[:, None], ctx.shape)[:, 0]
-        gam = gamma[det]
-        d_scale = (g * p).sum().reshape(1) * gam
-        d_bias = g.sum().reshape(1) * gam
+        F, T = ctx.shape
+        # one HIP pass over g_out[:, det]: the adaptive-pool backward as a fixed-order gather and the four scalar
+        # gradients from fixed-order partials (gww_qadapter_tail_backward_f32; no float atomics, reproducible bits)
+        d_y, d_scale, d_bias, d_gam, d_bet = ops.qadapter_tail_backward(g_out[:, det], y, scale, bias, gamma[det:det + 1],
+                                                                        F, T)
         d_gamma = torch.zeros_like(gamma)
-        d_gamma[det] = (g * (scale * p + bias)).sum()
+        d_gamma[det:det + 1] = d_gam
         d_beta = torch.zeros_like(gamma)
-        d_beta[det] = g.sum()
-        d_y = torch.ops.aten._adaptive_avg_pool2d_backward((g * (scale * gam))[:, None].contiguous(), y[:, None])[:, 0]
+        d_beta[det:det + 1] = d_bet
         g_rest = g_out.clone()
         g_rest[:, det] = 0                                                    # this call overwrote detector `det` of `out`
         return d_y, d_scale, d_bias, d_gamma, d_beta, g_rest, None

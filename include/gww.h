@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -464,6 +464,32 @@ int gww_dora_grads_multi(const void* X, long ldx, const void* dY, const void* Y,
                          const float* scaling, const float* const* A, const float* const* B,
                          const float* const* mag, const float* const* nrm, float* const* dA, float* const* dB,
                          float* const* dm, long M, int d, void* stream);
+/* MLGWSC-1 training program (contrastive.hip; fp32, no float atomics: two identical calls give identical bits).
+ * InfoNCE of ContrastivePretrainer._info_nce (MLGWSC-1/train.py:410-424): z1, z2 fp32 [B, P] (B >= 1, P <= 1024), each
+ * row L2-normalised as F.normalize does (z / max(|z|, 1e-12)); loss = (1/B) sum over the 2B rows of Z = [n1; n2] of
+ * LSE_{j != r}(Z Z^T / tau)_rj - (Z Z^T / tau)_{r, pair(r)}, with a max-subtracted LSE (finite where the reference's fp32
+ * exp overflows, tau < ~1/88.7).  The forward writes the device scalar `loss` and saves n [2B, P], nrm [2B] (|z| per row),
+ * lse [2B] and term [2B] (lse - S_{r,pair}) for the backward.  The backward reads the upstream gradient from the device
+ * scalar `dloss` (no host sync) and writes dz1, dz2 [B, P]. */
+int gww_info_nce_forward_f32(const float* z1, const float* z2, int B, int P, float tau, float* n, float* nrm, float* lse,
+                             float* term, float* loss, void* stream);
+int gww_info_nce_backward_f32(const float* n, const float* nrm, const float* lse, const float* term, int B, int P,
+                              float tau, const float* dloss, float* dz1, float* dz2, void* stream);
+/* Backward of gww_qadapter_tail_f32 for one detector: g fp32, element (b, f, t) at g[b * g_batch_stride + f * T + t] (the
+ * gradient of the stacked feature tensor at detector i); y fp32 [B, Hin, Win] as the forward read it.  Writes
+ * d_y [B, Hin, Win] (the adaptive-pool backward as a fixed-order gather) and the device scalars d_scale, d_bias,
+ * d_gamma_i, d_beta_i (not accumulated).  Win <= 4096, T <= 4096; workspace: gww_qadapter_tail_backward_workspace_bytes. */
+size_t gww_qadapter_tail_backward_workspace_bytes(int B, int Hin);
+int gww_qadapter_tail_backward_f32(const float* g, long g_batch_stride, const float* y, int B, int Hin, int Win, int F,
+                                   int T, const float* scale, const float* bias, const float* gamma_i, float* d_y, void* ws,
+                                   size_t ws_bytes, float* d_scale, float* d_bias, float* d_gamma_i, float* d_beta_i,
+                                   void* stream);
+/* Batch assembly of BinaryGWDataset / PretrainDataset (MLGWSC-1/train.py:262-273, 342-351): row r of out [R, row_len] is
+ * noise[idx_noise[r]] + snr[r] * wave[idx_wave[r]] (fp32 product rounded, then fp32 sum rounded: torch's bits), or the
+ * noise row alone when idx_wave[r] < 0.  noise [n_noise, row_len], wave [n_wave, row_len]; idx_noise, idx_wave (int32)
+ * and snr (fp32) are device arrays of R entries.  A row with an index outside its array is written NaN. */
+int gww_assemble_batch_f32(const float* noise, long n_noise, const float* wave, long n_wave, long row_len,
+                           const int* idx_noise, const int* idx_wave, const float* snr, int R, float* out, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
