@@ -17,6 +17,7 @@ PREC_BF16 = 0
 PREC_F32 = 1
 
 EPI_BIAS, EPI_GELU, EPI_RESID = 0, 1, 2
+EPI_DGELU = 5          # gemm_astat only: C = delta * gelu'(A W^T + bias)
 
 
 class EncCfg(C.Structure):

@@ -463,7 +463,8 @@ using namespace gww;
 extern "C" int gww_gemm_astat_bf16(const void* A, const void* delta, float* x_out, const float* ln_u,
                                    const float* ln_cb, const void* W, const float* bias, void* C, long M, int N,
                                    int K, int epilogue, void* stream) {
-  GWW_REQUIRE(epilogue == 0 || epilogue == 1, "gww_gemm_astat_bf16: epilogue must be 0 (bias) or 1 (GELU)");
+  GWW_REQUIRE(epilogue == EPI_BIAS || epilogue == EPI_GELU || epilogue == EPI_DGELU,
+              "gww_gemm_astat_bf16: epilogue must be 0 (bias), 1 (GELU) or 5 (GELU backward)");
   GWW_REQUIRE((ln_u == nullptr) == (ln_cb == nullptr), "gww_gemm_astat_bf16: ln_u and ln_cb go together");
   static const long dbg_panel = lab_int("GWW_ASTAT_PANEL", 0);   // tuning aid (lab build)
   return launch_gemm_astat(A, K, delta, x_out, ln_u, ln_cb, W, bias, C, M, N, K, epilogue, 0, (hipStream_t)stream,

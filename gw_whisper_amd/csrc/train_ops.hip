@@ -733,6 +733,11 @@ int launch_dora_grads(const void* X, long ldx, const void* dY, const void* Y, lo
                       void* scratch, size_t scratch_bytes) {
   GWW_REQUIRE(r == 8 && (d == 128 || d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280),
               "dora_grads: only r = 8 and d in {128, 384, 512, 768, 1024, 1280} (got d=%d r=%d)", d, r);
+  // every kernel reads 8 bf16 per load: row strides and section starts on 16-byte boundaries
+  GWW_REQUIRE(ldx >= d && ldy >= d && ldx % 8 == 0 && ldy % 8 == 0 &&
+                  ((((uintptr_t)X) | ((uintptr_t)dY) | ((uintptr_t)Y)) & 15) == 0,
+              "dora_grads: row strides (ldx=%ld ldy=%ld) must be multiples of 8 elements >= d and X / dY / Y 16-byte "
+              "aligned", ldx, ldy);
   if (M == 0) return GWW_OK;
   static const int old_kernel = (int)lab_int("GWW_DORA_OLD", 0);   // comparison aid: 1 = VALU
   // kernels only, 2 = register-blocked VALU kernel instead of the MFMA kernel

@@ -168,26 +168,37 @@ def ln_fold_weights(w: torch.Tensor, ln_w: torch.Tensor, ln_b: torch.Tensor, bia
 
 
 def gemm_astat(a: torch.Tensor, w: torch.Tensor, bias=None, epilogue: int = 0, ln=None, delta=None,
-               return_x: bool = False):
+               return_x: bool = False, out=None):
     """A-stationary bf16 GEMM (K in {256,384,512}) -> bf16 [M, N].
 
     ``ln=(u, cb)`` (from ``ln_fold_weights``, with ``w`` the folded panel): ``a`` is the fp32
     residual stream, ``x_new = a + delta`` (bf16 ``delta`` optional) and LayerNorm are fused
     into the GEMM in one pass; ``return_x`` also returns ``x_new``.  Output rows are padded
-    to a multiple of 256 internally."""
+    to a multiple of 256 internally, or ``out`` (bf16, contiguous, >= roundup(M, 256) rows) is
+    written.  ``epilogue=EPI_DGELU``: C = delta * gelu'(a w^T + bias) with ``delta`` the incoming
+    bf16 [M, N] gradient; ``out`` may be ``delta`` itself (the encoder's in-place form)."""
     fused = ln is not None
+    dgelu = epilogue == _lib.EPI_DGELU
     a = _dev(a, torch.float32 if fused else torch.bfloat16, "A")
     w = _dev(w, torch.bfloat16, "W")
     M, K = a.shape
     N = w.shape[0]
     Mp = (M + 255) // 256 * 256
-    c = torch.empty((Mp, N), dtype=torch.bfloat16, device=a.device)
+    if out is None:
+        c = torch.empty((Mp, N), dtype=torch.bfloat16, device=a.device)
+    else:
+        c = out
+        if c.dtype != torch.bfloat16 or not c.is_cuda or not c.is_contiguous() or c.dim() != 2 or c.shape[0] < Mp \
+                or c.shape[1] != N:
+            raise _lib.GwwError(f"gemm_astat: out must be a contiguous bf16 GPU tensor of [>= {Mp}, {N}]")
+    if dgelu and (delta is None or tuple(delta.shape[1:]) != (N,) or delta.shape[0] < M or not delta.is_contiguous()):
+        raise _lib.GwwError(f"gemm_astat: the gelu-backward epilogue needs a contiguous delta of [>= {M}, {N}]")
     dl = _dev(delta, torch.bfloat16, "delta") if delta is not None else None
     # x_new is only materialised when there is a delta to add; otherwise x_new IS a
     x_out = torch.empty_like(a) if (fused and return_x and dl is not None) else None
     with torch.cuda.device(a.device):
         check(lib().gww_gemm_astat_bf16(
-            a.data_ptr(), dl.data_ptr() if (dl is not None and x_out is not None) else None,
+            a.data_ptr(), dl.data_ptr() if (dl is not None and (x_out is not None or dgelu)) else None,
             x_out.data_ptr() if x_out is not None else None,
             _dev(ln[0], torch.float32).data_ptr() if fused else None,
             _dev(ln[1], torch.float32).data_ptr() if fused else None, w.data_ptr(),
@@ -547,19 +558,28 @@ def dora_grads_multi(x, dy, y, col_off, bias_st, yscale, scaling, A, B, mag, nrm
     return out
 
 
-def dora_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
-    """(dA [r,d], dB [d,r], dm [d]) of one DoRA projection; x, dy, y bf16 [M, d]."""
-    x, dy, y = (_dev(t, torch.bfloat16) for t in (x, dy, y))
+def dora_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm, col_off: int = 0):
+    """(dA [r,d], dB [d,r], dm [d]) of one DoRA projection.  x bf16 [M, d]; dy, y bf16 [M, W] (W >= col_off + d)
+    whose columns col_off .. col_off + d hold the projection -- with W = 3 d and col_off 0 / d / 2 d, the q / k / v
+    sections of the packed qkv / dqkv the encoder passes.  Rows of x and of dy / y may be strided (stride(1) == 1)."""
+    if any(t.dtype != torch.bfloat16 or not t.is_cuda for t in (x, dy, y)):
+        raise _lib.GwwError("dora_grads: x, dy and y must be bf16 GPU tensors")
+    if x.dim() != 2 or dy.dim() != 2 or x.stride(1) != 1 or dy.stride(1) != 1 or dy.stride() != y.stride() \
+            or dy.shape != y.shape:
+        raise _lib.GwwError("dora_grads: 2-D x, dy, y with contiguous rows; dy and y of the same shape and strides")
     M, d = x.shape
     r = A.shape[0]
+    if dy.shape[0] != M or col_off < 0 or col_off + d > dy.shape[1]:
+        raise _lib.GwwError(f"dora_grads: dy / y {tuple(dy.shape)} hold no [{M}, {d}] section at column {col_off}")
     dA = torch.zeros((r, d), dtype=torch.float32, device=x.device)
     dB = torch.zeros((d, r), dtype=torch.float32, device=x.device)
     dm = torch.zeros((d,), dtype=torch.float32, device=x.device)
     f = lambda t: _dev(t, torch.float32).data_ptr()
+    off = col_off * dy.element_size()
     with torch.cuda.device(x.device):
-        check(lib().gww_dora_grads(x.data_ptr(), d, dy.data_ptr(), y.data_ptr(), d, f(bias_st), float(yscale),
-                                   float(scaling), f(A), f(B), f(mag), f(nrm), dA.data_ptr(), dB.data_ptr(),
-                                   dm.data_ptr(), M, d, r, _stream()), "gww_dora_grads")
+        check(lib().gww_dora_grads(x.data_ptr(), x.stride(0), dy.data_ptr() + off, y.data_ptr() + off, dy.stride(0),
+                                   f(bias_st), float(yscale), float(scaling), f(A), f(B), f(mag), f(nrm),
+                                   dA.data_ptr(), dB.data_ptr(), dm.data_ptr(), M, d, r, _stream()), "gww_dora_grads")
     return dA, dB, dm
 
 

@@ -289,7 +289,7 @@ int gww_gemm_bf16(const void* A, const void* W, const float* bias, const float* 
 int gww_gemm_bf16_v4_split(const void* A, const void* W, const float* bias, const float* resid, void* C,
                            long M, int N, int K, int epilogue, int n_split, void* stream);
 /* A-stationary bf16 GEMM for K in {256, 384, 512}, N % 128 == 0 (QKV / fc1 / out_proj at
- * whisper-tiny/base): C = epi(f(A) @ W^T + bias), C bf16, epilogue 0 (bias) or 1 (GELU).
+ * whisper-tiny/base): C = epi(f(A) @ W^T + bias), C bf16, epilogue 0 (bias), 1 (GELU) or 5 (GELU backward).
  *   ln_u == NULL : A is bf16 [M,K], W the plain bf16 [N,K] panel.
  *   ln_u != NULL : A is the fp32 residual stream x [M,K].  In ONE pass the kernel forms
  *                  x_new = x + delta (delta bf16 [M,K] or NULL), writes it to x_out (fp32 [M,K],
@@ -297,6 +297,9 @@ int gww_gemm_bf16_v4_split(const void* A, const void* W, const float* bias, cons
  *                  HF:modeling_whisper.py:392,402) algebraically: W must be the gain-folded
  *                  panel and ln_u / ln_cb the vectors produced by gww_ln_fold_weights; `bias`
  *                  is ignored (it is inside ln_cb).
+ *   epilogue 5   : the backward of fc1's GELU, C = delta * gelu'(A @ W^T + bias) (each factor rounded to
+ *                  bf16): A bf16 [M,K], `delta` the incoming gradient, bf16 [M,N] row-major, x_out and ln_u
+ *                  NULL.  C may alias delta (in place); delta rows >= M are never read.
  * Rows of C must be ALLOCATED up to the next multiple of 256: whole 256-row panels are stored
  * unconditionally (rows >= M are scratch). */
 int gww_gemm_astat_bf16(const void* A, const void* delta, float* x_out, const float* ln_u,
@@ -451,7 +454,10 @@ int gww_layernorm_bwd(const float* x, const float* gamma, const void* dy, int dy
                       int accumulate, void* dx_bf16, long M, int d, void* stream);
 /* bf16 GELU: out = gelu(z) (dgelu == NULL) or out = dgelu * gelu'(z); n % 8 == 0 */
 int gww_gelu_bf16(const void* z, const void* dgelu_or_null, void* out, long n, void* stream);
-/* DoRA parameter gradients of one [d,d] projection (see train_ops.hip) */
+/* DoRA parameter gradients of one [d,d] projection (see train_ops.hip): X [M,d] with row stride ldx, dY / Y
+ * [M,d] sections with row stride ldy (e.g. one of the q / k / v column blocks of the packed [M,3d] qkv / dqkv),
+ * bias_st in stored units, yscale = dy_true / dy_stored.  d in {128, 384, 512, 768, 1024, 1280}, r = 8;
+ * gradients are accumulated. */
 int gww_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
                    float yscale, float scaling, const float* A, const float* B, const float* mag,
                    const float* nrm, float* dA, float* dB, float* dm, long M, int d, int r, void* stream);

@@ -13,6 +13,7 @@ import pytest
 
 from gw_whisper_amd import synth
 from oracle import logmel as olm
+from tests.helpers import encoder64
 
 pytestmark = pytest.mark.gpu
 
@@ -109,7 +110,7 @@ def test_wgrad_rejects_bad_strides_and_shapes(T, gww):
         ops.gemm_wgrad(dy, x[:, :120].contiguous())
 
 
-@pytest.mark.parametrize("d", [128, 384, 768])
+@pytest.mark.parametrize("d", [128, 384, 512, 768, 1024, 1280])
 @pytest.mark.parametrize("dy_f32", [True, False])
 def test_layernorm_param_grads_match_fp64(T, gww, d, dy_f32):
     from gw_whisper_amd import ops
@@ -131,36 +132,12 @@ def test_layernorm_param_grads_match_fp64(T, gww, d, dy_f32):
     assert T.equal(again[0], dgamma) and T.equal(again[1], dbeta)
 
 
-# ---------------------------------------------------------------- float64 restatement of the HF encoder
-def _encoder64(T, p, mel, cfg):
-    """HF:models/whisper/modeling_whisper.py WhisperEncoder.forward in float64 (eval: no dropout)."""
-    F_ = T.nn.functional
-    d, L, H = cfg
-    x = F_.gelu(F_.conv1d(mel, p["conv1.weight"], p["conv1.bias"], padding=1))
-    x = F_.gelu(F_.conv1d(x, p["conv2.weight"], p["conv2.bias"], stride=2, padding=1))
-    x = x.permute(0, 2, 1) + p["embed_positions.weight"]
-    B, Tn, _ = x.shape
-    for i in range(L):
-        q_ = lambda n: p[f"layers.{i}.{n}"]
-        h = F_.layer_norm(x, (d,), q_("self_attn_layer_norm.weight"), q_("self_attn_layer_norm.bias"), 1e-5)
-        q = (h @ q_("self_attn.q_proj.weight").t() + q_("self_attn.q_proj.bias")) * (d // H) ** -0.5
-        k = h @ q_("self_attn.k_proj.weight").t()
-        v = h @ q_("self_attn.v_proj.weight").t() + q_("self_attn.v_proj.bias")
-        sh = lambda t: t.view(B, Tn, H, d // H).transpose(1, 2)
-        a = T.softmax(sh(q) @ sh(k).transpose(-1, -2), dim=-1) @ sh(v)
-        a = a.transpose(1, 2).reshape(B, Tn, d)
-        x = x + a @ q_("self_attn.out_proj.weight").t() + q_("self_attn.out_proj.bias")
-        h = F_.layer_norm(x, (d,), q_("final_layer_norm.weight"), q_("final_layer_norm.bias"), 1e-5)
-        h = F_.gelu(h @ q_("fc1.weight").t() + q_("fc1.bias"))
-        x = x + h @ q_("fc2.weight").t() + q_("fc2.bias")
-    return F_.layer_norm(x, (d,), p["layer_norm.weight"], p["layer_norm.bias"], 1e-5)
-
-
-_SIZES = dict(synth.ENCODER_SIZES, small_l2=(768, 2, 12, 3072))
+# two-layer encoders of whisper-base / -small / -medium width: every kernel route of those widths at a small cost
+_SIZES = dict(synth.ENCODER_SIZES, base_l2=(512, 2, 8, 2048), small_l2=(768, 2, 12, 3072), medium_l2=(1024, 2, 16, 4096))
 
 
 @pytest.mark.parametrize("mode", ["hidden", "last_token"])
-@pytest.mark.parametrize("enc_name", ["micro", "tiny", "small_l2"])
+@pytest.mark.parametrize("enc_name", ["micro", "tiny", "base_l2", "small_l2", "medium_l2"])
 def test_every_base_gradient_matches_fp64_autograd(T, gww, enc_name, mode):
     """loss.backward() through the fully fine-tuned HIP encoder: every base parameter's gradient against fp64 autograd
     (per-tensor relative Frobenius error <= 3 %, the bf16-vs-fp64 bound of the DoRA tests), two central finite-difference
@@ -188,7 +165,7 @@ def test_every_base_gradient_matches_fp64_autograd(T, gww, enc_name, mode):
     wl64 = T.from_numpy(wl)
 
     def loss64(params, m):
-        h = _encoder64(T, params, m, (d, L, H))
+        h = encoder64(T, params, m, (d, L, H))
         return (h[:, -1, :] * wl64).sum()
 
     l64 = loss64(p64, mel64)

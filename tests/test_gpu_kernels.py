@@ -80,7 +80,7 @@ def test_logmel_idempotent_batching(T, gww):
 
 
 # ------------------------------------------------------------------ LayerNorm / cast
-@pytest.mark.parametrize("d", [128, 384, 512, 768])
+@pytest.mark.parametrize("d", [128, 384, 512, 768, 1024, 1280])
 def test_layernorm(T, gww, d):
     from gw_whisper_amd import ops
     rng = np.random.default_rng(d)

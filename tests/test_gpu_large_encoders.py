@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 
 from gw_whisper_amd import synth
-from tests.test_gpu_full_finetune import _encoder64
+from tests.helpers import dora64, encoder64
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +99,7 @@ def test_stem_and_one_layer_against_fp64(T, gww, C, d, precision):
     enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(d, 1, H, F, num_mel_bins=C), precision=precision).cuda()
     with T.no_grad():
         out = enc(mel).last_hidden_state.double().cpu()
-    ref = _encoder64(T, {k: T.from_numpy(v).double() for k, v in sd.items()}, mel.double().cpu(), (d, 1, H))
+    ref = encoder64(T, {k: T.from_numpy(v).double() for k, v in sd.items()}, mel.double().cpu(), (d, 1, H))
     err = (out - ref).abs()
     print(f"C={C} d={d} {precision}: max err {float(err.max()):.2e}, rms {float(err.pow(2).mean().sqrt()):.2e}")
     if precision == "fp32":
@@ -181,16 +181,6 @@ def test_full_large_v3_last_token(T, gww, golden):
 
 
 # ------------------------------------------------------------------ training at 128 mels
-def _dora64(T, sd, theta, mel, cfg, scaling):
-    """fp64 forward with DoRA-merged q / k / v (peft: the weight norm enters detached)."""
-    p = {k: T.from_numpy(v).double() for k, v in sd.items()}
-    for name, (A, Bm, m) in theta.items():
-        W0 = p[name + ".weight"]
-        Wp = W0 + scaling * (Bm @ A)
-        p[name + ".weight"] = (m / T.linalg.norm(Wp, dim=1).detach())[:, None] * Wp
-    return _encoder64(T, p, mel, cfg)
-
-
 def test_dora_step_128_mels_matches_fp64_autograd(T, gww):
     """DoRA (r 8, alpha 32) on q, k, v of both layers of the reduced large-v3 encoder (d 1280, 128 mels): adapter
     gradients and the input-feature gradient d_mel against fp64 autograd, per-tensor relative Frobenius error <= 3 %
@@ -218,7 +208,7 @@ def test_dora_step_128_mels_matches_fp64_autograd(T, gww):
     (out * T.from_numpy(wl).cuda().float()).sum().backward()
 
     mel64 = mel.double().cpu().requires_grad_(True)
-    h = _dora64(T, sd, theta, mel64, (d, L, H), 4.0)
+    h = dora64(T, sd, theta, mel64, (d, L, H), 4.0)
     (h[:, -1, :] * T.from_numpy(wl)).sum().backward()
     worst = []
     for name in targets:
@@ -253,7 +243,7 @@ def test_full_finetune_step_128_mels_matches_fp64_autograd(T, gww):
     (enc(mel_t).last_hidden_state[:, -1, :] * T.from_numpy(wl).cuda().float()).sum().backward()
     p64 = {k: T.from_numpy(v).double().requires_grad_(True) for k, v in sd.items()}
     mel64 = mel.double().cpu().requires_grad_(True)
-    (_encoder64(T, p64, mel64, (d, L, H))[:, -1, :] * T.from_numpy(wl)).sum().backward()
+    (encoder64(T, p64, mel64, (d, L, H))[:, -1, :] * T.from_numpy(wl)).sum().backward()
     worst = []
     for n, p in enc.named_parameters():
         g_ = p.grad.double().cpu()
