@@ -69,6 +69,7 @@ int launch_ln_param_grads(const float* x, const void* dy, int dy_f32, long M, in
                           void* workspace, size_t ws_bytes, hipStream_t s);
 size_t ln_param_grads_workspace_bytes(long M, int d);
 int launch_pos_grad(const float* dx0, float* dpos, int B, int T, int d, hipStream_t s);
+int launch_attention_probs(const void* qkv, bool bf16, bool q_log2, float* probs, int B, int T, int H, hipStream_t s);
 }
 
 using namespace gww;
@@ -467,9 +468,12 @@ extern "C" int gww_encoder_set_split(gww_encoder* e, int on) {
   return GWW_OK;
 }
 
+// hidden_slab / attn_slab (gww_encoder_forward_outputs): per-layer outputs, layer l at + l * hs_stride / as_stride
+// elements.  They only ADD stores and launches: every launch that feeds last_hidden is the one the plain forward makes.
 static int forward_impl(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
                         size_t workspace_bytes, float* last_hidden, float* last_token, void* stream,
-                        hipEvent_t skew_event = nullptr) {
+                        hipEvent_t skew_event = nullptr, float* hidden_slab = nullptr, float* attn_slab = nullptr,
+                        size_t hs_stride = 0, size_t as_stride = 0) {
   GWW_REQUIRE(e && mel, "gww_encoder_forward: NULL argument");
   if (!e->ready) return fail(GWW_ERR_STATE, "gww_encoder_forward: weights not set");
   GWW_REQUIRE(precision == GWW_PREC_BF16 || precision == GWW_PREC_F32, "gww_encoder_forward: bad precision %d",
@@ -551,7 +555,8 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   const bool fuse_qkv = mlp_fused && !(generic_mask & 16);                          // bit 4 = stand-alone LN1 + QKV kernels
   bool qkv_done = false;
   // only the last token wanted: the last layer runs on B rows above its attention (bit 5 of the mask disables it)
-  const bool pooled = astat && !last_hidden && last_token && T >= 3 && !(generic_mask & 32);
+  const bool outs = hidden_slab || attn_slab;   // per-layer outputs wanted: every layer runs on all rows
+  const bool pooled = astat && !last_hidden && last_token && T >= 3 && !(generic_mask & 32) && !outs;
   if (conv1_direct)
     TR(TR_CONV1, launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s));
   else if (bf && d % 128 == 0 && !(generic_mask & 2))
@@ -570,6 +575,24 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
                       T + 1));
   const bool q_log2 = attention_log2q_enabled();   // the LN-folded q panel carries log2(e) (pack_weights)
   float* xc = x;                       // current residual stream
+  // per-layer outputs: hidden_states[l] = the residual stream entering layer l (complete: no delta pending where it is
+  // tapped), attentions[l] = softmax of the q / k in qkv, read before the next launch overwrites qkv;
+  // hidden_states[L] = last_hidden (a copy unless the caller placed last_hidden in the slab)
+  auto tap_hidden = [&](int l, const float* src) -> int {
+    if (hidden_slab)
+      GWW_HIP(hipMemcpyAsync(hidden_slab + (size_t)l * hs_stride, src, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+    return GWW_OK;
+  };
+  auto tap_attn = [&](int l) -> int {
+    if (attn_slab) GWW_TRY(launch_attention_probs(qkv, bf, bf && q_log2, attn_slab + (size_t)l * as_stride, B, T, H, s));
+    return GWW_OK;
+  };
+  auto tap_final = [&]() -> int {
+    float* dst = hidden_slab ? hidden_slab + (size_t)e->cfg.n_layers * hs_stride : nullptr;
+    if (dst && dst != last_hidden)
+      GWW_HIP(hipMemcpyAsync(dst, last_hidden, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+    return GWW_OK;
+  };
   const void* pending = nullptr;       // bf16 delta not yet added to xc (A-stationary path)
   if (astat) {
     // Deferred residual: out_proj / fc2 emit a bf16 delta; the NEXT LayerNorm prologue does
@@ -590,6 +613,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
         }
       }
       qkv_done = false;
+      GWW_TRY(tap_hidden(i, xc));   // (the q / k / v step above folded any pending delta into xc)
       if (i == 0 && skew_event) GWW_HIP(hipEventRecord(skew_event, s));   // the other half batch starts here
       if (pooled && i == e->cfg.n_layers - 1) {
         // ---- pooled forward: only token T-1 is wanted (Signal_vs_Noise/src/model.py:25-26) and everything above
@@ -611,6 +635,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
         return GWW_OK;
       }
       TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, q_log2));
+      GWW_TRY(tap_attn(i));   // before the fused block below writes the next layer's q / k / v over qkv
       // out_proj fused in front of the MLP block (ctx is the A operand of a GEMM into the block's idle output
       // accumulators; the bf16 delta never reaches HBM): needs no delta pending on xc, which holds on this path
       const bool op = mlp_fused && fuse_qkv && !pending && !(generic_mask & 128);
@@ -636,6 +661,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
         if (last_token)
           GWW_HIP(hipMemcpy2DAsync(last_token, (size_t)d * 4, last_hidden + (size_t)(T - 1) * d, (size_t)T * d * 4, (size_t)d * 4,
                                    B, hipMemcpyDeviceToDevice, s));
+        GWW_TRY(tap_final());
         return GWW_OK;
       }
       if (mlp_fused) {
@@ -652,9 +678,10 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
     }
   } else {
     // only the last token wanted (bf16 generic path, e.g. whisper-small): same pooled last layer as above
-    const bool pooled_g = bf && !last_hidden && last_token && T >= 3 && !(generic_mask & 32);
+    const bool pooled_g = bf && !last_hidden && last_token && T >= 3 && !(generic_mask & 32) && !outs;
     for (int i = 0; i < e->cfg.n_layers; ++i) {
       const LayerW& L = e->layers[i];
+      GWW_TRY(tap_hidden(i, x));
       TR(TR_LN, launch_layernorm(x, L.ln1w, L.ln1b, h, bf ? 1 : 0, M, d, s));
       TR(TR_QKV, gemm(h, d, L.wqkv, L.wqkv32, bf ? L.bqkv16 : L.bqkv, nullptr, nullptr, qkv, M, 3 * d, d, EPI_BIAS, 0));
       if (pooled_g && i == e->cfg.n_layers - 1) {
@@ -675,6 +702,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
       }
       if (bf) TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, q_log2));
       else TR(TR_ATTN, launch_attention_f32((const float*)qkv, (float*)ctx, B, T, H, s));
+      GWW_TRY(tap_attn(i));
       TR(TR_OUT, gemm(ctx, d, L.wo, L.wo32, L.bo, x, nullptr, x, M, d, d, EPI_RESID, 0));
       TR(TR_LN, launch_layernorm(x, L.ln2w, L.ln2b, h, bf ? 1 : 0, M, d, s));
       TR(TR_FC1, gemm(h, d, L.w1, L.w132, L.b1, nullptr, nullptr, f1, M, F, d, EPI_GELU, 0));
@@ -687,17 +715,24 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   if (last_token)
     TR(TR_LNROWS, launch_layernorm_rows(xc + (long)(T - 1) * d, (long)T * d, e->lnw, e->lnb, last_token, B, d, s,
                                     pending ? (const char*)pending + (size_t)(T - 1) * d * 2 : nullptr));
+  if (last_hidden) GWW_TRY(tap_final());
 #undef TR
   return GWW_OK;
 }
 
 
-extern "C" int gww_encoder_forward(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
-                                   size_t workspace_bytes, float* last_hidden, float* last_token,
-                                   void* stream) {
+// the plain forward and gww_encoder_forward_outputs: with the split on, both slabs are offset for the second half as
+// last_hidden is (their layer strides stay those of the full batch)
+static int forward_split(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
+                         size_t workspace_bytes, float* last_hidden, float* last_token, float* hidden_slab,
+                         float* attn_slab, void* stream) {
   GWW_REQUIRE(e && mel, "gww_encoder_forward: NULL argument");
+  const size_t T_ = (size_t)(e->cfg.t_in / 2);
+  const size_t hs_stride = (size_t)(batch > 0 ? batch : 0) * T_ * e->cfg.d_model;
+  const size_t as_stride = (size_t)(batch > 0 ? batch : 0) * e->cfg.n_heads * T_ * T_;
   if (batch <= 0 || !use_split(e, batch))
-    return forward_impl(e, mel, batch, precision, workspace, workspace_bytes, last_hidden, last_token, stream);
+    return forward_impl(e, mel, batch, precision, workspace, workspace_bytes, last_hidden, last_token, stream, nullptr,
+                        hidden_slab, attn_slab, hs_stride, as_stride);
   // two independent half batches on two streams, forked from / joined to the caller's stream
   hipStream_t s = (hipStream_t)stream;
   const int d = e->cfg.d_model, T = e->cfg.t_in / 2;
@@ -715,13 +750,34 @@ extern "C" int gww_encoder_forward(gww_encoder* e, const float* mel, int batch, 
                                 (char*)workspace + (i ? w0 : 0), i ? w1 : w0,
                                 last_hidden ? last_hidden + (size_t)off * T * d : nullptr,
                                 last_token ? last_token + (size_t)off * d : nullptr, e->s2[i],
-                                (i == 0 && skew) ? e->ev_skew : nullptr);
+                                (i == 0 && skew) ? e->ev_skew : nullptr,
+                                hidden_slab ? hidden_slab + (size_t)off * T * d : nullptr,
+                                attn_slab ? attn_slab + (size_t)off * e->cfg.n_heads * T_ * T_ : nullptr, hs_stride, as_stride);
     if (rc != GWW_OK) return rc;
     GWW_HIP(hipEventRecord(e->ev_join[i], e->s2[i]));
     GWW_HIP(hipStreamWaitEvent(s, e->ev_join[i], 0));
     off += b[i];
   }
   return GWW_OK;
+}
+
+extern "C" int gww_encoder_forward(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
+                                   size_t workspace_bytes, float* last_hidden, float* last_token,
+                                   void* stream) {
+  return forward_split(e, mel, batch, precision, workspace, workspace_bytes, last_hidden, last_token, nullptr, nullptr,
+                       stream);
+}
+
+extern "C" int gww_encoder_forward_outputs(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
+                                           size_t workspace_bytes, float* last_hidden, float* hidden_slab,
+                                           float* attn_slab, void* stream) {
+  GWW_REQUIRE(e && mel, "gww_encoder_forward_outputs: NULL argument");
+  // last_hidden may be left NULL when hidden_slab is given: layer L of the slab is then last_hidden_state itself
+  if (!last_hidden && hidden_slab && batch > 0)
+    last_hidden = hidden_slab + (size_t)e->cfg.n_layers * batch * (e->cfg.t_in / 2) * e->cfg.d_model;
+  GWW_REQUIRE(last_hidden != nullptr, "gww_encoder_forward_outputs: no last_hidden and no hidden_slab");
+  return forward_split(e, mel, batch, precision, workspace, workspace_bytes, last_hidden, nullptr, hidden_slab, attn_slab,
+                       stream);
 }
 
 

@@ -14,7 +14,10 @@ Mirrors the HuggingFace surface the reference uses:
 * ``encoder(mel)`` takes ``[B, num_mel_bins, 3000]`` fp32 (80 mels, 128 for large-v3) on the GPU and returns an object
   with ``.last_hidden_state [B, 1500, d]`` (``src/model.py:25-26``);
   ``encoder.config.d_model`` exists (``src/model.py:11``);
-* ``gradient_checkpointing_enable()`` is accepted (``MLGWSC-1/train.py:662``).
+* ``gradient_checkpointing_enable()`` is accepted (``MLGWSC-1/train.py:662``);
+* ``encoder(mel, output_hidden_states=True, output_attentions=True)`` returns HF's per-layer outputs
+  (``.hidden_states``: L + 1 tensors ``[B, 1500, d]``, ``.attentions``: L tensors ``[B, H, 1500, 1500]``, eager
+  attention's ``attn_weights``), inference only; ``return_dict=False`` returns HF's plain tuple.
 
 The submodules hold parameters only; all arithmetic runs in the HIP library.
 Calling the module with CPU tensors raises -- there is no CPU fallback.
@@ -43,6 +46,10 @@ class WhisperConfig:
     num_mel_bins: int = 80
     max_source_positions: int = 1500
     dropout: float = 0.0
+    # what forward() returns when its keyword is None (HF PretrainedConfig fields of the same names)
+    output_hidden_states: bool = False
+    output_attentions: bool = False
+    return_dict: bool = True
 
     @staticmethod
     def named(name: str) -> "WhisperConfig":
@@ -52,21 +59,33 @@ class WhisperConfig:
     @staticmethod
     def from_json_file(path: str) -> "WhisperConfig":
         """The encoder fields of an HF Whisper ``config.json`` (what ``save_pretrained`` writes); a missing
-        ``num_mel_bins`` means 80, as in HF."""
+        ``num_mel_bins`` means 80, as in HF; so do the output flags that are absent."""
         import json
         with open(path) as f:
             j = json.load(f)
         return WhisperConfig(j["d_model"], j["encoder_layers"], j["encoder_attention_heads"], j["encoder_ffn_dim"],
                              num_mel_bins=j.get("num_mel_bins", 80),
-                             max_source_positions=j.get("max_source_positions", 1500))
+                             max_source_positions=j.get("max_source_positions", 1500),
+                             output_hidden_states=bool(j.get("output_hidden_states", False)),
+                             output_attentions=bool(j.get("output_attentions", False)),
+                             return_dict=bool(j.get("return_dict", True)))
 
 
 @dataclass
 class BaseModelOutput:
+    """HF ``BaseModelOutput``: the tuple view (indexing, ``to_tuple()``, ``return_dict=False``) skips the fields that
+    are None, so ``o[0]`` is always ``last_hidden_state``."""
     last_hidden_state: torch.Tensor
+    hidden_states: tuple | None = None
+    attentions: tuple | None = None
+
+    def to_tuple(self) -> tuple:
+        return tuple(v for v in (self.last_hidden_state, self.hidden_states, self.attentions) if v is not None)
 
     def __getitem__(self, i):
-        return (self.last_hidden_state,)[i]
+        if isinstance(i, str):
+            return getattr(self, i)
+        return self.to_tuple()[i]
 
 
 # Structure epoch: bumped whenever a sub-module or parameter is (re)assigned on one of the encoder's own module classes -- which is
@@ -376,8 +395,8 @@ class WhisperEncoder(_Tracked):
             self._ws = torch.empty((need,), dtype=torch.uint8, device=device)
         return self._ws
 
-    def forward_raw(self, input_features: torch.Tensor, want_hidden: bool = True, want_last: bool = False):
-        """Launch the HIP forward; returns (last_hidden_state | None, last_token | None)."""
+    def _launch_input(self, input_features: torch.Tensor):
+        """Checked fp32 contiguous input of a HIP forward and the library precision code."""
         x = input_features
         if not x.is_cuda:
             raise _lib.GwwError("WhisperEncoder.forward needs GPU tensors: gw_whisper_amd has no CPU fallback "
@@ -390,8 +409,13 @@ class WhisperEncoder(_Tracked):
         if next(self.parameters()).device != x.device:
             raise _lib.GwwError("encoder parameters and input are on different devices")
         x = x.to(torch.float32).contiguous()
+        return x, {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
+
+    def forward_raw(self, input_features: torch.Tensor, want_hidden: bool = True, want_last: bool = False):
+        """Launch the HIP forward; returns (last_hidden_state | None, last_token | None)."""
+        x, prec = self._launch_input(input_features)
+        c = self.config
         B = x.shape[0]
-        prec = {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
         with torch.cuda.device(x.device):
             self._sync_weights()
             ws = self._workspace(B, prec, x.device)
@@ -403,6 +427,28 @@ class WhisperEncoder(_Tracked):
                                             last.data_ptr() if want_last else None,
                                             torch.cuda.current_stream().cuda_stream), "gww_encoder_forward")
         return hidden, last
+
+    def forward_outputs_raw(self, input_features: torch.Tensor, want_hidden_states: bool, want_attentions: bool):
+        """Launch the HIP forward with HF's per-layer outputs (gww_encoder_forward_outputs); returns
+        (last_hidden_state, hidden_states | None, attentions | None).  Each output is a view of one fp32 slab;
+        ``hidden_states[-1]`` is ``last_hidden_state`` itself."""
+        x, prec = self._launch_input(input_features)
+        c = self.config
+        B, T, d, L, H = x.shape[0], c.max_source_positions, c.d_model, c.encoder_layers, c.encoder_attention_heads
+        f32 = dict(dtype=torch.float32, device=x.device)
+        with torch.cuda.device(x.device):
+            self._sync_weights()
+            ws = self._workspace(B, prec, x.device)
+            hs = torch.empty((L + 1, B, T, d), **f32) if want_hidden_states else None
+            last = hs[L] if want_hidden_states else torch.empty((B, T, d), **f32)
+            at = torch.empty((L, B, H, T, T), **f32) if want_attentions else None
+            check(lib().gww_encoder_forward_outputs(self._handle, x.data_ptr(), B, prec, ws.data_ptr(), ws.numel(),
+                                                    last.data_ptr(), hs.data_ptr() if hs is not None else None,
+                                                    at.data_ptr() if at is not None else None,
+                                                    torch.cuda.current_stream().cuda_stream), "gww_encoder_forward_outputs")
+        hidden_states = tuple(hs[:L].unbind(0)) + (last,) if hs is not None else None
+        attentions = tuple(at.unbind(0)) if at is not None else None
+        return last, hidden_states, attentions
 
     def set_split(self, on: bool = True):
         """Process large batches as two half batches on two streams (see gww_encoder_set_split)."""
@@ -421,14 +467,30 @@ class WhisperEncoder(_Tracked):
         check(lib().gww_encoder_trace_read(self._ensure_handle(), ms, cnt), "gww_encoder_trace_read")
         return {lib().gww_encoder_trace_class_name(i).decode(): (float(ms[i]), int(cnt[i])) for i in range(n)}
 
-    def forward(self, input_features, attention_mask=None, **kwargs):
+    def forward(self, input_features, attention_mask=None, output_hidden_states=None, output_attentions=None,
+                return_dict=None, **kwargs):
+        """HF ``WhisperEncoder.forward``: ``None`` flags fall back to the config.  ``output_hidden_states`` /
+        ``output_attentions`` are inference only (no gradient flows through them): with autograd on and trainable
+        adapters (or an input that requires grad) they raise."""
+        c = self.config
+        want_h = c.output_hidden_states if output_hidden_states is None else bool(output_hidden_states)
+        want_a = c.output_attentions if output_attentions is None else bool(output_attentions)
+        as_dict = c.return_dict if return_dict is None else bool(return_dict)
         self._check_input(input_features)
         if self._wants_grad(input_features):
+            if want_h or want_a:
+                raise _lib.GwwError("WhisperEncoder: output_hidden_states / output_attentions are inference only (no "
+                                    "gradient flows through them): run under torch.no_grad() or freeze the adapters")
             # DoRA training step: HIP forward that keeps activations + HIP backward (training.py)
             from .training import encoder_train_forward
-            return BaseModelOutput(last_hidden_state=encoder_train_forward(self, input_features))
-        hidden, _ = self.forward_raw(input_features, want_hidden=True, want_last=False)
-        return BaseModelOutput(last_hidden_state=hidden)
+            out = BaseModelOutput(last_hidden_state=encoder_train_forward(self, input_features))
+        elif want_h or want_a:
+            last, hs, at = self.forward_outputs_raw(input_features, want_h, want_a)
+            out = BaseModelOutput(last_hidden_state=last, hidden_states=hs, attentions=at)
+        else:
+            hidden, _ = self.forward_raw(input_features, want_hidden=True, want_last=False)
+            out = BaseModelOutput(last_hidden_state=hidden)
+        return out if as_dict else out.to_tuple()
 
     def _wants_grad(self, input_features) -> bool:
         if not torch.is_grad_enabled():

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -130,6 +130,18 @@ size_t gww_encoder_workspace_bytes(const gww_encoder* enc, int batch, int precis
 int gww_encoder_forward(gww_encoder* enc, const float* mel, int batch, int precision,
                         void* workspace, size_t workspace_bytes,
                         float* last_hidden, float* last_token, void* stream);
+/* The forward with HF's per-layer outputs (output_hidden_states / output_attentions), inference only.  Same
+ * workspace as gww_encoder_forward; last_hidden is bit-identical to what gww_encoder_forward writes (this entry only
+ * adds stores and launches; the pooled last-layer shortcut does not apply).  Each slab may be NULL:
+ *   hidden_slab [L+1, batch, 1500, d] fp32: [0] stem output + positions, [l] (0 < l < L) the residual stream
+ *               leaving layer l-1 (before any LayerNorm), [L] last_hidden_state.  last_hidden may be NULL when
+ *               hidden_slab is given: slab layer L is then written directly; otherwise it receives a copy.
+ *   attn_slab   [L, batch, n_heads, 1500, 1500] fp32: layer l's softmax(q k^T / 8) before dropout (HF eager
+ *               attn_weights), from gww_attention_probs_* on the layer's qkv.
+ * The layer strides are those of the full batch (also with the split on: the second half batch is offset). */
+int gww_encoder_forward_outputs(gww_encoder* enc, const float* mel, int batch, int precision,
+                                void* workspace, size_t workspace_bytes, float* last_hidden,
+                                float* hidden_slab, float* attn_slab, void* stream);
 
 /* Dual-stream split (off by default): batches of >= 64 segments are processed as two independent
  * half batches on two library-owned streams forked from / joined to the caller's stream, so the
@@ -449,6 +461,12 @@ int gww_attention_bwd_log2q_bf16(const void* qkv, const void* ctx, const void* d
                                  float* d_scratch, void* dqkv, int B, int T, int n_heads, void* stream);
 /* forward attention that also returns the row log-sum-exp lse [B,H,T] */
 int gww_attention_lse_bf16(const void* qkv, void* ctx, float* lse, int B, int T, int n_heads, void* stream);
+/* attention probabilities P[b,h,i,j] = softmax_j(q_i . k_j), fp32 [B, n_heads, T, T] (HF eager attn_weights) from
+ * qkv [B*T, 3d] as the attention kernels read it (q pre-scaled by 1/8; bf16: times log2(e) when q_log2 != 0, the
+ * encoder's packed bf16 q panels).  Scores by MFMA on the given operands (bf16: 32x32x16 bf16, fp32: 32x32x2 f32);
+ * each workgroup takes the row max / sum over all keys, then recomputes and stores the normalised rows.  T % 4 == 0. */
+int gww_attention_probs_bf16(const void* qkv, int q_log2, float* probs, int B, int T, int n_heads, void* stream);
+int gww_attention_probs_f32(const float* qkv, float* probs, int B, int T, int n_heads, void* stream);
 /* LayerNorm backward: dx (+)= dLN/dx . dy   (dy fp32 or bf16; optional bf16 copy of the result) */
 int gww_layernorm_bwd(const float* x, const float* gamma, const void* dy, int dy_is_f32, float* dx,
                       int accumulate, void* dx_bf16, long M, int d, void* stream);
