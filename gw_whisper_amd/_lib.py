@@ -92,6 +92,7 @@ SIGNATURES = {
                                              C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_void_p]),
     "gww_train_workspace_bytes_full": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "gww_train_workspace_bytes_adapters": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "gww_encoder_train_backward_full": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_int, C.POINTER(EncGrads), C.c_void_p]),
@@ -113,6 +114,11 @@ SIGNATURES = {
     "gww_dora_grads": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_float,
                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_void_p]),
+    "gww_adapter_grads_scratch_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int, C.c_int]),
+    "gww_adapter_grads": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_float,
+                                    C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                    C.c_void_p]),
     "gww_dora_grads_multi": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_int,
                                        C.POINTER(C.c_long), C.POINTER(C.c_void_p), C.POINTER(C.c_float),
                                        C.POINTER(C.c_float), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),

@@ -25,6 +25,8 @@
 //             the same accumulator collects sum_rows dy_p (the bias term of dm).
 // Accumulators stay in registers over all tiles of the workgroup; each workgroup then stores its partial sums to a
 // slab of scratch memory and k_dora_reduce adds the (at most 256) slabs into the gradients.
+#include <algorithm>
+
 #include "common.h"
 
 namespace gww {
@@ -382,6 +384,331 @@ int launch_dora_grads_multi(const void* X, long ldx, const void* dY, const void*
   return GWW_OK;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Adapter gradients of any adapted linear layer: rectangular projections (fc1 [4d, d], fc2 [d, 4d]) and every rank
+// 1..64 (the kernels above serve r = 8 on [d, d] only).  Same contract as k_dora_grads (x [M, d_in], dy / y [M, d_out]
+// bf16 with row strides, bias in stored units, g = yscale mag / nrm, gradients ACCUMULATED), in three launches:
+//   prep    Wu = bf16 A [RP][d_in], Wv = bf16 (g . B)^T [RP][d_out]; ranks r .. RP - 1 zero (RP = 32 or 64)
+//   uv      u = x Wu^T, v = dy Wv^T  [RP][Mp] bf16, rank-major; 32 rows per wave on the 32x32x16 MFMA: each lane
+//           streams 64 contiguous bytes of its row per 64-column step (the contraction's k order is permuted alike
+//           in both operands, so a half-wave covers 128 contiguous bytes of a row)
+//   outer   one workgroup per (128-column block of x or of dy, row split): the 32-row tile goes through ONE LDS
+//           image in the dual layout above and is read transposed (ds_read_b64_tr_b16) as the A operand of
+//           dA^T[col][rank] += x^T v  or  dB[col][rank] += dy^T u; the column sums of dy y and dy (dm) ride on the
+//           staging threads.  Each workgroup stores its partial sums to the slab of its row split
+//   reduce  sums the slabs in a fixed order and adds the scaled sums to dA / dB / dm (one thread per element: no
+//           float atomics, two identical calls give identical bits)
+// The row-wise contractions need the whole row, the outer products want the columns split across workgroups
+// (r (d_in + d_out) fp32 accumulators do not fit one workgroup at r = 64, d = 1280): x and dy are read twice,
+// y once.
+namespace {
+struct AdapterPlan {
+  int RP, n_cb, n_rs;
+  long Mp, E;                                   // padded rows; floats per slab
+  size_t wu, wv, u, v, slab, total;             // byte offsets inside the scratch
+};
+AdapterPlan adapter_plan(long M, int d_in, int d_out, int r) {
+  AdapterPlan p{};
+  p.RP = r <= 32 ? 32 : 64;
+  p.Mp = (M + 31) / 32 * 32;
+  p.n_cb = (d_in + d_out) / 128;
+  long rs = cdiv(1024, p.n_cb);                 // ~4 workgroups per CU in the outer-product pass
+  rs = std::min(rs, std::min(std::max(p.Mp / 32, 1L), 128L));
+  p.n_rs = (int)std::max(rs, 1L);
+  p.E = (long)p.RP * (d_in + d_out) + 2L * d_out;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
+  p.wu = take((size_t)p.RP * d_in * 2);
+  p.wv = take((size_t)p.RP * d_out * 2);
+  p.u = take((size_t)p.RP * p.Mp * 2);
+  p.v = take((size_t)p.RP * p.Mp * 2);
+  p.slab = take((size_t)p.n_rs * p.E * 4);
+  p.total = off;
+  return p;
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void k_adapter_prep(const float* __restrict__ A, const float* __restrict__ Bm,
+                                                      const float* __restrict__ mag, const float* __restrict__ nrm,
+                                                      float yscale, int r, int RP, int d_in, int d_out,
+                                                      __bf16* __restrict__ Wu, __bf16* __restrict__ Wv) {
+  const long n_u = (long)RP * d_in, n = n_u + (long)RP * d_out;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    if (i < n_u) {
+      const int j = (int)(i / d_in);
+      Wu[i] = (__bf16)(j < r ? A[i] : 0.f);
+    } else {
+      const long q = i - n_u;
+      const int j = (int)(q / d_out), c = (int)(q - (long)j * d_out);
+      Wv[q] = (__bf16)(j < r ? yscale * (mag[c] / nrm[c]) * Bm[(long)c * r + j] : 0.f);
+    }
+  }
+}
+
+// blockIdx.y = 0: u from x, 1: v from dy.  Rows M .. Mp - 1 come out zero.
+template <int NB>
+__global__ __launch_bounds__(256) void k_adapter_uv(const unsigned short* __restrict__ X, long ldx,
+                                                    const unsigned short* __restrict__ dY, long ldy,
+                                                    const __bf16* __restrict__ Wu, const __bf16* __restrict__ Wv,
+                                                    int d_in, int d_out, long M, long Mp, unsigned short* __restrict__ U,
+                                                    unsigned short* __restrict__ V) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n = lane & 31, hh = lane >> 5;
+  const long row0 = (long)blockIdx.x * 128 + 32 * wave;
+  if (row0 >= Mp) return;
+  const bool isv = blockIdx.y == 1;
+  const int K = isv ? d_out : d_in;
+  const long row = row0 + n;
+  const bool ok = row < M;
+  const unsigned short* a_ptr = (isv ? dY : X) + (ok ? row : 0L) * (isv ? ldy : ldx) + 32 * hh;
+  const __bf16* b_ptr = (isv ? Wv : Wu) + (long)n * K + 32 * hh;
+  f32x16 acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[nb][j] = 0.f;
+  // k-step s of the 64-column group k0 holds columns k0 + 32 hh + 8 s .. + 7 in BOTH operands; the next group's
+  // operands are loaded before this group's MFMAs (two groups, 128 bytes of the row per lane, in flight)
+  u32x4 a[4], b[NB][4];
+  auto load = [&](int k0) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      a[s] = ok ? *reinterpret_cast<const u32x4*>(a_ptr + k0 + 8 * s) : u32x4{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) b[nb][s] = *reinterpret_cast<const u32x4*>(b_ptr + (long)nb * 32 * K + k0 + 8 * s);
+    }
+  };
+  load(0);
+  for (int k0 = 0; k0 < K; k0 += 64) {
+    u32x4 ac[4], bc[NB][4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+      ac[s] = a[s];
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb) bc[nb][s] = b[nb][s];
+    }
+    if (k0 + 64 < K) load(k0 + 64);
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac[s]),
+                                                          __builtin_bit_cast(bf16x8, bc[nb][s]), acc[nb], 0, 0, 0);
+  }
+  // acc[4 c + e] = out[row 8 c + 4 hh + e][rank n]  ->  [rank][row]
+  unsigned short* out = isv ? V : U;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      *reinterpret_cast<u32x2*>(out + (long)(32 * nb + n) * Mp + row0 + 8 * c + 4 * hh) =
+          u32x2{pack2bf(acc[nb][4 * c], acc[nb][4 * c + 1]), pack2bf(acc[nb][4 * c + 2], acc[nb][4 * c + 3])};
+}
+
+// blockIdx.x < d_in / 128: column block of x (dA); otherwise of dy / y (dB, dm).  blockIdx.y: row split.
+//   slab (floats): dA^T-blocks [RP][d_in] | dB [RP][d_out] | sum dy y [d_out] | sum dy [d_out]
+template <int NB>
+__global__ __launch_bounds__(256) void k_adapter_outer(const unsigned short* __restrict__ X, long ldx,
+                                                       const unsigned short* __restrict__ dY,
+                                                       const unsigned short* __restrict__ Y, long ldy,
+                                                       const unsigned short* __restrict__ U,
+                                                       const unsigned short* __restrict__ V, int d_in, int d_out,
+                                                       long M, long Mp, long E, float* __restrict__ scratch) {
+  __shared__ __attribute__((aligned(16))) unsigned char img[32 * 256];
+  __shared__ float red[2][16][128];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, n = lane & 31, hh = lane >> 5;
+  const int nbx = d_in / 128;
+  const bool isx = (int)blockIdx.x < nbx;
+  const int col0 = 128 * (isx ? (int)blockIdx.x : (int)blockIdx.x - nbx);
+  const unsigned short* src = isx ? X : dY;
+  const long ld = isx ? ldx : ldy;
+  const unsigned short* opB = isx ? V : U;      // dA^T = x^T v,  dB = dy^T u
+  const int c8 = tid & 15, ph = tid >> 4;       // staging: chunk c8 of rows ph and ph + 16
+  float sy[8], sd[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) sy[j] = sd[j] = 0.f;
+  f32x16 acc[NB];
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[nb][j] = 0.f;
+
+  const long n_tiles = Mp / 32;
+  u32x4 pa[2], py[2], pb[NB][2];
+  // the next tile's operands are in flight while the current one is on the matrix cores
+  auto fetch = [&](long t) {
+    const long r0 = t * 32;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const long row = r0 + ph + 16 * i;
+      const bool ok = row < M;
+      pa[i] = ok ? *reinterpret_cast<const u32x4*>(src + row * ld + col0 + 8 * c8) : u32x4{0u, 0u, 0u, 0u};
+      py[i] = (ok && !isx) ? *reinterpret_cast<const u32x4*>(Y + row * ldy + col0 + 8 * c8) : u32x4{0u, 0u, 0u, 0u};
+    }
+    // B operand rows r0 + 16 ks + {4 hh + (j & 3) + 8 (j >> 2)}: the K order of tr_frag_dual
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+      for (int ks = 0; ks < 2; ++ks) {
+        const unsigned short* p = opB + (long)(32 * nb + n) * Mp + r0 + 16 * ks + 4 * hh;
+        const u32x2 lo = *reinterpret_cast<const u32x2*>(p), hi = *reinterpret_cast<const u32x2*>(p + 8);
+        pb[nb][ks] = u32x4{lo[0], lo[1], hi[0], hi[1]};
+      }
+  };
+  long t = blockIdx.y;
+  if (t < n_tiles) fetch(t);
+  for (; t < n_tiles; t += gridDim.y) {
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      *reinterpret_cast<u32x4*>(img + dual_off(ph + 16 * i, c8)) = pa[i];
+      if (!isx) {
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+          const float d0 = bf_lo(pa[i][w]), d1 = bf_hi(pa[i][w]);
+          sy[2 * w] = fmaf(d0, bf_lo(py[i][w]), sy[2 * w]);
+          sy[2 * w + 1] = fmaf(d1, bf_hi(py[i][w]), sy[2 * w + 1]);
+          sd[2 * w] += d0;
+          sd[2 * w + 1] += d1;
+        }
+      }
+    }
+    u32x4 b[NB][2];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) { b[nb][0] = pb[nb][0]; b[nb][1] = pb[nb][1]; }
+    __syncthreads();
+    if (t + gridDim.y < n_tiles) fetch(t + gridDim.y);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) {
+      const bf16x8 a = tr_frag_dual(img, 16 * ks, wave, lane);
+#pragma unroll
+      for (int nb = 0; nb < NB; ++nb)
+        acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, __builtin_bit_cast(bf16x8, b[nb][ks]), acc[nb], 0, 0, 0);
+    }
+  }
+
+  // acc[4 c + e] = out[column 32 wave + 8 c + 4 hh + e][rank n]
+  float* slab = scratch + (long)blockIdx.y * E;
+  float* dst = slab + (isx ? 0L : (long)NB * 32 * d_in);
+  const int ldo = isx ? d_in : d_out;
+#pragma unroll
+  for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      *reinterpret_cast<f32x4*>(dst + (long)(32 * nb + n) * ldo + col0 + 32 * wave + 8 * c + 4 * hh) =
+          f32x4{acc[nb][4 * c], acc[nb][4 * c + 1], acc[nb][4 * c + 2], acc[nb][4 * c + 3]};
+  if (!isx) {   // column sums of the 16 row phases, in a fixed order
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      red[0][ph][8 * c8 + j] = sy[j];
+      red[1][ph][8 * c8 + j] = sd[j];
+    }
+    __syncthreads();
+    const int which = tid >> 7, col = tid & 127;
+    float sum = 0.f;
+#pragma unroll
+    for (int q = 0; q < 16; ++q) sum += red[which][q][col];
+    slab[(long)NB * 32 * (d_in + d_out) + (long)which * d_out + col0 + col] = sum;
+  }
+}
+
+// element i of the output (dA | dB | dm), its partial sums of the n_rs slabs: 64 elements per workgroup, four slab
+// phases per element (eight loads in flight each), combined in a fixed order
+__global__ __launch_bounds__(256) void k_adapter_reduce(const float* __restrict__ scratch, int n_rs, long E, int RP,
+                                                        int r, int d_in, int d_out, const float* __restrict__ bias,
+                                                        float yscale, float scaling, const float* __restrict__ mag,
+                                                        const float* __restrict__ nrm, float* dA, float* dB, float* dm) {
+  __shared__ float part[2][4][64];
+  const int tid = threadIdx.x, el = tid & 63, sl = tid >> 6;
+  const long nA = (long)r * d_in, nBv = (long)r * d_out, n_out = nA + nBv + d_out;
+  const long i = (long)blockIdx.x * 64 + el;
+  long o = -1, o2 = -1;   // slab offsets of the element (dm: the two column sums)
+  if (i < nA) o = i;                                          // slab index j * d_in + c == dA index
+  else if (i < nA + nBv) o = (long)RP * d_in + (i - nA);      // [rank][d_out]
+  else if (i < n_out) {
+    o = (long)RP * (d_in + d_out) + (i - nA - nBv);
+    o2 = o + d_out;
+  }
+  float s1 = 0.f, s2 = 0.f;
+  if (o >= 0) {
+#pragma unroll 8
+    for (int w = sl; w < n_rs; w += 4) {
+      s1 += scratch[(long)w * E + o];
+      if (o2 >= 0) s2 += scratch[(long)w * E + o2];
+    }
+  }
+  part[0][sl][el] = s1;
+  part[1][sl][el] = s2;
+  __syncthreads();
+  if (sl != 0 || i >= n_out) return;
+  const float s = (part[0][0][el] + part[0][1][el]) + (part[0][2][el] + part[0][3][el]);
+  if (i < nA) {
+    dA[i] += scaling * s;
+  } else if (i < nA + nBv) {
+    const long q = i - nA;
+    const int j = (int)(q / d_out), c = (int)(q - (long)j * d_out);
+    dB[(long)c * r + j] += scaling * yscale * (mag[c] / nrm[c]) * s;
+  } else {
+    const int c = (int)(i - nA - nBv);
+    const float sdd = (part[1][0][el] + part[1][1][el]) + (part[1][2][el] + part[1][3][el]);
+    dm[c] += (s - bias[c] * sdd) / mag[c];   // (sum dy y - b sum dy) / m
+  }
+}
+
+size_t adapter_grads_scratch_bytes(long M, int d_in, int d_out, int r) {
+  if (M <= 0 || d_in <= 0 || d_out <= 0 || r < 1 || r > 64) return 0;
+  return adapter_plan(M, d_in, d_out, r).total;
+}
+
+int launch_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                         float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                         const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                         hipStream_t s, void* scratch, size_t scratch_bytes) {
+  GWW_REQUIRE(r >= 1 && r <= 64, "adapter_grads: rank r=%d is outside 1..64 (the limit of the adapter-gradient kernel)",
+              r);
+  GWW_REQUIRE(d_in > 0 && d_out > 0 && d_in % 128 == 0 && d_out % 128 == 0,
+              "adapter_grads: d_in=%d and d_out=%d must be positive multiples of 128", d_in, d_out);
+  GWW_REQUIRE(M >= 0 && ldx >= d_in && ldy >= d_out && ldx % 8 == 0 && ldy % 8 == 0 &&
+                  ((((uintptr_t)X) | ((uintptr_t)dY) | ((uintptr_t)Y)) & 15) == 0,
+              "adapter_grads: row strides (ldx=%ld ldy=%ld) must be multiples of 8 elements >= d_in / d_out and X / dY / "
+              "Y 16-byte aligned", ldx, ldy);
+  if (M == 0) return GWW_OK;
+  const AdapterPlan p = adapter_plan(M, d_in, d_out, r);
+  char* ws = (char*)scratch;
+  bool own_alloc = false;
+  if (!ws || scratch_bytes < p.total) {
+    GWW_HIP(hipMallocAsync((void**)&ws, p.total, s));
+    own_alloc = true;
+  }
+  __bf16* Wu = (__bf16*)(ws + p.wu);
+  __bf16* Wv = (__bf16*)(ws + p.wv);
+  unsigned short* U = (unsigned short*)(ws + p.u);
+  unsigned short* V = (unsigned short*)(ws + p.v);
+  float* slabs = (float*)(ws + p.slab);
+  const long n_w = (long)p.RP * (d_in + d_out);
+  hipLaunchKernelGGL(k_adapter_prep, dim3((unsigned)std::min(cdiv(n_w, 256), 2048L)), dim3(256), 0, s, A, Bm, mag, nrm,
+                     yscale, r, p.RP, d_in, d_out, Wu, Wv);
+  const dim3 g_uv((unsigned)cdiv(p.Mp, 128), 2), g_out((unsigned)p.n_cb, (unsigned)p.n_rs);
+  const auto* x = (const unsigned short*)X;
+  const auto* dy = (const unsigned short*)dY;
+  const auto* y = (const unsigned short*)Y;
+  if (p.RP == 32) {
+    hipLaunchKernelGGL(k_adapter_uv<1>, g_uv, dim3(256), 0, s, x, ldx, dy, ldy, Wu, Wv, d_in, d_out, M, p.Mp, U, V);
+    hipLaunchKernelGGL(k_adapter_outer<1>, g_out, dim3(256), 0, s, x, ldx, dy, y, ldy, U, V, d_in, d_out, M, p.Mp, p.E,
+                       slabs);
+  } else {
+    hipLaunchKernelGGL(k_adapter_uv<2>, g_uv, dim3(256), 0, s, x, ldx, dy, ldy, Wu, Wv, d_in, d_out, M, p.Mp, U, V);
+    hipLaunchKernelGGL(k_adapter_outer<2>, g_out, dim3(256), 0, s, x, ldx, dy, y, ldy, U, V, d_in, d_out, M, p.Mp, p.E,
+                       slabs);
+  }
+  const long n_out = (long)r * (d_in + d_out) + d_out;
+  hipLaunchKernelGGL(k_adapter_reduce, dim3((unsigned)cdiv(n_out, 64)), dim3(256), 0, s, slabs, p.n_rs, p.E, p.RP, r,
+                     d_in, d_out, bias_st, yscale, scaling, mag, nrm, dA, dB, dm);
+  GWW_LAUNCH_CHECK();
+  if (own_alloc) GWW_HIP(hipFreeAsync(ws, s));
+  return GWW_OK;
+}
+
 }  // namespace gww
 
 using namespace gww;
@@ -395,4 +722,17 @@ extern "C" int gww_dora_grads_multi(const void* X, long ldx, const void* dY, con
               "gww_dora_grads_multi: NULL argument");
   return launch_dora_grads_multi(X, ldx, dY, Y, ldy, np, col_off, bias_st, yscale, scaling, A, B, mag, nrm, dA, dB, dm,
                                  M, d, (hipStream_t)stream, nullptr, 0);
+}
+
+extern "C" size_t gww_adapter_grads_scratch_bytes(long M, int d_in, int d_out, int r) {
+  return adapter_grads_scratch_bytes(M, d_in, d_out, r);
+}
+
+extern "C" int gww_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                                 float yscale, float scaling, const float* A, const float* B, const float* mag,
+                                 const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                                 void* scratch, size_t scratch_bytes, void* stream) {
+  GWW_REQUIRE(X && dY && Y && bias_st && A && B && mag && nrm && dA && dB && dm, "gww_adapter_grads: NULL argument");
+  return launch_adapter_grads(X, ldx, dY, Y, ldy, bias_st, yscale, scaling, A, B, mag, nrm, dA, dB, dm, M, d_in, d_out,
+                              r, (hipStream_t)stream, scratch, scratch_bytes);
 }

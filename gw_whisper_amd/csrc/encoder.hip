@@ -59,6 +59,11 @@ int launch_dora_grads_multi(const void* X, long ldx, const void* dY, const void*
                             const float* const* mag, const float* const* nrm, float* const* dA, float* const* dB,
                             float* const* dm, long M, int d, hipStream_t s, void* scratch, size_t scratch_bytes);
 size_t dora_grads_scratch_bytes(int np, int d);
+int launch_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                         float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                         const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                         hipStream_t s, void* scratch, size_t scratch_bytes);
+size_t adapter_grads_scratch_bytes(long M, int d_in, int d_out, int r);
 int launch_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse, float* D,
                               void* dqkv, int B, int T, int H, hipStream_t s, bool q_log2);
 int launch_mel_to_tokens(const float* mel, void* out, int out_bf16, int B, int C, int T, hipStream_t s);
@@ -870,6 +875,22 @@ extern "C" size_t gww_train_workspace_bytes_full(const gww_encoder* e, int batch
   return (e && batch > 0) ? train_ws(e->cfg, batch).total + train_param_scratch_bytes(e->cfg, batch) : 0;
 }
 
+// fc1 / fc2 targets and ranks other than 8 (the adapter-gradient kernel): its scratch for the largest target shape,
+// behind the backward's workspace (and behind the full fine-tuning region, should both be asked for)
+static size_t train_adapter_scratch_bytes(const gww_enc_cfg& c, int B, int max_r) {
+  const long M = (long)B * (c.t_in / 2);
+  const int d = c.d_model, F = c.ffn;
+  size_t mx = 0;
+  for (int di : {d, F})
+    for (int dd : {d, F}) mx = std::max(mx, adapter_grads_scratch_bytes(M, di, dd, max_r));
+  return align_up(mx);
+}
+
+extern "C" size_t gww_train_workspace_bytes_adapters(const gww_encoder* e, int batch, int max_r) {
+  return (e && batch > 0 && max_r >= 1 && max_r <= 64)
+             ? train_ws(e->cfg, batch).total + train_adapter_scratch_bytes(e->cfg, batch, max_r) : 0;
+}
+
 extern "C" size_t gww_train_saved_bytes(const gww_encoder* e, int batch) {
   return (e && batch > 0) ? saved_layout(e->cfg, batch).total : 0;
 }
@@ -1081,7 +1102,9 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
   const bool want_ln1_0 = L > 0 && (LGf(0).ln1_w || LGf(0).ln1_b);
   for (int i = 0; i < n_targets; ++i) {
     const gww_dora_target& t = targets[i];
-    GWW_REQUIRE(t.layer >= 0 && t.layer < L && t.proj >= 0 && t.proj <= 3, "gww_encoder_train_backward: bad target %d", i);
+    GWW_REQUIRE(t.layer >= 0 && t.layer < L && t.proj >= 0 && t.proj <= 5, "gww_encoder_train_backward: bad target %d", i);
+    GWW_REQUIRE(t.r >= 1 && t.r <= 64, "gww_encoder_train_backward: target %d has rank %d: adapter gradients support "
+                "ranks 1..64", i, t.r);
     GWW_REQUIRE(t.A && t.B && t.mag && t.nrm && t.dA && t.dB && t.dm, "gww_encoder_train_backward: NULL pointer in target %d", i);
   }
   // dX GEMMs: A-stationary kernel for the K <= 512 contractions, full-N kernel for the long-K, N = d ones
@@ -1103,7 +1126,22 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
   // the stored q is  q_ysc * (W' x + b): 1 / 8 (head_dim^-0.5), times log2(e) when the bf16 panels carry log2 units
   const float q_ysc = attention_log2q_enabled() ? 0.125f * 1.44269504088896340736f : 0.125f;
   bool multi_ok = (d == 384 || d == 512) && lab_int("GWW_DORA_OLD", 0) == 0;
-  for (int i = 0; i < n_targets; ++i) multi_ok = multi_ok && targets[i].r == 8;
+  for (int i = 0; i < n_targets; ++i) multi_ok = multi_ok && (targets[i].proj > 2 || targets[i].r == 8);
+  // fc1 / fc2 targets and ranks other than 8: the adapter-gradient kernel (dora_grads.hip), its scratch behind the
+  // workspace when the caller sized it with gww_train_workspace_bytes_adapters (else allocated stream-ordered)
+  const size_t a_off = w.total + pscr_bytes;
+  void* ascr = workspace_bytes > a_off ? base + a_off : nullptr;
+  const size_t ascr_bytes = workspace_bytes > a_off ? workspace_bytes - a_off : 0;
+  auto agrad = [&](const gww_dora_target& t, const void* X, long ldx, const void* dY, const void* Y, long ldy,
+                   const float* bias, float ysc, long rows, int d_in, int d_out) -> int {
+    return launch_adapter_grads(X, ldx, dY, Y, ldy, bias, ysc, t.scaling, t.A, t.B, t.mag, t.nrm, t.dA, t.dB, t.dm, rows,
+                                d_in, d_out, t.r, s, ascr, ascr_bytes);
+  };
+  auto find_target = [&](int l, int proj) -> const gww_dora_target* {
+    for (int i = 0; i < n_targets; ++i)
+      if (targets[i].layer == l && targets[i].proj == proj) return &targets[i];
+    return nullptr;
+  };
   // final LayerNorm backward -> dx (grad w.r.t. x_in[L]); pooled: on the B last-token rows only
   if (grads) GWW_TRY(lng(x_in(L), d_last_hidden, 1, pooled ? B : M, grads->ln_w, grads->ln_b));
   GWW_TRY(launch_ln_bwd(x_in(L), e->lnw, d_last_hidden, 1, dx, 0, dxb, pooled ? B : M, d, s));
@@ -1134,9 +1172,16 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
         GWW_TRY(wg(dxb, d, f1, F, B, d, F, 1.0f, LG.fc2_w, LG.fc2_b, 0));
       }
       GWW_TRY(launch_gelu_bf16(z, dbig, dbig, (((long)B * F + 7) / 8) * 8, s));
-      if (LG.fc1_w || LG.fc1_b) {
-        GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, ln2o, 1, B, d, s));
-        GWW_TRY(wg(dbig, F, ln2o, d, B, F, d, 1.0f, LG.fc1_w, LG.fc1_b, 0));
+      const gww_dora_target* fc1t = find_target(l, 4);
+      const gww_dora_target* fc2t = find_target(l, 5);
+      if (LG.fc1_w || LG.fc1_b || fc1t) GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, ln2o, 1, B, d, s));
+      if (LG.fc1_w || LG.fc1_b) GWW_TRY(wg(dbig, F, ln2o, d, B, F, d, 1.0f, LG.fc1_w, LG.fc1_b, 0));
+      // fc1 adapter: x = LN2(x_mid), dy = d(pre-activation), y = z;  fc2: x = gelu(z), dy = d(x_out), y = x_out - x_mid
+      if (fc1t) GWW_TRY(agrad(*fc1t, ln2o, d, dbig, z, F, W.b1, 1.0f, B, d, F));
+      if (fc2t) {
+        GWW_TRY(launch_gelu_bf16(z, nullptr, f1, (((long)B * F + 7) / 8) * 8, s));
+        GWW_TRY(launch_sub_f32_bf16(x_in(L), x_mid, dh, (long)B * d, s));
+        GWW_TRY(agrad(*fc2t, f1, F, dxb, dh, d, W.b2, 1.0f, B, F, d));
       }
       GWW_TRY(launch_gemm_bf16(dbig, F, W.w1T, nullptr, nullptr, nullptr, dh, B, d, F, EPI_BIAS, 0, s, 0));
       GWW_TRY(lng(x_mid, dh, 0, B, LG.ln2_w, LG.ln2_b));
@@ -1152,6 +1197,10 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
                                    B, hipMemcpyDeviceToDevice, s));
           GWW_TRY(launch_sub_f32_bf16(x_mid, xl, dh, (long)B * d, s));
           have_y = true;
+        }
+        if (t.r != 8) {
+          GWW_TRY(agrad(t, ctx_last, (long)T * d, dxb, dh, d, W.bo, 1.0f, B, d, d));
+          continue;
         }
         GWW_TRY(launch_dora_grads(ctx_last, (long)T * d, dxb, dh, d, W.bo, 1.0f, t.scaling, t.A, t.B, t.mag, t.nrm,
                                   t.dA, t.dB, t.dm, B, d, t.r, s, base + w.dgs, w.dgs_bytes));
@@ -1172,7 +1221,30 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
     GWW_TRY(gemm_dx(dxb, d, W.w2T, dbig, F, d));
     const bool want_fc2 = LG.fc2_w || LG.fc2_b;
     const void* ln2_out = nullptr;   // LN2(x_mid), when a weight gradient needs it
-    if (fused) {
+    const gww_dora_target* fc1t = find_target(l, 4);
+    const gww_dora_target* fc2t = find_target(l, 5);
+    if (fc1t || fc2t) {
+      // fc1 / fc2 adapters.  fc1: x = LN2(x_mid), dy = d(pre-activation), y = z (+ b1);  fc2: x = gelu(z),
+      // dy = d(x_out) (dxb), y = x_out - x_mid (+ b2).  The fused forward kept no z: it is recomputed into f1 by the
+      // A-stationary GEMM with the plain bias epilogue, and the GELU backward reads it from there.
+      const void* zz = z;
+      if (fused) {
+        GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, dctx, 1, M, d, s));
+        ln2_out = dctx;
+        GWW_TRY(launch_gemm_astat(dctx, d, nullptr, nullptr, nullptr, nullptr, W.w1, W.b1, f1, M, F, d, EPI_BIAS, 0, s));
+        zz = f1;
+      } else if (fc1t) {
+        GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, ln2o, 1, M, d, s));
+        ln2_out = ln2o;
+      }
+      GWW_TRY(launch_gelu_bf16(zz, dbig, dbig, ((M * F + 7) / 8) * 8, s));
+      if (fc1t) GWW_TRY(agrad(*fc1t, ln2_out, d, dbig, zz, F, W.b1, 1.0f, M, d, F));
+      if (fc2t || want_fc2) GWW_TRY(launch_gelu_bf16(zz, nullptr, f1, ((M * F + 7) / 8) * 8, s));   // in place when fused
+      if (fc2t) {
+        GWW_TRY(launch_sub_f32_bf16(x_in(l + 1), x_mid, dh, M * d, s));
+        GWW_TRY(agrad(*fc2t, f1, F, dxb, dh, d, W.b2, 1.0f, M, F, d));
+      }
+    } else if (fused) {
       // recompute: LN2(x_mid) (LayerNorm kernel, into the idle dctx buffer) -> fc1 as a plain A-stationary GEMM whose
       // epilogue applies gelu'(pre-activation) to the gradient in place: neither the pre-activation nor a separate
       // GELU-backward pass touches HBM
@@ -1207,6 +1279,10 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
           GWW_TRY(launch_sub_f32_bf16(x_mid, x_in(l), dh, M * d, s));
           have_y = true;
         }
+        if (t.r != 8) {
+          GWW_TRY(agrad(t, ctx, d, dxb, dh, d, W.bo, 1.0f, M, d, d));
+          continue;
+        }
         GWW_TRY(launch_dora_grads(ctx, d, dxb, dh, d, W.bo, 1.0f, t.scaling, t.A, t.B, t.mag, t.nrm, t.dA, t.dB, t.dm,
                                   M, d, t.r, s, base + w.dgs, w.dgs_bytes));
       }
@@ -1223,7 +1299,7 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
       int np = 0;
       for (int i = 0; i < n_targets; ++i) {
         const gww_dora_target& t = targets[i];
-        if (t.layer != l || t.proj == 3) continue;
+        if (t.layer != l || t.proj > 2) continue;
         GWW_REQUIRE(np < 3, "gww_encoder_train_backward: duplicate q/k/v target in layer %d", l);
         off[np] = (long)t.proj * d;
         bias[np] = W.bqkv16 + off[np];
@@ -1239,8 +1315,13 @@ static int train_backward_impl(gww_encoder* e, int batch, void* workspace, size_
     } else {
       for (int i = 0; i < n_targets; ++i) {
         const gww_dora_target& t = targets[i];
-        if (t.layer != l || t.proj == 3) continue;
+        if (t.layer != l || t.proj > 2) continue;
         const long off = (long)t.proj * d;   // q | k | v section
+        if (t.r != 8) {
+          GWW_TRY(agrad(t, h1, d, (const unsigned short*)dqkv + off, (const unsigned short*)qkv + off, 3L * d,
+                        W.bqkv16 + off, t.proj == 0 ? q_ysc : 1.0f, M, d, d));
+          continue;
+        }
         GWW_TRY(launch_dora_grads(h1, d, (const unsigned short*)dqkv + off, (const unsigned short*)qkv + off, 3L * d,
                                   W.bqkv16 + off, t.proj == 0 ? q_ysc : 1.0f, t.scaling, t.A, t.B, t.mag, t.nrm, t.dA,
                                   t.dB, t.dm, M, d, t.r, s, base + w.dgs, w.dgs_bytes));

@@ -726,11 +726,18 @@ int launch_dora_grads_multi(const void* X, long ldx, const void* dY, const void*
                             const float* const* mag, const float* const* nrm, float* const* dA, float* const* dB,
                             float* const* dm, long M, int d, hipStream_t s, void* scratch, size_t scratch_bytes);
 size_t dora_grads_scratch_bytes(int np, int d);
+int launch_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                         float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                         const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                         hipStream_t s, void* scratch, size_t scratch_bytes);
 
 int launch_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
                       float yscale, float scaling, const float* A, const float* Bm, const float* mag,
                       const float* nrm, float* dA, float* dB, float* dm, long M, int d, int r, hipStream_t s,
                       void* scratch, size_t scratch_bytes) {
+  // ranks other than 8: the adapter-gradient kernel of dora_grads.hip (its own scratch: allocated stream-ordered here)
+  if (r != 8) return launch_adapter_grads(X, ldx, dY, Y, ldy, bias_st, yscale, scaling, A, Bm, mag, nrm, dA, dB, dm, M, d,
+                                          d, r, s, nullptr, 0);
   GWW_REQUIRE(r == 8 && (d == 128 || d == 384 || d == 512 || d == 768 || d == 1024 || d == 1280),
               "dora_grads: only r = 8 and d in {128, 384, 512, 768, 1024, 1280} (got d=%d r=%d)", d, r);
   // every kernel reads 8 bf16 per load: row strides and section starts on 16-byte boundaries

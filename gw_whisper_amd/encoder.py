@@ -516,8 +516,8 @@ class WhisperEncoder(_Tracked):
 
     def _has_trainable_adapters(self) -> bool:
         for layer in self.layers:
-            for name in ("q_proj", "k_proj", "v_proj", "out_proj"):
-                mod = getattr(layer.self_attn, name)
+            mods = [getattr(layer.self_attn, n) for n in ("q_proj", "k_proj", "v_proj", "out_proj")] + [layer.fc1, layer.fc2]
+            for mod in mods:
                 if hasattr(mod, "lora_A") and any(p.requires_grad for p in mod.lora_A.parameters()):
                     return True
         return False

@@ -583,6 +583,35 @@ def dora_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm, col_off: int 
     return dA, dB, dm
 
 
+def adapter_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
+    """(dA [r, d_in], dB [d_out, r], dm [d_out]) of one adapted linear layer of any shape the encoder has -- [d, d],
+    fc1 [4d, d], fc2 [d, 4d] -- and rank 1..64 (``gww_adapter_grads``, matrix cores).  x bf16 [M, d_in]; dy, y bf16
+    [M, d_out] (the stored output, bias included); rows may be strided (stride(1) == 1, dy and y with the same stride).
+    Plain LoRA: mag = nrm = ones.  r > 64 raises GwwError."""
+    if any(t.dtype != torch.bfloat16 or not t.is_cuda for t in (x, dy, y)):
+        raise _lib.GwwError("adapter_grads: x, dy and y must be bf16 GPU tensors")
+    if x.dim() != 2 or dy.dim() != 2 or x.stride(1) != 1 or dy.stride(1) != 1 or dy.stride() != y.stride() \
+            or dy.shape != y.shape or dy.shape[0] != x.shape[0]:
+        raise _lib.GwwError("adapter_grads: 2-D x [M, d_in], dy / y [M, d_out] with contiguous rows; dy and y of the same "
+                            "shape and strides")
+    M, d_in = x.shape
+    d_out = dy.shape[1]
+    r = A.shape[0]
+    if tuple(A.shape) != (r, d_in) or tuple(B.shape) != (d_out, r):
+        raise _lib.GwwError(f"adapter_grads: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit x [{M}, {d_in}] and dy "
+                            f"[{M}, {d_out}]")
+    dA = torch.zeros((r, d_in), dtype=torch.float32, device=x.device)
+    dB = torch.zeros((d_out, r), dtype=torch.float32, device=x.device)
+    dm = torch.zeros((d_out,), dtype=torch.float32, device=x.device)
+    f = lambda t: _dev(t, torch.float32).data_ptr()
+    with torch.cuda.device(x.device):
+        check(lib().gww_adapter_grads(x.data_ptr(), x.stride(0), dy.data_ptr(), y.data_ptr(), dy.stride(0), f(bias_st),
+                                      float(yscale), float(scaling), f(A), f(B), f(mag), f(nrm), dA.data_ptr(),
+                                      dB.data_ptr(), dm.data_ptr(), M, d_in, d_out, r, None, 0, _stream()),
+              "gww_adapter_grads")
+    return dA, dB, dm
+
+
 def info_nce_forward(z1, z2, temperature: float):
     """InfoNCE of the reference's ContrastivePretrainer (``gww_info_nce_forward_f32``): z1, z2 fp32 [B, P] (P <= 1024) ->
     (loss [1] device scalar, saved = (n [2B, P], nrm [2B], lse [2B], term [2B]) for ``info_nce_backward``)."""

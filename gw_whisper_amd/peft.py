@@ -161,6 +161,11 @@ class LoraModel(nn.Module):
         super().__init__()
         self.model = model
         self.peft_config = {"default": config}
+        if list(config.target_modules or []) == ["all-linear"]:
+            # peft's "all-linear": every nn.Linear (the encoder has no output head to leave out); the config keeps the
+            # expanded module names, as peft saves them in adapter_config.json
+            config.target_modules = sorted({n.rsplit(".", 1)[-1] for n, m in model.named_modules()
+                                            if isinstance(m, nn.Linear)})
         hit = 0
         for name, mod in list(model.named_modules()):
             if isinstance(mod, nn.Linear) and _match(name, config.target_modules or []):

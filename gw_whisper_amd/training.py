@@ -3,7 +3,7 @@
 ``encoder_train_forward(encoder, mel)`` runs the HIP training forward (activations kept in an
 arena) and returns ``last_hidden_state`` as a tensor that participates in torch autograd; its
 backward calls ``gww_encoder_train_backward`` and hands the A / B / magnitude gradients of every
-DoRA-wrapped q / k / v projection to autograd, so the reference's step
+DoRA-wrapped linear layer (q / k / v / out_proj, fc1 / fc2) to autograd, so the reference's step
 
     loss = criterion(model(h1, l1), labels); loss.backward(); optimizer.step()
     (Signal_vs_Noise/src/train.py:163-168)
@@ -27,6 +27,7 @@ from ._lib import check, lib
 from .peft import DoraLinear
 
 _PROJ = {"q_proj": 0, "k_proj": 1, "v_proj": 2, "out_proj": 3}
+_MLP = {"fc1": 4, "fc2": 5}   # gww_dora_target.proj of the MLP projections (include/gww.h)
 
 
 # base parameters in the order of gww_enc_grads / gww_enc_layer_grads (include/gww.h)
@@ -60,11 +61,12 @@ def base_targets(encoder):
 
 
 def dora_targets(encoder):
-    """[(layer index, proj id, DoraLinear)] of the adapted attention projections."""
+    """[(layer index, proj id, DoraLinear)] of the adapted linear layers: q / k / v / out_proj (0..3), fc1 / fc2 (4, 5)."""
     out = []
     for li, layer in enumerate(encoder.layers):
-        for name, pid in _PROJ.items():
-            mod = getattr(layer.self_attn, name)
+        mods = [(getattr(layer.self_attn, name), pid) for name, pid in _PROJ.items()]
+        mods += [(getattr(layer, name), pid) for name, pid in _MLP.items()]
+        for mod, pid in mods:
             if isinstance(mod, DoraLinear):
                 out.append((li, pid, mod))   # use_dora=False (plain LoRA, the reference's --method LoRA) included
     return out
@@ -83,7 +85,15 @@ class _EncoderTrain(torch.autograd.Function):
             _encoder._note_training(enc)   # from now on the packed weights follow every optimizer step at once
             h = enc._ensure_handle()
             full = bool(base_targets(enc))
-            ws_bytes = lib().gww_train_workspace_bytes_full(h, B) if full else lib().gww_train_workspace_bytes(h, B)
+            # fc1 / fc2 targets or ranks other than 8 run on the adapter-gradient kernel, whose scratch the attention-only
+            # rank-8 step does not need
+            wide = [t for t in dora_targets(enc) if t[1] > 3 or t[2].r != 8]
+            if full:
+                ws_bytes = lib().gww_train_workspace_bytes_full(h, B)
+            elif wide:
+                ws_bytes = lib().gww_train_workspace_bytes_adapters(h, B, max(t[2].r for t in wide))
+            else:
+                ws_bytes = lib().gww_train_workspace_bytes(h, B)
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
             saved = torch.empty((lib().gww_train_saved_bytes(h, B),), dtype=torch.uint8, device=dev)
             shape = (B, c.d_model) if pooled else (B, c.max_source_positions, c.d_model)

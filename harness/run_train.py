@@ -52,6 +52,11 @@ class EarlyStopper:   # src/train.py:27-43
         return False
 
 
+# the adapted modules of the reference (src/train.py:232; o_proj matches nothing in HF Whisper)
+DEFAULT_LORA_TARGETS = ("layers.*.self_attn.q_proj", "layers.*.self_attn.k_proj", "layers.*.self_attn.v_proj",
+                        "layers.*.self_attn.o_proj")
+
+
 def synthetic_dataset(n, seed):
     """n two-detector 1 s segments at 16 kHz, unit-variance noise; odd indices carry the same chirp in both."""
     from gw_whisper_amd import synth
@@ -115,8 +120,7 @@ def main(args):
         sd = synth.encoder_state_dict(d, L, H, F, seed=args.seed, n_mels=n_mels)
         encoder.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()})
     module_names = [name for name, _ in encoder.named_modules()]
-    patterns = ["layers.*.self_attn.q_proj", "layers.*.self_attn.k_proj", "layers.*.self_attn.v_proj",
-                "layers.*.self_attn.o_proj"]                          # src/train.py:232 (o_proj matches nothing in HF Whisper)
+    patterns = args.lora_targets
     matched = [m for p in patterns for m in fnmatch.filter(module_names, p)]
     if args.method not in ("DoRA", "LoRA", "full_finetune"):
         raise ValueError(f"--method {args.method}: expected DoRA, LoRA or full_finetune")
@@ -264,6 +268,9 @@ if __name__ == "__main__":
     parser.add_argument("--method", type=str, default="DoRA")
     parser.add_argument("--lora-rank", type=int, default=8)
     parser.add_argument("--lora-alpha", type=int, default=32)
+    parser.add_argument("--lora-targets", type=str, nargs="+", default=list(DEFAULT_LORA_TARGETS), metavar="PATTERN",
+                        help="fnmatch patterns of the encoder modules to adapt (e.g. 'layers.*.fc1'); a resumed adapter "
+                             "keeps the targets it was saved with")
     parser.add_argument("--synthetic", type=int, default=0, help="use N seeded synthetic segments instead of --data-path")
     parser.add_argument("--encoder-weights", type=str, default=None, help="HF WhisperEncoder state_dict (.pth / .safetensors)")
     main(parser.parse_args())

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_adapter_grads / _scratch_bytes, gww_train_workspace_bytes_adapters (adapter gradients of fc1 / fc2 and of ranks 1..64; gww_dora_target.proj 4 / 5); + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -206,13 +206,13 @@ int gww_dora_merge_batch_f32(const gww_dora_merge_item* items, int n, void* stre
  * -------------------------------------------------------------------------- */
 typedef struct {
   int layer;            /* encoder layer index */
-  int proj;             /* 0 q_proj, 1 k_proj, 2 v_proj, 3 out_proj */
-  int r;                /* LoRA rank (8) */
+  int proj;             /* 0 q_proj, 1 k_proj, 2 v_proj, 3 out_proj, 4 fc1 [ffn, d], 5 fc2 [d, ffn] */
+  int r;                /* LoRA rank, 1..64 */
   float scaling;        /* lora_alpha / r */
-  const float* A;       /* [r, d]   lora_A.weight */
-  const float* B;       /* [d, r]   lora_B.weight */
-  const float* mag;     /* [d]      lora_magnitude_vector */
-  const float* nrm;     /* [d]      ||W0 + s B A|| rows (norm_out of gww_dora_merge_f32) */
+  const float* A;       /* [r, d_in]   lora_A.weight */
+  const float* B;       /* [d_out, r]  lora_B.weight */
+  const float* mag;     /* [d_out]     lora_magnitude_vector */
+  const float* nrm;     /* [d_out]     ||W0 + s B A|| rows (norm_out of gww_dora_merge_f32) */
   float* dA;            /* gradients, ACCUMULATED into: zero them once per step */
   float* dB;
   float* dm;
@@ -220,6 +220,10 @@ typedef struct {
 
 size_t gww_train_saved_bytes(const gww_encoder* enc, int batch);
 size_t gww_train_workspace_bytes(const gww_encoder* enc, int batch);
+/* Workspace of a step with fc1 / fc2 targets or ranks other than 8 (at most max_r): gww_train_workspace_bytes plus the
+ * adapter-gradient scratch (gww_adapter_grads_scratch_bytes of the largest target shape).  With a smaller workspace the
+ * backward allocates that scratch stream-ordered on every such target. */
+size_t gww_train_workspace_bytes_adapters(const gww_encoder* enc, int batch, int max_r);
 int gww_encoder_train_forward(gww_encoder* enc, const float* mel, int batch, void* workspace,
                               size_t workspace_bytes, void* saved, size_t saved_bytes,
                               float* last_hidden, int pooled, void* stream);
@@ -474,8 +478,8 @@ int gww_layernorm_bwd(const float* x, const float* gamma, const void* dy, int dy
 int gww_gelu_bf16(const void* z, const void* dgelu_or_null, void* out, long n, void* stream);
 /* DoRA parameter gradients of one [d,d] projection (see train_ops.hip): X [M,d] with row stride ldx, dY / Y
  * [M,d] sections with row stride ldy (e.g. one of the q / k / v column blocks of the packed [M,3d] qkv / dqkv),
- * bias_st in stored units, yscale = dy_true / dy_stored.  d in {128, 384, 512, 768, 1024, 1280}, r = 8;
- * gradients are accumulated. */
+ * bias_st in stored units, yscale = dy_true / dy_stored.  d in {128, 384, 512, 768, 1024, 1280}, r = 8 (other ranks
+ * 1..64 go to gww_adapter_grads' kernel, its scratch allocated stream-ordered); gradients are accumulated. */
 int gww_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
                    float yscale, float scaling, const float* A, const float* B, const float* mag,
                    const float* nrm, float* dA, float* dB, float* dm, long M, int d, int r, void* stream);
@@ -483,6 +487,17 @@ int gww_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long 
  * Signal_vs_Noise/src/train.py:230-237) -- in one pass on the matrix cores (dora_grads.hip); d in {384, 512}, r = 8.
  * Projection p reads dY / Y at column col_off[p] of rows with stride ldy; all arrays have np entries (host memory,
  * device pointers inside).  Gradients are accumulated. */
+/* Adapter gradients of one adapted linear layer of any shape the encoder has -- [d, d], fc1 [4d, d], fc2 [d, 4d] -- and
+ * rank 1..64 (dora_grads.hip, on the matrix cores): X [M, d_in] (row stride ldx), dY / Y [M, d_out] (row stride ldy),
+ * bias_st [d_out], A [r, d_in], B [d_out, r], mag / nrm [d_out]; otherwise the contract of gww_dora_grads (plain LoRA:
+ * mag = nrm = 1).  d_in, d_out multiples of 128; r > 64 is an error.  Partial sums go through per-workgroup slabs
+ * summed in a fixed order: two identical calls give identical bits.  scratch (optional):
+ * gww_adapter_grads_scratch_bytes(M, d_in, d_out, r) bytes of device memory, else it is allocated stream-ordered. */
+size_t gww_adapter_grads_scratch_bytes(long M, int d_in, int d_out, int r);
+int gww_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                      float yscale, float scaling, const float* A, const float* B, const float* mag, const float* nrm,
+                      float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r, void* scratch,
+                      size_t scratch_bytes, void* stream);
 int gww_dora_grads_multi(const void* X, long ldx, const void* dY, const void* Y, long ldy, int np,
                          const long* col_off, const float* const* bias_st, const float* yscale,
                          const float* scaling, const float* const* A, const float* const* B,
