@@ -2,7 +2,7 @@
 """Headline benchmark (BASELINE.json): 1 s-strain segments/s through the whisper-tiny
 encoder forward at batch 256 x (80 x 3000) log-mel, bf16 MFMA, on N MI355X GPUs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over one batch: [256, 80, 3000] fp32 log-mel
@@ -12,12 +12,17 @@ final LayerNorm -> last_hidden_state [256, 1500, 384] fp32 AND the pooled last t
 Data-parallel: every rank runs its own batch (weak scaling), no collective on the
 inference path.
 
-Rank 0 prints ONE JSON line with the contract fields plus
-  roofline     : the dominant kernel (by time) against the gfx950 bf16 dense MFMA peak,
-                 its duration measured live with HIP events on the launch stream
-  cpu_baseline : oracle/encoder_torch.py -- the torch-CPU restatement of the encoder (a port, not the
-                 reference, which cannot travel to the GPU box), pinned by the HF goldens -- timed on
-                 this box's host cores on a bounded sample of the same workload
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints ONE
+JSON line (rank 0) with the contract fields.  --full measures everything else as well
+and adds it to the line:
+  frontend, frontend_qscan, q_adapter : the log-mel and Q-transform front ends on their own
+  kernels, roofline : per-kernel durations of a separate traced pass of the K steps; the
+                 dominant kernel (by time) against the gfx950 bf16 dense MFMA peak
+  pooled_classify, dora_step, extra : the last-token forward, the DoRA training step, the
+                 whisper-base / -small / fp32 forwards and BASELINE configs 3-5
+  cpu_baseline : oracle/encoder_torch.py -- the torch-CPU restatement of the encoder (a port,
+                 not the reference), pinned by the HF goldens -- timed on the host cores on a
+                 bounded sample of the same workload
 """
 
 from __future__ import annotations
@@ -309,114 +314,11 @@ def config5_composed(dev, rank, enc_names=("tiny", "small"), n_batches=4):
     return out
 
 
-def cpu_baseline(enc_name, budget_s=20.0):
-    """The encoder forward on the host cores: the torch-CPU restatement of the HF arithmetic (oracle/encoder_torch.py, a
-    port pinned by the HF goldens, not the reference itself -- the reference tree does not travel to the GPU box), fp32,
-    all the threads torch uses here (stated), on a bounded sample of the same workload sized to ~budget_s seconds."""
-    import torch as T
-    from gw_whisper_amd import synth
-    from oracle import encoder as oenc
-    from oracle import encoder_torch as oet
-    from oracle import logmel as olm
-    sd = synth.named_encoder_state_dict(enc_name, seed=0)
-    cfg = oenc.EncCfg.named(enc_name)
-    threads = T.get_num_threads()
-    chunk = 4
-    mel = olm.log_mel(synth.strain_segments(chunk, seed=0))
-    oet.encoder_forward(sd, mel, cfg, chunk=chunk)                # warm the thread pool / oneDNN primitives
-    t0 = time.perf_counter()
-    oet.encoder_forward(sd, mel, cfg, chunk=chunk)
-    probe = (time.perf_counter() - t0) / chunk
-    n_seg = int(min(256, max(chunk, round(budget_s / probe / chunk) * chunk)))
-    mel = olm.log_mel(synth.strain_segments(n_seg, seed=0))
-    t0 = time.perf_counter()
-    oet.encoder_forward(sd, mel, cfg, chunk=chunk)
-    dt = time.perf_counter() - t0
-    return {"value": n_seg / dt, "unit": "segments/s", "cores": int(threads), "kind": "port",
-            "sample": f"{n_seg} segments x [80,3000] log-mel, whisper-{enc_name} encoder fwd, torch-CPU fp32 restatement "
-                      f"(oracle/encoder_torch.py: oneDNN conv, threaded GEMMs, CPU SDPA), {threads} threads of "
-                      f"{os.cpu_count()} host CPUs, {dt:.1f} s wall"}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--encoder", default="tiny")
-    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-breakdown", action="store_true", help="skip the per-kernel event trace")
-    ap.add_argument("--split", type=int, default=0, help="0 (default): one stream; 1: two half batches on two HIP streams "
-                    "(paid off before the fused MLP kernel, which owns a whole CU; now within noise)")
-    ap.add_argument("--no-train", action="store_true", help="skip the DoRA step timing")
-    ap.add_argument("--no-pooled", action="store_true", help="skip the pooled (last-token-only) forward timing")
-    ap.add_argument("--train-batch", type=int, default=32, help="per-GPU batch of the DoRA step (reference default 32)")
-    ap.add_argument("--isolated", action="store_true", help="also time each kernel class in isolation")
-    ap.add_argument("--no-extra", action="store_true", help="skip the whisper-base forward / whisper-small DoRA step extras")
-    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned on rank 0 "
-                    "as DIR/<name>.npy: last_token whole, last_hidden_state as a fixed, seeded sample of rows (64 MB at most)")
-    args = ap.parse_args()
-    if args.steps < 1:
-        ap.error("--steps must be at least 1")
-    from gw_whisper_amd import synth as _synth   # numpy only: nothing has touched the GPU yet
-    if args.dump_outputs and args.batch * _synth.ENCODER_SIZES[args.encoder][0] * 4 > DUMP_BUDGET // 2:
-        ap.error(f"--dump-outputs: last_token of batch {args.batch} exceeds {DUMP_BUDGET // 2 >> 20} MB")
-
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
-        # plain `python bench.py --gpus N`: become the launcher of N child ranks (nothing here has touched the GPU yet)
-        sys.exit(self_launch(sys.argv[1:], args.gpus))
-    args.gpus = world
-    assert torch.cuda.is_available(), "bench.py needs an MI355X"
-    torch.cuda.set_device(local)
-    dev = torch.device("cuda", local)
-    import torch.distributed as dist
-
-    class _stdout_to_stderr:
-        """RCCL prints its version banner on the process's stdout (fd 1) when a communicator comes up; the driver parses
-        stdout as ONE JSON line, so fd 1 points at stderr while the group is created."""
-        def __enter__(self):
-            sys.stdout.flush()
-            self.saved = os.dup(1)
-            os.dup2(2, 1)
-        def __exit__(self, *exc):
-            sys.stdout.flush()
-            os.dup2(self.saved, 1)
-            os.close(self.saved)
-
-    def _bring_up(**kw):
-        with _stdout_to_stderr():
-            dist.init_process_group("nccl", device_id=dev, **kw)
-            t = torch.zeros(1, device=dev)
-            dist.all_reduce(t)          # the communicator itself is created by the first collective
-            torch.cuda.synchronize()
-    if world > 1:
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        _bring_up()
-    elif not args.no_train and args.precision == "bf16":
-        # N = 1: a world-size-1 RCCL group, so that the DoRA step below goes through dist.init's path and
-        # FlatGradBucket.all_reduce_mean issues a real ncclAllReduce on the 6.1 MB (tiny) / 10.8 MB (small) bucket --
-        # `dora_step.split_ms.allreduce` is then a measured collective, not a skipped branch
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        os.environ.setdefault("MASTER_PORT", str(free_port()))
-        _bring_up(rank=0, world_size=1)
-
+def frontend_figures(wave, mel, B, rank, dev):
+    """--full: the two front ends on their own -- the log-mel call (eager and replayed from a hipGraph; `mel` is what
+    the eager call returned on `wave`), the Q-scan, the whole Q-transform adapter in both of its variants and its tail
+    kernel -- as the result line's `frontend`, `frontend_qscan` and `q_adapter` entries."""
     from gw_whisper_amd import ops, synth
-    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
-
-    d, L, H, ffn = synth.ENCODER_SIZES[args.encoder]
-    B = args.batch
-    sd = synth.named_encoder_state_dict(args.encoder, seed=0)
-    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig.named(args.encoder), precision=args.precision).to(dev)
-    if args.split:
-        enc.set_split(True)
-    # synthetic whitened-like 1 s strain -> HIP log-mel front end; features stay resident in HBM
-    wave = torch.from_numpy(synth.strain_segments(B, seed=1000 + rank)).to(dev)
-    mel = ops.logmel(wave)
     fe_call_ms = time_kernel(lambda: ops.logmel(wave), iters=10, warm=2)     # what a caller of ops.logmel pays (host incl.)
     # ... and the device time of the same call (memset + k_logmel_frames_mfma + k_logmel_finalize) replayed from a
     # hipGraph, so that the host-side cost of the Python call does not pace the GPU
@@ -460,6 +362,145 @@ def main():
         del feat, ycnn, xw
     del strain2k
     torch.cuda.empty_cache()
+    return {
+        "frontend": {"kernel": "logmel (memset + k_logmel_frames_mfma + k_logmel_finalize)",
+                     "ms_per_batch": fe_ms, "ms_per_call_incl_host": fe_call_ms,
+                     "what": "ms_per_batch = device time of one ops.logmel call replayed from a hipGraph; "
+                             "ms_per_call_incl_host = the eager Python call (allocation of the 245 MB output, ctypes, "
+                             "three enqueues), host-paced",
+                     "segments_per_s": B / (fe_ms or fe_call_ms) * 1e3,
+                     "algorithmic_gbs": B * (64000 + 960000) / (fe_ms or fe_call_ms) / 1e6,
+                     "bound": "two kernels with different roofs: k_logmel_frames_mfma is fp32-MFMA-bound by the dense-DFT "
+                              "form (about 110 us of the call), only k_logmel_finalize (about 39 us for the 245 MB output) "
+                              "is HBM-bound -- per-kernel durations in profiles/*_kernel_stats.md; no single HBM fraction "
+                              "is quoted for the pair"},
+        "frontend_qscan": {"kernel": "rDFT GEMM + k_qscan_tiles + k_qscan_interp (parity unpinned, DESIGN.md section 2)",
+                           "ms_per_batch": q_ms, "windows_per_s": 2 * B / q_ms * 1e3,
+                           "config": f"{2 * B} x 2048 samples, qrange [4, 128], 148 tiles rows, 128 x 128 output"},
+        "q_adapter": {"what": f"QTransformAdapter forward on {B} two-detector windows -> [B, 2, 80, 3000] (Q-scan + the CNN's "
+                              "three HIP launches, csrc/qadapter_cnn.hip + gww_qadapter_tail_f32; no library call)", "ms_per_batch": adapter_ms,
+                      "tail_kernel_ms_per_detector": tail_ms,
+                      "tail_kernel_algorithmic_gbs": B * (80 * 3000 + 32 * 32) * 4 / tail_ms / 1e6,
+                      "tail_kernel_frac_of_hbm_peak": B * (80 * 3000 + 32 * 32) * 4 / tail_ms / 1e6 / HBM_PEAK_GBS}
+    }
+
+
+def cpu_baseline(enc_name, budget_s=20.0):
+    """The encoder forward on the host cores: the torch-CPU restatement of the HF arithmetic (oracle/encoder_torch.py, a
+    port pinned by the HF goldens, not the reference itself -- the reference tree does not travel to the GPU box), fp32,
+    all the threads torch uses here (stated), on a bounded sample of the same workload sized to ~budget_s seconds."""
+    import torch as T
+    from gw_whisper_amd import synth
+    from oracle import encoder as oenc
+    from oracle import encoder_torch as oet
+    from oracle import logmel as olm
+    sd = synth.named_encoder_state_dict(enc_name, seed=0)
+    cfg = oenc.EncCfg.named(enc_name)
+    threads = T.get_num_threads()
+    chunk = 4
+    mel = olm.log_mel(synth.strain_segments(chunk, seed=0))
+    oet.encoder_forward(sd, mel, cfg, chunk=chunk)                # warm the thread pool / oneDNN primitives
+    t0 = time.perf_counter()
+    oet.encoder_forward(sd, mel, cfg, chunk=chunk)
+    probe = (time.perf_counter() - t0) / chunk
+    n_seg = int(min(256, max(chunk, round(budget_s / probe / chunk) * chunk)))
+    mel = olm.log_mel(synth.strain_segments(n_seg, seed=0))
+    t0 = time.perf_counter()
+    oet.encoder_forward(sd, mel, cfg, chunk=chunk)
+    dt = time.perf_counter() - t0
+    return {"value": n_seg / dt, "unit": "segments/s", "cores": int(threads), "kind": "port",
+            "sample": f"{n_seg} segments x [80,3000] log-mel, whisper-{enc_name} encoder fwd, torch-CPU fp32 restatement "
+                      f"(oracle/encoder_torch.py: oneDNN conv, threaded GEMMs, CPU SDPA), {threads} threads of "
+                      f"{os.cpu_count()} host CPUs, {dt:.1f} s wall"}
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--encoder", default="tiny")
+    ap.add_argument("--precision", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true", help="also measure everything beside the headline: front ends, per-kernel "
+                    "trace and roofline, pooled forward, DoRA step, the other encoders and configs, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-breakdown", action="store_true", help="--full: skip the per-kernel event trace")
+    ap.add_argument("--split", type=int, default=0, help="0 (default): one stream; 1: two half batches on two HIP streams "
+                    "(paid off before the fused MLP kernel, which owns a whole CU; now within noise)")
+    ap.add_argument("--no-train", action="store_true", help="--full: skip the DoRA step timing")
+    ap.add_argument("--no-pooled", action="store_true", help="--full: skip the pooled (last-token-only) forward timing")
+    ap.add_argument("--train-batch", type=int, default=32, help="per-GPU batch of the DoRA step (reference default 32)")
+    ap.add_argument("--isolated", action="store_true", help="also time each kernel class in isolation")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the whisper-base forward / whisper-small DoRA "
+                    "step extras")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned on rank 0 "
+                    "as DIR/<name>.npy: last_token whole, last_hidden_state as a fixed, seeded sample of rows (64 MB at most)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    from gw_whisper_amd import synth as _synth   # numpy only: nothing has touched the GPU yet
+    if args.dump_outputs and args.batch * _synth.ENCODER_SIZES[args.encoder][0] * 4 > DUMP_BUDGET // 2:
+        ap.error(f"--dump-outputs: last_token of batch {args.batch} exceeds {DUMP_BUDGET // 2 >> 20} MB")
+    return args
+
+
+def main():
+    args = parse_args()
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    if "WORLD_SIZE" not in os.environ and args.gpus > 1:
+        # plain `python bench.py --gpus N`: become the launcher of N child ranks (nothing here has touched the GPU yet)
+        sys.exit(self_launch(sys.argv[1:], args.gpus))
+    args.gpus = world
+    assert torch.cuda.is_available(), "bench.py needs an MI355X"
+    torch.cuda.set_device(local)
+    dev = torch.device("cuda", local)
+    import torch.distributed as dist
+
+    class _stdout_to_stderr:
+        """RCCL prints its version banner on the process's stdout (fd 1) when a communicator comes up; the driver parses
+        stdout as ONE JSON line, so fd 1 points at stderr while the group is created."""
+        def __enter__(self):
+            sys.stdout.flush()
+            self.saved = os.dup(1)
+            os.dup2(2, 1)
+        def __exit__(self, *exc):
+            sys.stdout.flush()
+            os.dup2(self.saved, 1)
+            os.close(self.saved)
+
+    def _bring_up(**kw):
+        with _stdout_to_stderr():
+            dist.init_process_group("nccl", device_id=dev, **kw)
+            t = torch.zeros(1, device=dev)
+            dist.all_reduce(t)          # the communicator itself is created by the first collective
+            torch.cuda.synchronize()
+    if world > 1:
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        _bring_up()
+    elif args.full and not args.no_train and args.precision == "bf16":
+        # N = 1: a world-size-1 RCCL group, so that the DoRA step below goes through dist.init's path and
+        # FlatGradBucket.all_reduce_mean issues a real ncclAllReduce on the 6.1 MB (tiny) / 10.8 MB (small) bucket --
+        # `dora_step.split_ms.allreduce` is then a measured collective, not a skipped branch
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        os.environ.setdefault("MASTER_PORT", str(free_port()))
+        _bring_up(rank=0, world_size=1)
+
+    from gw_whisper_amd import ops, synth
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+
+    d, L, H, ffn = synth.ENCODER_SIZES[args.encoder]
+    B = args.batch
+    sd = synth.named_encoder_state_dict(args.encoder, seed=0)
+    enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig.named(args.encoder), precision=args.precision).to(dev)
+    if args.split:
+        enc.set_split(True)
+    # synthetic whitened-like 1 s strain -> HIP log-mel front end; features stay resident in HBM
+    wave = torch.from_numpy(synth.strain_segments(B, seed=1000 + rank)).to(dev)
+    mel = ops.logmel(wave)
+    front = frontend_figures(wave, mel, B, rank, dev) if args.full else {}
 
     def step():
         return enc.forward_raw(mel, want_hidden=True, want_last=True)
@@ -469,7 +510,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    trace = not args.no_breakdown
+    trace = args.full and not args.no_breakdown
     with torch.no_grad():
         for _ in range(args.warmup):
             step()
@@ -502,7 +543,7 @@ def main():
     # want_hidden=False the last layer runs on the B pooled rows above its attention.  Reported beside the full
     # forward, which stays the headline metric.
     pooled_ms = None
-    if not args.no_pooled:
+    if args.full and not args.no_pooled:
         with torch.no_grad():
             pooled_ms = time_kernel(lambda: enc.forward_raw(mel, want_hidden=False, want_last=True), iters=5, warm=2)
     if world > 1:
@@ -513,7 +554,7 @@ def main():
     value = world * B * args.steps / dt
 
     train = None
-    if not args.no_train and args.precision == "bf16":
+    if args.full and not args.no_train and args.precision == "bf16":
         del out
         enc._ws = None
         torch.cuda.empty_cache()
@@ -523,7 +564,7 @@ def main():
     # (q, k, v targets, per-GPU batch 32 x 2 detectors, gradients all-reduced over RCCL when world > 1) and the
     # whisper-base forward at B = 64
     extra = None
-    if not args.no_extra and args.precision == "bf16" and args.encoder == "tiny":
+    if args.full and not args.no_extra and args.precision == "bf16" and args.encoder == "tiny":
         torch.cuda.empty_cache()
         extra = {}
         db, Lb, Hb, fb = synth.ENCODER_SIZES["base"]
@@ -578,7 +619,7 @@ def main():
             "metric": "1s-strain segments/sec (encoder fwd)",
             "value": value, "unit": "segments/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic",
+            "dtype": "bf16" if args.precision == "bf16" else "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"whisper-{args.encoder} encoder fwd, batch {B} log-mel (80x3000) per GPU, "
                                    f"1500 tokens, random-init weights"
                                    + (" (BASELINE configs[1])" if (args.encoder, B) == ("tiny", 256) else ""),
@@ -586,33 +627,18 @@ def main():
                        "streams_per_gpu": 2 if args.split else 1},
             "forward": {"algorithmic_gflop_per_segment": fl["total"] / 1e9, "achieved_tflops_per_gpu": fwd_tflops,
                         "frac_of_bf16_mfma_peak": fwd_tflops / MFMA_BF16_PEAK_TFLOPS},
-            "frontend": {"kernel": "logmel (memset + k_logmel_frames_mfma + k_logmel_finalize)",
-                         "ms_per_batch": fe_ms, "ms_per_call_incl_host": fe_call_ms,
-                         "what": "ms_per_batch = device time of one ops.logmel call replayed from a hipGraph; "
-                                 "ms_per_call_incl_host = the eager Python call (allocation of the 245 MB output, ctypes, "
-                                 "three enqueues), host-paced",
-                         "segments_per_s": B / (fe_ms or fe_call_ms) * 1e3,
-                         "algorithmic_gbs": B * (64000 + 960000) / (fe_ms or fe_call_ms) / 1e6,
-                         "bound": "two kernels with different roofs: k_logmel_frames_mfma is fp32-MFMA-bound by the dense-DFT "
-                                  "form (about 110 us of the call), only k_logmel_finalize (about 39 us for the 245 MB output) "
-                                  "is HBM-bound -- per-kernel durations in profiles/*_kernel_stats.md; no single HBM fraction "
-                                  "is quoted for the pair"},
-            "frontend_qscan": {"kernel": "rDFT GEMM + k_qscan_tiles + k_qscan_interp (parity unpinned, DESIGN.md section 2)",
-                               "ms_per_batch": q_ms, "windows_per_s": 2 * B / q_ms * 1e3,
-                               "config": f"{2 * B} x 2048 samples, qrange [4, 128], 148 tiles rows, 128 x 128 output"},
-            "q_adapter": {"what": f"QTransformAdapter forward on {B} two-detector windows -> [B, 2, 80, 3000] (Q-scan + the CNN's "
-                                  "three HIP launches, csrc/qadapter_cnn.hip + gww_qadapter_tail_f32; no library call)", "ms_per_batch": adapter_ms,
-                          "tail_kernel_ms_per_detector": tail_ms,
-                          "tail_kernel_algorithmic_gbs": B * (80 * 3000 + 32 * 32) * 4 / tail_ms / 1e6,
-                          "tail_kernel_frac_of_hbm_peak": B * (80 * 3000 + 32 * 32) * 4 / tail_ms / 1e6 / HBM_PEAK_GBS},
-            "pooled_classify": {"what": "encoder.last_token(): same encoder, only last_hidden_state[:, -1] produced "
-                                        "(last layer: one query tile of attention, row-wise ops on B rows)",
-                                "ms_per_batch": pooled_ms, "segments_per_s_per_gpu": B / pooled_ms * 1e3}
-            if pooled_ms else None,
-            "dora_step_ms": train["ms"] if train else None,
-            "dora_step": train,
-            "extra": extra,
         }
+        if args.full:
+            line.update(front)
+            line.update({
+                "pooled_classify": {"what": "encoder.last_token(): same encoder, only last_hidden_state[:, -1] produced "
+                                            "(last layer: one query tile of attention, row-wise ops on B rows)",
+                                    "ms_per_batch": pooled_ms, "segments_per_s_per_gpu": B / pooled_ms * 1e3}
+                if pooled_ms else None,
+                "dora_step_ms": train["ms"] if train else None,
+                "dora_step": train,
+                "extra": extra,
+            })
         if traced:
             M = B * T_TOK
             es = 2 if args.precision == "bf16" else 4
@@ -691,7 +717,7 @@ def main():
                                     "launches_per_step": dom["launches_per_step"]}
         if args.isolated and args.precision == "bf16":
             line["kernels_isolated"] = kernel_breakdown(args.encoder, B, dev)
-        if not args.no_cpu_baseline and world == 1:     # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:     # reported at N = 1 only (rank 0's host cores)
             line["cpu_baseline"] = cpu_baseline(args.encoder)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():

@@ -100,3 +100,11 @@ def test_steps_below_one_are_refused(monkeypatch):
         raise AssertionError("main() returned")
     except SystemExit as e:
         assert e.code == 2
+
+
+def test_a_plain_run_leaves_the_other_figures_to_full():
+    """`bench.py --gpus 1 --steps N --warmup W` measures the headline only; --full (off by default) adds the rest."""
+    b = _bench()
+    plain = b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert plain.full is False and (plain.steps, plain.warmup) == (5, 2)
+    assert b.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2", "--full"]).full is True
