@@ -96,6 +96,22 @@ SIGNATURES = {
     "gww_encoder_train_backward_full": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                   C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
                                                   C.c_int, C.POINTER(EncGrads), C.c_void_p]),
+    "gww_train_saved_bytes_f32": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "gww_train_workspace_bytes_f32": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "gww_encoder_train_forward_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]),
+    "gww_encoder_train_backward_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.POINTER(DoraTarget), C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_void_p]),
+    "gww_attention_lse_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gww_attention_bwd_f32_scratch_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gww_attention_bwd_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gww_adapter_grads_f32_scratch_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int, C.c_int]),
+    "gww_adapter_grads_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_float,
+                                        C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_size_t, C.c_void_p]),
     "gww_gemm_wgrad_workspace_bytes": (C.c_size_t, [C.c_long, C.c_int, C.c_int]),
     "gww_gemm_wgrad_bf16": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

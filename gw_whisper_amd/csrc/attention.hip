@@ -1694,6 +1694,127 @@ __global__ __launch_bounds__(256) void k_attention_f32(const float* __restrict__
   }
 }
 
+// The same kernel that also stores the row log-sum-exp lse [B, H, T] (natural log: the training backward's input) and
+// takes the query tiles from qt0 on (n_qt = q_tiles - qt0 per (b, h): the pooled last layer needs only the tile that holds
+// row T - 1).  Kept a separate kernel so that the inference kernel above stays as it is; ctx is computed by the same
+// operations in the same order, so it is bit-identical to k_attention_f32's.
+__global__ __launch_bounds__(256) void k_attention_lse_f32(const float* __restrict__ qkv, float* __restrict__ ctx,
+                                                           float* __restrict__ lse, int T, int H, int n_qt, int qt0) {
+  __shared__ float Ks[FKB][FLDS];
+  __shared__ float Vs[FKB][FLDS];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qt = blockIdx.x % n_qt + qt0;
+  const int bh = blockIdx.x / n_qt;
+  const int b = bh / H, h = bh - b * H;
+  const int d = H * DH;
+  const long row_stride = 3L * d;
+  const float* base = qkv + (long)b * T * row_stride;
+  const float* qp = base + h * DH;
+  const float* kp = base + d + h * DH;
+  const float* vp = base + 2 * d + h * DH;
+  const int r = lane & 31, hh = lane >> 5;
+  const int q_row = qt * QB + wave * 32 + r;
+  const int q_ld = q_row < T ? q_row : T - 1;
+
+  float qf[32];   // Q[q = r][dh = 2 s + hh]
+#pragma unroll
+  for (int s = 0; s < 32; ++s) qf[s] = qp[(long)q_ld * row_stride + 2 * s + hh];
+
+  f32x16 ot[2];
+#pragma unroll
+  for (int n = 0; n < 2; ++n)
+#pragma unroll
+    for (int j = 0; j < 16; ++j) ot[n][j] = 0.f;
+  float m_run = -INFINITY, l_run = 0.f;
+
+  const int n_kt = (T + FKB - 1) / FKB;
+  for (int kt = 0; kt < n_kt; ++kt) {
+    // stage 32 keys x 64 dh of K and V (fp32): 2048 floats each, 8 per thread
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = tid + 256 * i, row = c >> 4, col = (c & 15) * 4;
+      int key = kt * FKB + row;
+      if (key >= T) key = T - 1;
+      const float4 kv = *reinterpret_cast<const float4*>(kp + (long)key * row_stride + col);
+      const float4 vv = *reinterpret_cast<const float4*>(vp + (long)key * row_stride + col);
+      Ks[row][col] = kv.x; Ks[row][col + 1] = kv.y; Ks[row][col + 2] = kv.z; Ks[row][col + 3] = kv.w;
+      Vs[row][col] = vv.x; Vs[row][col + 1] = vv.y; Vs[row][col + 2] = vv.z; Vs[row][col + 3] = vv.w;
+    }
+    __syncthreads();
+    f32x16 st;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) st[j] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 32; ++s)
+      st = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[r][2 * s + hh], qf[s], st, 0, 0, 0);
+    if (kt == n_kt - 1 && (T % FKB) != 0) {
+#pragma unroll
+      for (int j = 0; j < 16; ++j) {
+        const int key = kt * FKB + (j & 3) + 8 * (j >> 2) + 4 * hh;
+        if (key >= T) st[j] = -INFINITY;
+      }
+    }
+    float tmax = st[0];
+#pragma unroll
+    for (int j = 1; j < 16; ++j) tmax = fmaxf(tmax, st[j]);
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_run, tmax);
+    const float alpha = expf(m_run - m_new);
+    float psum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      st[j] = expf(st[j] - m_new);
+      psum += st[j];
+    }
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int j = 0; j < 16; ++j) ot[n][j] *= alpha;
+    // O^T[dh][q] += V^T[dh][key] P^T[key][q]; MFMA step rho pairs k=0 <-> key_a(rho), k=1 <-> key_a(rho)+4
+#pragma unroll
+    for (int rho = 0; rho < 16; ++rho) {
+      const int key = (rho & 3) + 8 * (rho >> 2) + 4 * hh;
+#pragma unroll
+      for (int n = 0; n < 2; ++n)
+        ot[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(Vs[key][32 * n + r], st[rho], ot[n], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+  const float l_tot = l_run + __shfl_xor(l_run, 32, 64);
+  const float inv = 1.0f / l_tot;
+  if (q_row < T && hh == 0) lse[(long)bh * T + q_row] = m_run + logf(l_tot);
+  if (q_row < T) {
+    float* orow = ctx + ((long)b * T + q_row) * d + h * DH;
+#pragma unroll
+    for (int n = 0; n < 2; ++n)
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const int dh = 32 * n + 8 * c + 4 * hh;
+        *reinterpret_cast<float4*>(orow + dh) = make_float4(ot[n][4 * c] * inv, ot[n][4 * c + 1] * inv,
+                                                            ot[n][4 * c + 2] * inv, ot[n][4 * c + 3] * inv);
+      }
+  }
+}
+
+// fp32 forward + lse (training); last_tile_only: only the query tile that holds row T - 1 (the other rows of ctx / lse
+// are not written)
+int launch_attention_lse_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, bool last_tile_only,
+                             hipStream_t s) {
+  GWW_REQUIRE(qkv && ctx && lse, "attention_lse_f32: NULL operand");
+  GWW_REQUIRE(B >= 0 && T > 0 && H > 0, "attention_lse_f32: bad shape B=%d T=%d H=%d", B, T, H);
+  GWW_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)ctx) & 15) == 0, "attention_lse_f32: 16-byte alignment");
+  if (B == 0) return GWW_OK;
+  const int q_tiles = (T + QB - 1) / QB;
+  const int qt0 = last_tile_only ? q_tiles - 1 : 0;
+  const long blocks = (long)(q_tiles - qt0) * B * H;
+  GWW_REQUIRE(blocks < 2147483647L, "attention_lse_f32: grid too large");
+  hipLaunchKernelGGL(k_attention_lse_f32, dim3((unsigned)blocks), dim3(256), 0, s, qkv, ctx, lse, T, H, q_tiles - qt0, qt0);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
 int launch_attention_f32(const float* qkv, float* ctx, int B, int T, int H, hipStream_t s) {
   GWW_REQUIRE(qkv && ctx, "attention_f32: NULL operand");
   GWW_REQUIRE(B >= 0 && T > 0 && H > 0, "attention_f32: bad shape B=%d T=%d H=%d", B, T, H);
@@ -1736,4 +1857,7 @@ extern "C" int gww_attention_log2q_bf16(const void* qkv, void* ctx, float* lse_o
 }
 extern "C" int gww_attention_f32(const float* qkv, float* ctx, int B, int T, int n_heads, void* stream) {
   return launch_attention_f32(qkv, ctx, B, T, n_heads, (hipStream_t)stream);
+}
+extern "C" int gww_attention_lse_f32(const float* qkv, float* ctx, float* lse, int B, int T, int n_heads, void* stream) {
+  return launch_attention_lse_f32(qkv, ctx, lse, B, T, n_heads, false, (hipStream_t)stream);
 }

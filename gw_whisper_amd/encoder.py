@@ -219,7 +219,8 @@ class WhisperEncoder(_Tracked):
         Glitch_classification/src/train_full_finetune.py): afterwards the base parameters that require grad get their
         gradients from the HIP base-weight backward (gww_encoder_train_backward_full); the others stay frozen.  Without
         this call an un-frozen base parameter is refused (_wants_grad).  DoRA / LoRA adapters cannot be combined with it
-        -- the reference never mixes them -- and only precision='bf16' has a training step."""
+        -- the reference never mixes them.  Full fine-tuning is bf16-only: precision='fp32' has an adapter training
+        step (training.py) but no fp32 base-weight backward."""
         if self.precision != "bf16":
             raise _lib.GwwError("full fine-tuning is implemented for precision='bf16'")
         if self._has_adapters():

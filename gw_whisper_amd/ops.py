@@ -470,6 +470,34 @@ def attention_bwd(qkv, ctx, dctx, lse, n_heads: int, q_log2: bool = False) -> to
     return dqkv
 
 
+def attention_lse_f32(qkv: torch.Tensor, n_heads: int):
+    """fp32 attention forward that also returns the row log-sum-exp [B, H, T]; ctx is bit-identical to
+    ``gww_attention_f32``'s (``gww_attention_lse_f32``)."""
+    qkv = _dev(qkv, torch.float32, "qkv")
+    B, T, d3 = qkv.shape
+    ctx = torch.empty((B, T, d3 // 3), dtype=torch.float32, device=qkv.device)
+    lse = torch.empty((B, n_heads, T), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        check(lib().gww_attention_lse_f32(qkv.data_ptr(), ctx.data_ptr(), lse.data_ptr(), B, T, n_heads, _stream()),
+              "gww_attention_lse_f32")
+    return ctx, lse
+
+
+def attention_bwd_f32(qkv, ctx, dctx, lse, n_heads: int) -> torch.Tensor:
+    """dqkv [B, T, 3 d] (fp32) of softmax(q k^T) v given dctx, exact fp32 (``gww_attention_bwd_f32``); the q section is
+    the gradient with respect to the stored (pre-scaled) q."""
+    qkv, ctx, dctx, lse = (_dev(t, torch.float32) for t in (qkv, ctx, dctx, lse))
+    B, T, d3 = qkv.shape
+    dqkv = torch.empty_like(qkv)
+    scratch = torch.empty(lib().gww_attention_bwd_f32_scratch_bytes(B, T, n_heads) // 4, dtype=torch.float32,
+                          device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        check(lib().gww_attention_bwd_f32(qkv.data_ptr(), ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(),
+                                          scratch.data_ptr(), dqkv.data_ptr(), B, T, n_heads, _stream()),
+              "gww_attention_bwd_f32")
+    return dqkv
+
+
 def layernorm_bwd(x, gamma, dy, dx=None, want_bf16: bool = False):
     """dx (+)= LayerNorm'(x)^T dy; dy fp32 or bf16.  Returns (dx fp32, dx bf16 | None)."""
     x = _dev(x, torch.float32, "x")
@@ -609,6 +637,33 @@ def adapter_grads(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
                                       float(yscale), float(scaling), f(A), f(B), f(mag), f(nrm), dA.data_ptr(),
                                       dB.data_ptr(), dm.data_ptr(), M, d_in, d_out, r, None, 0, _stream()),
               "gww_adapter_grads")
+    return dA, dB, dm
+
+
+def adapter_grads_f32(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
+    """``adapter_grads`` in exact fp32 (``gww_adapter_grads_f32``): x fp32 [M, d_in]; dy, y fp32 [M, d_out] (rows may
+    be strided, stride(1) == 1, dy and y with the same strides).  Returns fresh (dA, dB, dm).  r > 64 raises GwwError."""
+    if any(t.dtype != torch.float32 or not t.is_cuda for t in (x, dy, y)):
+        raise _lib.GwwError("adapter_grads_f32: x, dy and y must be fp32 GPU tensors")
+    if x.dim() != 2 or dy.dim() != 2 or x.stride(1) != 1 or dy.stride(1) != 1 or dy.stride() != y.stride() \
+            or dy.shape != y.shape or dy.shape[0] != x.shape[0]:
+        raise _lib.GwwError("adapter_grads_f32: 2-D x [M, d_in], dy / y [M, d_out] with contiguous rows; dy and y of "
+                            "the same shape and strides")
+    M, d_in = x.shape
+    d_out = dy.shape[1]
+    r = A.shape[0]
+    if tuple(A.shape) != (r, d_in) or tuple(B.shape) != (d_out, r):
+        raise _lib.GwwError(f"adapter_grads_f32: A {tuple(A.shape)} / B {tuple(B.shape)} do not fit x [{M}, {d_in}] "
+                            f"and dy [{M}, {d_out}]")
+    dA = torch.zeros((r, d_in), dtype=torch.float32, device=x.device)
+    dB = torch.zeros((d_out, r), dtype=torch.float32, device=x.device)
+    dm = torch.zeros((d_out,), dtype=torch.float32, device=x.device)
+    f = lambda t: _dev(t, torch.float32).data_ptr()
+    with torch.cuda.device(x.device):
+        check(lib().gww_adapter_grads_f32(x.data_ptr(), x.stride(0), dy.data_ptr(), y.data_ptr(), dy.stride(0),
+                                          f(bias_st), float(yscale), float(scaling), f(A), f(B), f(mag), f(nrm),
+                                          dA.data_ptr(), dB.data_ptr(), dm.data_ptr(), M, d_in, d_out, r, None, 0,
+                                          _stream()), "gww_adapter_grads_f32")
     return dA, dB, dm
 
 

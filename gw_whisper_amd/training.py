@@ -11,6 +11,9 @@ DoRA-wrapped linear layer (q / k / v / out_proj, fc1 / fc2) to autograd, so the 
 works with the MLP head, the loss and AdamW in plain torch on the GPU and everything inside the
 encoder in libgww.  The DoRA weight norm is detached exactly like peft 0.12.0 ``dora.py``.
 
+An encoder built with ``precision="fp32"`` runs the exact-fp32 twin of the step (``gww_encoder_train_forward_f32`` /
+``_backward_f32``): the reference's own training arithmetic, with no autocast anywhere.
+
 With ``WhisperEncoder.enable_full_finetune()`` the base parameters that require grad are inputs of the same autograd
 node, and the backward is ``gww_encoder_train_backward_full`` with their fp32 gradient buffers.
 """
@@ -84,24 +87,28 @@ class _EncoderTrain(torch.autograd.Function):
             enc._sync_weights()
             _encoder._note_training(enc)   # from now on the packed weights follow every optimizer step at once
             h = enc._ensure_handle()
+            f32 = enc.precision == "fp32"   # the exact-fp32 step (gww_encoder_train_forward_f32): its own arena sizes
             full = bool(base_targets(enc))
             # fc1 / fc2 targets or ranks other than 8 run on the adapter-gradient kernel, whose scratch the attention-only
             # rank-8 step does not need
             wide = [t for t in dora_targets(enc) if t[1] > 3 or t[2].r != 8]
-            if full:
+            if f32:
+                ws_bytes = lib().gww_train_workspace_bytes_f32(h, B)
+            elif full:
                 ws_bytes = lib().gww_train_workspace_bytes_full(h, B)
             elif wide:
                 ws_bytes = lib().gww_train_workspace_bytes_adapters(h, B, max(t[2].r for t in wide))
             else:
                 ws_bytes = lib().gww_train_workspace_bytes(h, B)
             ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-            saved = torch.empty((lib().gww_train_saved_bytes(h, B),), dtype=torch.uint8, device=dev)
+            saved_bytes = lib().gww_train_saved_bytes_f32(h, B) if f32 else lib().gww_train_saved_bytes(h, B)
+            saved = torch.empty((saved_bytes,), dtype=torch.uint8, device=dev)
             shape = (B, c.d_model) if pooled else (B, c.max_source_positions, c.d_model)
             hidden = torch.empty(shape, dtype=torch.float32, device=dev)
-            check(lib().gww_encoder_train_forward(h, x.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(),
-                                                  saved.numel(), hidden.data_ptr(), int(pooled),
-                                                  torch.cuda.current_stream().cuda_stream),
-                  "gww_encoder_train_forward")
+            fwd = lib().gww_encoder_train_forward_f32 if f32 else lib().gww_encoder_train_forward
+            check(fwd(h, x.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(),
+                      int(pooled), torch.cuda.current_stream().cuda_stream),
+                  "gww_encoder_train_forward" + ("_f32" if f32 else ""))
         ctx.enc, ctx.B, ctx.ws, ctx.saved, ctx.pooled = enc, B, ws, saved, bool(pooled)
         ctx.n_params = len(params)
         ctx.mel_shape = tuple(x.shape)
@@ -164,7 +171,9 @@ class _EncoderTrain(torch.autograd.Function):
                     d_hidden.data_ptr(), arr, len(targets), None, d_mel.data_ptr() if d_mel is not None else None,
                     int(ctx.pooled))
             stream = torch.cuda.current_stream().cuda_stream
-            if base:
+            if enc.precision == "fp32":
+                check(lib().gww_encoder_train_backward_f32(*args, stream), "gww_encoder_train_backward_f32")
+            elif base:
                 check(lib().gww_encoder_train_backward_full(*args, C.byref(gl), stream), "gww_encoder_train_backward_full")
             else:
                 check(lib().gww_encoder_train_backward(*args, stream), "gww_encoder_train_backward")
@@ -182,8 +191,10 @@ def encoder_train_forward(encoder, mel: torch.Tensor, pooled: bool = False) -> t
     reference reads, ``Signal_vs_Noise/src/model.py:25-26``; the last layer's row-wise ops and their backward then run
     on B rows instead of B * 1500) -- with autograd through the DoRA parameters and, when ``mel.requires_grad``,
     through the conv stem to the input features."""
-    if encoder.precision != "bf16":
-        raise _lib.GwwError("the training step is implemented for precision='bf16'")
+    if encoder.precision not in ("bf16", "fp32"):
+        raise _lib.GwwError(f"no training step for precision={encoder.precision!r}")
+    if encoder.precision == "fp32" and base_targets(encoder):   # (enable_full_finetune refuses fp32 already)
+        raise _lib.GwwError("full fine-tuning is implemented for precision='bf16'")
     params = []
     for _, _, mod in dora_targets(encoder):
         params += [mod.lora_A[mod.adapter].weight, mod.lora_B[mod.adapter].weight]

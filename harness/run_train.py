@@ -109,7 +109,7 @@ def main(args):
     # src/dataset.py:12 -- the extractor of the same size: 128 mel bins for large-v3 / large-v3-turbo, 80 otherwise
     n_mels = WhisperFeatureExtractor.from_pretrained(f"openai/whisper-{args.encoder}").feature_size
     assert n_mels == config.num_mel_bins
-    encoder = WhisperEncoder(config, precision="bf16")
+    encoder = WhisperEncoder(config, precision=args.precision)
     if args.encoder_weights:
         if args.encoder_weights.endswith(".safetensors"):
             from safetensors.torch import load_file
@@ -273,4 +273,7 @@ if __name__ == "__main__":
                              "keeps the targets it was saved with")
     parser.add_argument("--synthetic", type=int, default=0, help="use N seeded synthetic segments instead of --data-path")
     parser.add_argument("--encoder-weights", type=str, default=None, help="HF WhisperEncoder state_dict (.pth / .safetensors)")
+    parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
+                        help="encoder arithmetic: bf16 (default) or exact fp32, the reference's own training arithmetic "
+                             "(DoRA / LoRA only: full fine-tuning is bf16)")
     main(parser.parse_args())

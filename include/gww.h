@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_adapter_grads / _scratch_bytes, gww_train_workspace_bytes_adapters (adapter gradients of fc1 / fc2 and of ranks 1..64; gww_dora_target.proj 4 / 5); + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_encoder_train_forward_f32 / _backward_f32, gww_train_saved_bytes_f32 / gww_train_workspace_bytes_f32, gww_attention_lse_f32, gww_attention_bwd_f32 / _scratch_bytes, gww_adapter_grads_f32 / _scratch_bytes (exact-fp32 DoRA / LoRA training step); + gww_adapter_grads / _scratch_bytes, gww_train_workspace_bytes_adapters (adapter gradients of fc1 / fc2 and of ranks 1..64; gww_dora_target.proj 4 / 5); + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -272,6 +272,20 @@ int gww_encoder_train_backward_full(gww_encoder* enc, int batch, void* workspace
                                     const void* saved, size_t saved_bytes, const float* d_last_hidden,
                                     const gww_dora_target* targets, int n_targets, float* d_x0, float* d_mel,
                                     int pooled, const gww_enc_grads* grads, void* stream);
+/* The same step in exact fp32 (precision="fp32": every saved activation fp32, every contraction on the fp32 MFMA; the
+ * per-op path at every width).  Same arguments and contract as gww_encoder_train_forward / _backward, on an arena and a
+ * workspace sized by the two queries below (the workspace includes the adapter-gradient scratch for ranks up to 64).
+ * LN1 / LN2 outputs and the fc1 pre-activation are recomputed in the backward, not saved.  No base-parameter gradients
+ * (full fine-tuning stays bf16).  workspace and saved 256-byte aligned, mel and d_last_hidden 16-byte aligned. */
+size_t gww_train_saved_bytes_f32(const gww_encoder* enc, int batch);
+size_t gww_train_workspace_bytes_f32(const gww_encoder* enc, int batch);
+int gww_encoder_train_forward_f32(gww_encoder* enc, const float* mel, int batch, void* workspace,
+                                  size_t workspace_bytes, void* saved, size_t saved_bytes,
+                                  float* last_hidden, int pooled, void* stream);
+int gww_encoder_train_backward_f32(gww_encoder* enc, int batch, void* workspace, size_t workspace_bytes,
+                                   const void* saved, size_t saved_bytes, const float* d_last_hidden,
+                                   const gww_dora_target* targets, int n_targets, float* d_x0, float* d_mel,
+                                   int pooled, void* stream);
 
 /* Weight-gradient GEMM (csrc/wgrad.hip): dW[N,K] += alpha * sum_m dY[m,n] X[m,k], db[N] += alpha * sum_m dY[m,n]
  * (db may be NULL).  dY [M, ldy] and X [M, ldx] bf16 row-major, 16-byte aligned; dW, db fp32.  The reduction over M
@@ -465,6 +479,14 @@ int gww_attention_bwd_log2q_bf16(const void* qkv, const void* ctx, const void* d
                                  float* d_scratch, void* dqkv, int B, int T, int n_heads, void* stream);
 /* forward attention that also returns the row log-sum-exp lse [B,H,T] */
 int gww_attention_lse_bf16(const void* qkv, void* ctx, float* lse, int B, int T, int n_heads, void* stream);
+/* fp32 twins (exact fp32 MFMA): the forward with lse -- ctx bit-identical to gww_attention_f32's -- and the backward.
+ * qkv / ctx / dctx / dqkv fp32 with the layouts above, q as stored (pre-scaled by 1/8) and its gradient with respect to
+ * that stored q; d_scratch: gww_attention_bwd_f32_scratch_bytes (row dots + live flags of 32-row query tiles: tiles
+ * whose dctx rows are all zero are skipped).  No atomics: two identical calls give identical bits. */
+int gww_attention_lse_f32(const float* qkv, float* ctx, float* lse, int B, int T, int n_heads, void* stream);
+size_t gww_attention_bwd_f32_scratch_bytes(int B, int T, int n_heads);
+int gww_attention_bwd_f32(const float* qkv, const float* ctx, const float* dctx, const float* lse,
+                          float* d_scratch, float* dqkv, int B, int T, int n_heads, void* stream);
 /* attention probabilities P[b,h,i,j] = softmax_j(q_i . k_j), fp32 [B, n_heads, T, T] (HF eager attn_weights) from
  * qkv [B*T, 3d] as the attention kernels read it (q pre-scaled by 1/8; bf16: times log2(e) when q_log2 != 0, the
  * encoder's packed bf16 q panels).  Scores by MFMA on the given operands (bf16: 32x32x16 bf16, fp32: 32x32x2 f32);
@@ -498,6 +520,16 @@ int gww_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, lo
                       float yscale, float scaling, const float* A, const float* B, const float* mag, const float* nrm,
                       float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r, void* scratch,
                       size_t scratch_bytes, void* stream);
+/* gww_adapter_grads in exact fp32 (train_f32.hip): X, dY, Y fp32 with the same strides and contract; d_in, d_out
+ * multiples of 32, ranks 1..64, row strides multiples of 4.  u = x A^T and v = (g dy) B on the fp32 MFMA, dA / dB by a
+ * row-reduction GEMM over fixed row slabs summed in slab order: two identical calls give identical bits.  scratch
+ * (optional, 256-byte aligned): gww_adapter_grads_f32_scratch_bytes(M, d_in, d_out, r) bytes, else allocated
+ * stream-ordered. */
+size_t gww_adapter_grads_f32_scratch_bytes(long M, int d_in, int d_out, int r);
+int gww_adapter_grads_f32(const float* X, long ldx, const float* dY, const float* Y, long ldy, const float* bias_st,
+                          float yscale, float scaling, const float* A, const float* B, const float* mag, const float* nrm,
+                          float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r, void* scratch,
+                          size_t scratch_bytes, void* stream);
 int gww_dora_grads_multi(const void* X, long ldx, const void* dY, const void* Y, long ldy, int np,
                          const long* col_off, const float* const* bias_st, const float* yscale,
                          const float* scaling, const float* const* A, const float* const* B,
