@@ -200,6 +200,15 @@ SIGNATURES = {
                                                 + [C.c_void_p] * 5),
     "gww_assemble_batch_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gww_head_forward_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong,
+                                       C.c_ulonglong] + [C.c_void_p] * 9),
+    "gww_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gww_head_backward_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
+                              + [C.c_void_p] * 11),
+    "gww_head_dropout_mask_f32": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                            C.c_void_p]),
+    "gww_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

@@ -753,3 +753,95 @@ def assemble_batch(noise, wave, idx_noise, idx_wave, snr):
                                            noise[0].numel(), plan_d[0].data_ptr(), plan_d[1].data_ptr(),
                                            plan_d[2].data_ptr(), R, out.data_ptr(), _stream()), "gww_assemble_batch_f32")
     return out
+
+
+HEAD_WIDTHS = (512, 256, 128)      # hidden widths of models.glitch_classifier's head (Glitch_classification/src/model.py)
+
+
+def _head_params(params):
+    if len(params) != 8:
+        raise _lib.GwwError("head: expected (w1, b1, w2, b2, w3, b3, w4, b4)")
+    ps = [_dev(p, torch.float32, "head parameter") for p in params]
+    d_in, C = ps[0].shape[1], ps[6].shape[0]
+    shapes = [(512, d_in), (512,), (256, 512), (256,), (128, 256), (128,), (C, 128), (C,)]
+    for p, s in zip(ps, shapes):
+        if tuple(p.shape) != s:
+            raise _lib.GwwError(f"head: parameter of shape {tuple(p.shape)} where the glitch head d_in -> 512 -> 256 -> 128 "
+                                f"-> C has {s}")
+    return ps, d_in, C
+
+
+def head_forward(x, params, labels, p: float = 0.3, train: bool = False, seed: int = 0, offset: int = 0):
+    """Glitch head + CrossEntropyLoss forward (``gww_head_forward_f32``, 2 launches): x fp32 [B, d_in], params the eight
+    ``nn.Linear`` tensors of ``glitch_classifier.classifier`` in order, labels int64 [B].  Returns (loss [1] device
+    scalar, logits [B, C], row_loss [B], pred [B] int64, saved) with ``saved`` what ``head_backward`` needs."""
+    x = _dev(x, torch.float32, "x")
+    labels = _dev(labels, torch.int64, "labels")
+    ps, d_in, C = _head_params(params)
+    if x.dim() != 2 or x.shape[1] != d_in or labels.shape != (x.shape[0],):
+        raise _lib.GwwError(f"head_forward: x {tuple(x.shape)} / labels {tuple(labels.shape)} do not fit d_in = {d_in}")
+    B, dev = x.shape[0], x.device
+    h = [torch.empty((B, w), dtype=torch.float32, device=dev) for w in HEAD_WIDTHS]
+    logits = torch.empty((B, C), dtype=torch.float32, device=dev)
+    dz = torch.empty((B, C), dtype=torch.float32, device=dev)
+    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    pred = torch.empty((B,), dtype=torch.int64, device=dev)
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], labels.data_ptr(), B, d_in, C, float(p),
+                                         int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
+                                         h[0].data_ptr(), h[1].data_ptr(), h[2].data_ptr(), logits.data_ptr(),
+                                         row_loss.data_ptr(), pred.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
+              "gww_head_forward_f32")
+    return loss, logits, row_loss, pred, (x, ps, h, dz, float(p), bool(train))
+
+
+def head_backward(saved, dloss=None):
+    """(dx [B, d_in], [dw1, db1, ..., dw4, db4]) of ``head_forward``'s loss times the device scalar ``dloss``
+    (``gww_head_backward_f32``, 2 launches; no host sync)."""
+    x, ps, h, dz, p, train = saved
+    B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
+    if dloss is not None:
+        dloss = _dev(dloss.reshape(1), torch.float32, "dloss")
+    ws = torch.empty((lib().gww_head_workspace_bytes(B, C) // 4,), dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x)
+    grads = [torch.empty_like(t) for t in ps]
+    with torch.cuda.device(dev):
+        check(lib().gww_head_backward_f32(x.data_ptr(), ps[0].data_ptr(), ps[2].data_ptr(), ps[4].data_ptr(),
+                                          ps[6].data_ptr(), h[0].data_ptr(), h[1].data_ptr(), h[2].data_ptr(), dz.data_ptr(),
+                                          None if dloss is None else dloss.data_ptr(), B, d_in, C, p, int(train),
+                                          ws.data_ptr(), dx.data_ptr(), *[g.data_ptr() for g in grads], _stream()),
+              "gww_head_backward_f32")
+    return dx, grads
+
+
+def head_dropout_mask(seed: int, offset: int, layer: int, B: int, width: int, p: float = 0.3, device="cuda"):
+    """The [B, width] fp32 mask (1 kept / 0 dropped) ``head_forward(train=True)`` applies after hidden layer ``layer``
+    (0, 1, 2) for this (seed, offset): Philox4x32-10 on the element index, independent of B and of launch geometry."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.GwwError(f"head_dropout_mask: device must be a GPU (got {device}); gw_whisper_amd has no CPU path")
+    mask = torch.empty((B, width), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        check(lib().gww_head_dropout_mask_f32(int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), layer, B, width,
+                                              float(p), mask.data_ptr(), _stream()), "gww_head_dropout_mask_f32")
+    return mask
+
+
+def eval_accumulate(logits, labels, row_loss, confusion, loss_sum, n):
+    """One batch into the device-resident evaluation state (``gww_eval_accumulate``, one launch, no host sync):
+    confusion int64 [C, C] (rows = true class), loss_sum fp64 [1], n int64 [1] are updated in place."""
+    logits = _dev(logits, torch.float32, "logits")
+    labels = _dev(labels, torch.int64, "labels")
+    row_loss = _dev(row_loss, torch.float32, "row_loss")
+    B, C = logits.shape
+    for t, dt, shape, name in ((confusion, torch.int64, (C, C), "confusion"), (loss_sum, torch.float64, (1,), "loss_sum"),
+                               (n, torch.int64, (1,), "n")):
+        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise _lib.GwwError(f"eval_accumulate: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
+    if labels.shape != (B,) or row_loss.shape != (B,):
+        raise _lib.GwwError("eval_accumulate: labels and row_loss must be [B]")
+    with torch.cuda.device(logits.device):
+        check(lib().gww_eval_accumulate(logits.data_ptr(), labels.data_ptr(), row_loss.data_ptr(), B, C,
+                                        confusion.data_ptr(), loss_sum.data_ptr(), n.data_ptr(), _stream()),
+              "gww_eval_accumulate")

@@ -128,3 +128,36 @@ def strain_segments(n: int, seed: int = 0, n_samples: int = 16000) -> np.ndarray
     (BASELINE.md section 3)."""
     rng = np.random.default_rng(seed)
     return rng.standard_normal((n, n_samples)).astype(np.float32)
+
+
+def glitch_class_names(n_classes: int) -> list:
+    """Raw (dataset-style) label strings of the synthetic glitch set: ``GW`` first, then ``burst_band_<k>``."""
+    return ["GW"] + [f"burst_band_{k:02d}" for k in range(1, n_classes)]
+
+
+def glitch_segments(n: int, n_classes: int, seed: int = 0, n_samples: int = 16000):
+    """Seeded, learnable multi-class set for the glitch-classification programs: unit-variance noise plus one glitch-like
+    burst per segment whose frequency band, duration and chirp sign are the class (the idea of the config 4 fixture,
+    tools/make_golden.py:317); as with real glitch classes the typical loudness differs by class as well, which is what
+    reaches the pooled last token of a 1 s segment most directly (it sets the log-mel clamp of the 29 s of padding).  Segment ``i`` has class ``i % n_classes``; centre time and loudness vary per segment.
+    Returns (wave [n, n_samples] float32, class index [n] int64, SNR-like loudness [n] float32)."""
+    if n_classes < 1 or n_classes > 64:
+        raise ValueError(f"n_classes={n_classes}: expected 1..64")
+    seg = strain_segments(n, seed=seed, n_samples=n_samples)
+    rng = np.random.default_rng(seed + 104729)
+    t = np.arange(n_samples, dtype=np.float64) / 16000.0
+    labels = (np.arange(n) % n_classes).astype(np.int64)
+    loud = np.empty(n, np.float32)
+    for i in range(n):
+        c = int(labels[i])
+        band = (0, 4, 2, 6, 1, 5, 3, 7)[c % 8]                                   # few classes: bands far apart
+        f0 = 80.0 * (1.8 ** band) * (1.0 + 0.04 * rng.standard_normal())         # band: 80 Hz ... 4.9 kHz
+        dur = (0.015, 0.06, 0.2)[(c // 8) % 3]                                   # duration
+        sign = 1.0 if (c // 24) % 2 == 0 else -1.0                               # chirp sign
+        chirp = sign * (0.5 if c >= 24 else 0.0) * f0 / max(dur, 1e-3)
+        tc = 0.3 + 0.4 * rng.random()
+        amp = 3.0 * (1.6 ** (c % 5)) * (1.0 + 0.05 * rng.standard_normal())      # classes differ in typical loudness too
+        dt = t - tc
+        seg[i] += (amp * np.sin(2 * np.pi * (f0 + 0.5 * chirp * dt) * dt) * np.exp(-(dt / dur) ** 2)).astype(np.float32)
+        loud[i] = amp
+    return seg, labels, loud

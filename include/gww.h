@@ -561,6 +561,36 @@ int gww_qadapter_tail_backward_f32(const float* g, long g_batch_stride, const fl
  * and snr (fp32) are device arrays of R entries.  A row with an index outside its array is written NaN. */
 int gww_assemble_batch_f32(const float* noise, long n_noise, const float* wave, long n_wave, long row_len,
                            const int* idx_noise, const int* idx_wave, const float* snr, int R, float* out, void* stream);
+/* Glitch-classification head step (classify.hip; fp32 on the exact fp32 MFMA, no float atomics: two identical calls give
+ * identical bits).  The head is models.glitch_classifier's nn.Sequential (Glitch_classification/src/model.py:4-39):
+ * x [B, d_in] -> Linear 512 -> ReLU -> Dropout(p) -> Linear 256 -> ReLU -> Dropout -> Linear 128 -> ReLU -> Dropout ->
+ * Linear C, CrossEntropyLoss (mean) against labels [B] (int64).  d_in a multiple of 128 in 128..1280, C 1..64, B 1..1024;
+ * w_i [out, in] and b_i [out] as nn.Linear stores them, every float pointer 16-byte aligned.
+ * Forward (2 launches): writes the post-dropout activations h1 [B, 512], h2 [B, 256], h3 [B, 128], logits [B, C],
+ * row_loss [B] (lse - z[y]; NaN for a label outside [0, C)), pred [B] (int64 argmax: a NaN logit is the maximum, ties go
+ * to the lowest index), dz [B, C] = (softmax - onehot) / B and the device scalar loss = mean(row_loss).  train != 0
+ * applies dropout: element e = row * width + col of layer l (0..2) is dropped when word e % 4 of
+ * Philox4x32-10(counter = (e / 4, l, offset lo, offset hi), key = (seed lo, seed hi)) is below p * 2^32, kept values are
+ * scaled by 1 / (1 - p); gww_head_dropout_mask_f32 returns that mask (1 kept / 0 dropped) for a [B, width] activation.
+ * Backward (2 launches): reads the upstream gradient of the loss from the device scalar dloss (NULL: 1), writes
+ * dx [B, d_in] and the eight parameter gradients (not accumulated); ws: gww_head_workspace_bytes(B, C) bytes. */
+int gww_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                         const float* w3, const float* b3, const float* w4, const float* b4, const long long* labels,
+                         int B, int d_in, int C, float p, int train, unsigned long long seed, unsigned long long offset,
+                         float* h1, float* h2, float* h3, float* logits, float* row_loss, long long* pred, float* dz,
+                         float* loss, void* stream);
+size_t gww_head_workspace_bytes(int B, int C);
+int gww_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
+                          const float* h1, const float* h2, const float* h3, const float* dz, const float* dloss, int B,
+                          int d_in, int C, float p, int train, float* ws, float* dx, float* dw1, float* db1, float* dw2,
+                          float* db2, float* dw3, float* db3, float* dw4, float* db4, void* stream);
+int gww_head_dropout_mask_f32(unsigned long long seed, unsigned long long offset, int layer, int B, int width, float p,
+                              float* mask, void* stream);
+/* Evaluation accumulate, one one-workgroup launch per batch: confusion [C, C] (int64, rows = true class) += 1 at
+ * (labels[r], argmax logits[r]) with gww_head_forward_f32's argmax rule, loss_sum (fp64) += sum of row_loss in a fixed
+ * order, n (int64) += B; all three are device buffers the host reads once per epoch.  C 1..64, B 1..65536. */
+int gww_eval_accumulate(const float* logits, const long long* labels, const float* row_loss, int B, int C,
+                        long long* confusion, double* loss_sum, long long* n, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
