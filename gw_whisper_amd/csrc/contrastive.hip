@@ -348,8 +348,9 @@ extern "C" int gww_qadapter_tail_backward_f32(const float* g, long g_batch_strid
   GWW_REQUIRE(B >= 1 && Hin > 0 && Win > 0 && Win <= gww::TB_MAXW && F > 0 && T > 0 && T <= gww::TB_MAXT,
               "gww_qadapter_tail_backward_f32: bad shape B=%d Hin=%d Win=%d F=%d T=%d", B, Hin, Win, F, T);
   GWW_REQUIRE(g_batch_stride >= (long)F * T, "gww_qadapter_tail_backward_f32: g batch stride %ld < F * T", g_batch_stride);
-  GWW_REQUIRE(ws_bytes >= gww_qadapter_tail_backward_workspace_bytes(B, Hin),
-              "gww_qadapter_tail_backward_f32: workspace of %zu bytes is too small", ws_bytes);
+  if (ws_bytes < gww_qadapter_tail_backward_workspace_bytes(B, Hin))
+    return ::gww::fail(GWW_ERR_WORKSPACE, "gww_qadapter_tail_backward_f32: workspace %zu bytes < required %zu", ws_bytes,
+                gww_qadapter_tail_backward_workspace_bytes(B, Hin));
   hipStream_t s = (hipStream_t)stream;
   double* part = (double*)ws;
   for (int b0 = 0; b0 < B; b0 += 65535) {   // gridDim.y limit

@@ -109,6 +109,8 @@ class _EncoderTrain(torch.autograd.Function):
             check(fwd(h, x.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(),
                       int(pooled), torch.cuda.current_stream().cuda_stream),
                   "gww_encoder_train_forward" + ("_f32" if f32 else ""))
+        # the backward gets THIS workspace back: d_mel and the conv-stem gradients are formed from what the forward left
+        # at its front (include/gww.h); everything else in it is scratch
         ctx.enc, ctx.B, ctx.ws, ctx.saved, ctx.pooled = enc, B, ws, saved, bool(pooled)
         ctx.n_params = len(params)
         ctx.mel_shape = tuple(x.shape)

@@ -240,6 +240,12 @@ int gww_encoder_train_backward(gww_encoder* enc, int batch, void* workspace, siz
  * [batch, n_mels, t_in] gradient w.r.t. the input features through the conv stem -- the encoder call is
  * differentiable w.r.t. its input, as MLGWSC-1/train.py:494-504 (trainable Q-adapter in front of the frozen
  * encoder) requires. */
+/* workspace / saved between the two calls of a step: `saved` carries the activations and goes to the backward unmodified.
+ * `workspace` is scratch -- its contents need not survive from the forward to the backward -- EXCEPT when the backward is
+ * asked for d_mel or (gww_encoder_train_backward_full) for a conv1 / conv2 gradient: those are formed from the stem's
+ * transposed input and conv1 output, which the forward leaves at the front of ITS workspace and does not copy into
+ * `saved`.  Such a backward must be handed the forward's workspace with those bytes untouched (the Python shim keeps the
+ * forward's workspace on the autograd node for every step).  The same holds for the fp32 twins below. */
 
 /* --------------------------------------------------------------------------
  * Full fine-tuning (bf16): the same backward, plus the gradients of the base parameters

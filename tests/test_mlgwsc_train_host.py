@@ -198,7 +198,7 @@ def test_new_entries_are_bound_and_validate_without_gpu():
     assert lib.gww_qadapter_tail_backward_f32(p, 240000, p, 0, 32, 32, 80, 3000, p, p, p, p, p, 1 << 20,
                                               p, p, p, p, None) == -1                             # B < 1
     assert lib.gww_qadapter_tail_backward_f32(p, 240000, p, 2, 32, 32, 80, 3000, p, p, p, p, p, 8,
-                                              p, p, p, p, None) == -1                             # workspace too small
+                                              p, p, p, p, None) == -3                             # GWW_ERR_WORKSPACE
     assert b"workspace" in lib.gww_last_error()
     assert lib.gww_assemble_batch_f32(p, 4, p, 2, 4096, None, p, p, 8, p, None) == -1
     assert lib.gww_assemble_batch_f32(p, 4, p, 2, 4096, p, p, p, 0, p, None) == -1              # R < 1
