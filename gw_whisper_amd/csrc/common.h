@@ -105,6 +105,15 @@ __device__ __forceinline__ float gelu_sig4(float x) {
   const float e = __builtin_amdgcn_exp2f(x * q);
   return x * __builtin_amdgcn_rcpf(1.0f + e);
 }
+// ... and its sigmoid factor alone: gelu_sig4(x) == x * gelu_sig4_sigma(x), operation for operation (the compact conv stem
+// stores x and this factor apart, gemm_v4.hip: EPI_CONV2T).  Keep the two in step.
+__device__ __forceinline__ float gelu_sig4_sigma(float x) {
+  const float s = fminf(x * x, 64.0f);
+  float q = fmaf(s, 0.0010148164f, -0.1067791331f);
+  q = fmaf(s, q, -2.3011178f);
+  const float e = __builtin_amdgcn_exp2f(x * q);
+  return __builtin_amdgcn_rcpf(1.0f + e);
+}
 
 // gelu'(z) = Phi(z) + z phi(z) for the training backward: the same 7.1.26 polynomial, whose exp(-z^2 / 2) factor is
 // sqrt(2 pi) phi(z) -- 16 VALU operations (two transcendental) where ocml erff + expf take about sixty
@@ -145,7 +154,14 @@ int launch_gemm_astat(const void* A, long lda, const void* delta, float* x_out, 
                       int epi, int rows_per_batch, hipStream_t s, long c_panel_rows = 0);
 int launch_cast_f32_bf16(const float* x, void* y, long n, hipStream_t s);
 bool conv1_mel_supported(int n_mels, int d, int kpad);
-int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s);
+int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s,
+                     int t_stride = 0, const int* run_flag = nullptr, int run_if = 0);
+// the constant tail of a padded log-mel (stem_tail.hip): the stem on the first kStemTc frames, kStemTt compact tokens
+constexpr int kStemTc = 256, kStemTt = kStemTc / 2;
+bool stem_tail_supported(int t_in, int d);
+int launch_stem_detect(const float* mel, int* flag, long rows, int t_in, hipStream_t s);
+int launch_stem_fill(const float* xs, const float* tr, const float* pos, float* x, const int* flag, int B, int T, int d,
+                     hipStream_t s);
 int launch_pack_weight(const float* w, void* out, int out_bf16, int N, int C, int taps, int Kpad,
                        float scale, hipStream_t s);
 int launch_scale_copy(const float* in, float* out, int n, float scale, hipStream_t s);
@@ -188,7 +204,8 @@ int launch_gemm_bf16(const void* A, long lda, const void* W, const float* bias, 
                      hipStream_t s, int rows_padded_256 = 0);
 int launch_gemm_bf16_v4(const void* A, long lda, const void* W, const float* bias, const float* resid, void* C, long M,
                         int N, int K, int epi, hipStream_t s, int force_split = 0, const float* pos = nullptr,
-                        int rows_per_batch = 0, int n_real = 0, float* dump = nullptr);
+                        int rows_per_batch = 0, int n_real = 0, float* dump = nullptr, const int* run_flag = nullptr,
+                        int run_if = 0, float* tmpl_r = nullptr, int tmpl_t = 0);
 int launch_gemm_fulln(const void* A, long lda, const void* W, const float* bias, const float* pos, void* C,
                       long M, int N, int K, int epi, int rows_per_batch, hipStream_t s);
 int launch_gemm_f32(const float* A, long lda, const float* W, const float* bias, const float* resid,

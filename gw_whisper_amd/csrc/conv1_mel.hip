@@ -20,6 +20,11 @@
 //   * D[channel][token]: a lane holds four consecutive channels of one token -> bias + GELU + one 8-byte store per
 //     16 x 16 tile, no transpose; the 8 waves of a workgroup fill the 768-byte (d = 384) rows between them.
 //   * the zero rows 0 and T + 1 of every segment (Conv1d padding of conv2) are written by the first / last chunk.
+//   * T is the LOGICAL length of a segment, ts the distance between two mel rows in memory (a segment is 80 ts floats).  They
+//     differ for the compact stem (encoder.hip): the first T = 256 frames of every 3 000-frame segment as a sequence of its own,
+//     frame T reading as Conv1d's zero padding like the end of a whole segment does, into a compact c1 [B, T + 2, d].
+//   * run_flag (optional): the launch does nothing unless *run_flag == run_if -- the stem enqueues the full and the compact
+//     form behind each other and k_stem_detect's flag says which of them runs.
 #include "common.h"
 
 #ifndef GWW_C1M_TABLE
@@ -43,7 +48,9 @@ constexpr int C1M_NPF = (C1M_PAIRS + 511) / 512;
 template <int NCB>   // 16-channel blocks per wave
 __global__ __launch_bounds__(512, 1) void k_conv1_mel(const float* __restrict__ mel, const unsigned short* __restrict__ W,
                                                       const float* __restrict__ bias, unsigned short* __restrict__ c1,
-                                                      int T, int d, int chunks_per_seg, int n_items) {
+                                                      int T, int ts, int d, int chunks_per_seg, int n_items,
+                                                      const int* __restrict__ run_flag, int run_if) {
+  if (run_flag && *run_flag != run_if) return;   // block-uniform (one scalar load), in front of every barrier
   __shared__ __attribute__((aligned(16))) unsigned char tile[2 * C1M_BUF];
 #if GWW_C1M_TABLE
   // GELU by table: Phi on [-8, 8) in 1 024 intervals with its forward difference beside it -- gelu(x) = x (Phi_i + f dPhi_i),
@@ -91,7 +98,7 @@ __global__ __launch_bounds__(512, 1) void k_conv1_mel(const float* __restrict__ 
   float pf[C1M_NPF][2];
   auto request = [&](int item) {
     const int b = item / chunks_per_seg, t0 = (item - b * chunks_per_seg) * C1M_TOK;
-    const float* src = mel + (long)b * C1M_C * T;
+    const float* src = mel + (long)b * C1M_C * ts;
 #pragma unroll
     for (int i = 0; i < C1M_NPF; ++i) {
       const int e = i * 512 + tid;
@@ -100,9 +107,9 @@ __global__ __launch_bounds__(512, 1) void k_conv1_mel(const float* __restrict__ 
       cp = cp < C1M_C / 2 ? cp : C1M_C / 2 - 1;
       int t = t0 - 1 + ti;
       t = t < 0 ? 0 : (t < T ? t : T - 1);
-      const float* p = src + (long)(2 * cp) * T + t;
+      const float* p = src + (long)(2 * cp) * ts + t;
       pf[i][0] = p[0];
-      pf[i][1] = p[T];
+      pf[i][1] = p[ts];
     }
   };
   auto deposit = [&](int buf, int item) {
@@ -185,12 +192,15 @@ bool conv1_mel_supported(int n_mels, int d, int kpad) {
 }
 
 // mel [B, 80, T] fp32 (HF input_features), W [d, 256] bf16 with k = tap * 80 + c (zero for k >= 240), bias [d] fp32
-// -> c1 [B, T + 2, d] bf16 incl. its zero rows.
-int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s) {
+// -> c1 [B, T + 2, d] bf16 incl. its zero rows.  t_stride > T: mel is [B, 80, t_stride] and only its first T frames are read.
+int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s,
+                     int t_stride, const int* run_flag, int run_if) {
   GWW_REQUIRE(mel && W && bias && c1, "conv1_mel: NULL operand");
   GWW_REQUIRE(conv1_mel_supported(C1M_C, d, C1M_KPAD), "conv1_mel: d=%d unsupported", d);
   GWW_REQUIRE(T > 0 && (((uintptr_t)W) & 15) == 0 && (((uintptr_t)c1) & 7) == 0 && (((uintptr_t)bias) & 15) == 0,
               "conv1_mel: bad shape or alignment");
+  if (t_stride == 0) t_stride = T;
+  GWW_REQUIRE(t_stride >= T, "conv1_mel: row stride %d < length %d", t_stride, T);
   if (B == 0) return GWW_OK;
   const int cps = (int)cdiv(T, C1M_TOK);
   const long n_items = (long)B * cps;
@@ -199,11 +209,11 @@ int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c
   const int cus = 256 / nsplit;
   dim3 grid((unsigned)(n_items < cus ? n_items : cus), (unsigned)nsplit);
   if (ncb == 3)
-    hipLaunchKernelGGL(k_conv1_mel<3>, grid, dim3(512), 0, s, mel, (const unsigned short*)W, bias, (unsigned short*)c1, T, d,
-                       cps, (int)n_items);
+    hipLaunchKernelGGL(k_conv1_mel<3>, grid, dim3(512), 0, s, mel, (const unsigned short*)W, bias, (unsigned short*)c1, T, t_stride,
+                       d, cps, (int)n_items, run_flag, run_if);
   else
-    hipLaunchKernelGGL(k_conv1_mel<4>, grid, dim3(512), 0, s, mel, (const unsigned short*)W, bias, (unsigned short*)c1, T, d,
-                       cps, (int)n_items);
+    hipLaunchKernelGGL(k_conv1_mel<4>, grid, dim3(512), 0, s, mel, (const unsigned short*)W, bias, (unsigned short*)c1, T, t_stride,
+                       d, cps, (int)n_items, run_flag, run_if);
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }

@@ -131,6 +131,7 @@ struct gww_encoder {
   gww_enc_cfg cfg{};
   bool ready = false;
   bool trace = false;
+  bool stem_shortcut = true;        // the constant-tail shortcut of the bf16 inference stem (gww_encoder_set_stem_shortcut)
   std::vector<TraceSpan> spans;     // recorded since the last read
   std::vector<hipEvent_t> pool;     // reusable events
   // dual-stream split: two half batches on two library-owned streams, so HBM-bound kernels of one
@@ -144,6 +145,7 @@ struct gww_encoder {
   unsigned short *c1wT = nullptr, *c2wT = nullptr;   // [Kpad, d] / [3 d, d]: input-gradient GEMMs of the stem
   float *c1w32 = nullptr, *c2w32 = nullptr;
   float *c1b = nullptr, *c2b = nullptr, *pos = nullptr, *lnw = nullptr, *lnb = nullptr;
+  float* pos_c = nullptr;           // [kStemTt, d] positions of the compact stem: pos[0 .. Tt - 3], a zero row, pos[T - 1]
   std::vector<LayerW> layers;
 };
 
@@ -167,6 +169,7 @@ extern "C" int gww_encoder_create(const gww_enc_cfg* cfg, gww_encoder** out) {
   const size_t o_c1wT = take((size_t)d * Kc1 * 2), o_c2wT = take((size_t)d * 3 * d * 2);
   const size_t o_c1b = take(d * 4), o_c2b = take(d * 4), o_pos = take((size_t)T * d * 4);
   const size_t o_lnw = take(d * 4), o_lnb = take(d * 4);
+  const size_t o_posc = take((size_t)kStemTt * d * 4);
   struct LO { size_t wqkv, wo, w1, w2, wqkv32, wo32, w132, w232, bqkv, bqkv16, bo, b1, b2, ln1w, ln1b, ln2w, ln2b,
                      wqkv_ln, w1_ln, uqkv, cbqkv, u1, cb1, wqkvT, woT, w1T, w2T, wmlp, wqkv_st, wmlp_op; };
   std::vector<LO> lo(L);
@@ -220,6 +223,7 @@ extern "C" int gww_encoder_create(const gww_enc_cfg* cfg, gww_encoder** out) {
   e->pos = (float*)(p + o_pos);
   e->lnw = (float*)(p + o_lnw);
   e->lnb = (float*)(p + o_lnb);
+  e->pos_c = (float*)(p + o_posc);
   e->layers.resize(L);
   for (int i = 0; i < L; ++i) {
     LayerW& w = e->layers[i];
@@ -332,6 +336,14 @@ static int pack_weights(gww_encoder* e, const gww_enc_globals* g, const gww_enc_
     GWW_TRY(pb.copy(g->conv1_b, e->c1b, d, 1.f));
     GWW_TRY(pb.copy(g->conv2_b, e->c2b, d, 1.f));
     GWW_HIP(hipMemcpyAsync(e->pos, g->pos, (size_t)T * d * 4, hipMemcpyDeviceToDevice, s));
+    if (T > kStemTt) {
+      // the compact stem's table (stem_tail.hip): compact tokens 0 .. Tt - 3 are the real ones, Tt - 2 is the position-free
+      // shared row (its store bypasses the table), Tt - 1 is the real token T - 1
+      GWW_HIP(hipMemcpyAsync(e->pos_c, g->pos, (size_t)(kStemTt - 2) * d * 4, hipMemcpyDeviceToDevice, s));
+      GWW_HIP(hipMemsetAsync(e->pos_c + (size_t)(kStemTt - 2) * d, 0, (size_t)d * 4, s));
+      GWW_HIP(hipMemcpyAsync(e->pos_c + (size_t)(kStemTt - 1) * d, g->pos + (size_t)(T - 1) * d, (size_t)d * 4,
+                             hipMemcpyDeviceToDevice, s));
+    }
     GWW_TRY(pb.copy(g->ln_w, e->lnw, d, 1.f));
     GWW_TRY(pb.copy(g->ln_b, e->lnb, d, 1.f));
   }
@@ -461,6 +473,34 @@ WsLayout ws_layout(const gww_enc_cfg& c, int B, int precision) {
   w.total = off;
   return w;
 }
+
+// ---- the constant-tail shortcut of the bf16 inference stem (stem_tail.hip).  Its buffers live in workspace that is idle
+// during the stem -- x2, the ping-pong partner of the residual stream, first written by layer 0 -- and its flag in the first
+// word of melT, which the direct conv1 never touches: gww_encoder_workspace_bytes is unchanged.
+struct StemTailLayout {
+  size_t c1s, xs, tr, dump, total;   // byte offsets inside x2
+};
+StemTailLayout stem_tail_layout(int B, int d) {
+  StemTailLayout t{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
+  // (like c1: conv2's 256-row panels read 2 * 255 + 3 rows past the last segment)
+  t.c1s = take((((size_t)B * (kStemTc + 2) + 255) / 256 * 256 + 520) * d * 2);
+  t.xs = take((size_t)B * kStemTt * d * 4);
+  t.tr = take((size_t)B * d * 4);
+  t.dump = take((size_t)d * 4);
+  t.total = off;
+  return t;
+}
+// where the shortcut applies: bf16, conv1 on k_conv1_mel, conv2 on k_gemm_bf16_v4 (bit 11 of GWW_GENERIC_PATH disables it)
+bool stem_shortcut_applies(const gww_encoder* e, int batch, int precision) {
+  static const int generic_mask = (int)lab_int("GWW_GENERIC_PATH", 0);
+  const gww_enc_cfg& c = e->cfg;
+  if (!e->stem_shortcut || precision != GWW_PREC_BF16 || batch <= 0 || (generic_mask & (2 | 4 | 2048))) return false;
+  if (!conv1_mel_supported(c.n_mels, c.d_model, conv1_kpad(c.n_mels)) || !stem_tail_supported(c.t_in, c.d_model)) return false;
+  const WsLayout w = ws_layout(c, batch, precision);
+  return stem_tail_layout(batch, c.d_model).total <= w.h - w.x2;
+}
 }  // namespace
 
 constexpr int kSplitMin = 32;   // segments per half below which splitting does not pay
@@ -474,6 +514,33 @@ extern "C" size_t gww_encoder_workspace_bytes(const gww_encoder* e, int batch, i
     return ws_layout(e->cfg, b0, precision).total + ws_layout(e->cfg, batch - b0, precision).total;
   }
   return ws_layout(e->cfg, batch, precision).total;
+}
+
+extern "C" int gww_encoder_set_stem_shortcut(gww_encoder* e, int on) {
+  GWW_REQUIRE(e != nullptr, "gww_encoder_set_stem_shortcut: NULL handle");
+  e->stem_shortcut = on != 0;
+  return GWW_OK;
+}
+
+// The device flags of the last forward that ran in `workspace` with this batch and precision (blocking; synchronise the
+// forward's stream first): flags[i] = 1 where half batch i took the shortcut, 0 where it ran the full stem, -1 where the
+// shortcut does not apply (switched off, fp32, a generic path, no second half).
+extern "C" int gww_encoder_stem_shortcut_flags(const gww_encoder* e, int batch, int precision, const void* workspace,
+                                               int* flags) {
+  GWW_REQUIRE(e && workspace && flags, "gww_encoder_stem_shortcut_flags: NULL argument");
+  GWW_REQUIRE(batch > 0 && (precision == GWW_PREC_BF16 || precision == GWW_PREC_F32),
+              "gww_encoder_stem_shortcut_flags: bad batch %d / precision %d", batch, precision);
+  flags[0] = flags[1] = -1;
+  const bool split = use_split(e, batch);
+  const int b[2] = {split ? batch / 2 : batch, split ? batch - batch / 2 : 0};
+  size_t off = 0;
+  for (int i = 0; i < 2 && b[i] > 0; ++i) {
+    const WsLayout w = ws_layout(e->cfg, b[i], precision);
+    if (stem_shortcut_applies(e, b[i], precision))
+      GWW_HIP(hipMemcpy(&flags[i], (const char*)workspace + off + w.melT, sizeof(int), hipMemcpyDeviceToHost));
+    off += w.total;
+  }
+  return GWW_OK;
 }
 
 extern "C" int gww_encoder_set_split(gww_encoder* e, int on) {
@@ -569,7 +636,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   }
   // A-stationary kernels (A panel in registers, fused residual-add + LayerNorm prologue) for K = d <= 512
   // GWW_GENERIC_PATH (debug aid): bit 0 = generic layer GEMMs, bit 1 = generic conv1, bit 2 = generic conv2, bit 3 = unfused MLP,
-  // bit 4 = stand-alone QKV, bit 5 = no pooled last layer, bit 6 = layer 0's LN1 + QKV by the LN-fused A-stationary GEMM, bit 7 = stand-alone out_proj, bit 8 = stand-alone final LayerNorm, bit 9 = A-stationary layer GEMMs at d = 512
+  // bit 4 = stand-alone QKV, bit 5 = no pooled last layer, bit 6 = layer 0's LN1 + QKV by the LN-fused A-stationary GEMM, bit 7 = stand-alone out_proj, bit 8 = stand-alone final LayerNorm, bit 9 = A-stationary layer GEMMs at d = 512, bit 10 = conv2 on the generic GEMM where k_gemm_fulln would take it, bit 11 = no constant-tail shortcut of the stem
   // d = 512 (whisper-base): since round 3 the LayerNorm kernel + the 256 x 256 GEMM (k_gemm_bf16_v3) beat the LN-fused
   // A-stationary layer GEMMs there (8.78 against 9.33 ms per 64 segments; bit 9 of the mask brings them back)
   const bool astat = bf && (d == 384 || (d == 512 && (generic_mask & 512))) && F % 128 == 0 && !(generic_mask & 1);
@@ -579,8 +646,35 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   // only the last token wanted: the last layer runs on B rows above its attention (bit 5 of the mask disables it)
   const bool outs = hidden_slab || attn_slab;   // per-layer outputs wanted: every layer runs on all rows
   const bool pooled = astat && !last_hidden && last_token && T >= 3 && !(generic_mask & 32) && !outs;
+  // The constant tail of a padded log-mel (stem_tail.hip): detection, then the stem on the first kStemTc frames and the fill
+  // of x, all predicated on the device flag; the full stem stays enqueued behind them and returns at once when the flag is 1,
+  // so it never reads the (then stale) c1.  One span per trace class: bench.py indexes its table by their names.
+  const bool shortcut = conv1_direct && stem_shortcut_applies(e, B, precision);
+  int* const st_flag = (int*)melT;
+  const StemTailLayout st = stem_tail_layout(B, d);
+  char* const st_base = base + w.x2;
+  void* const c1s = st_base + st.c1s;
+  float* const xs = (float*)(st_base + st.xs);
+  float* const st_tr = (float*)(st_base + st.tr);
+  auto stem_conv1 = [&]() -> int {
+    if (shortcut) {
+      GWW_TRY(launch_stem_detect(mel, st_flag, (long)B * C, Tin, s));
+      GWW_TRY(launch_conv1_mel(mel, e->c1w, e->c1b, c1s, B, kStemTc, d, s, Tin, st_flag, 1));
+    }
+    return launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s, 0, shortcut ? st_flag : nullptr, 0);
+  };
+  auto stem_conv2 = [&]() -> int {
+    const int Np = (d + 255) / 256 * 256;
+    if (shortcut) {
+      GWW_TRY(launch_gemm_bf16_v4(c1s, 2L * d, e->c2w, e->c2b, nullptr, xs, (long)B * (kStemTt + 1), Np, 3 * d, EPI_CONV2, s, 0,
+                                  e->pos_c, kStemTt + 1, d, (float*)(st_base + st.dump), st_flag, 1, st_tr, kStemTt - 2));
+      GWW_TRY(launch_stem_fill(xs, st_tr, e->pos, x, st_flag, B, T, d, s));
+    }
+    return launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), Np, 3 * d, EPI_CONV2, s, 0, e->pos,
+                               T + 1, d, x + (((size_t)B * T + 255) / 256 * 256) * d, shortcut ? st_flag : nullptr, 0);
+  };
   if (conv1_direct)
-    TR(TR_CONV1, launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s));
+    TR(TR_CONV1, stem_conv1());
   else if (bf && d % 128 == 0 && !(generic_mask & 2))
     TR(TR_CONV1, launch_gemm_astat(melT, C, nullptr, nullptr, nullptr, nullptr, e->c1w, e->c1b, c1,
                                    (long)B * (Tin + 2), d, Kc1, EPI_CONV1, Tin + 2, s));
@@ -588,8 +682,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
     TR(TR_CONV1, gemm(melT, C, e->c1w, e->c1w32, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, Kc1,
                       EPI_CONV1, Tin + 2));
   if (bf && d % 128 == 0 && d <= 3072 && !(generic_mask & 4))   // the eight-phase 256 x 256 GEMM over overlapping rows (gemm_v4.hip)
-    TR(TR_CONV2, launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), (d + 255) / 256 * 256, 3 * d,
-                                     EPI_CONV2, s, 0, e->pos, T + 1, d, x + (((size_t)B * T + 255) / 256 * 256) * d));
+    TR(TR_CONV2, stem_conv2());
   else if (bf && (d == 384 || d == 512) && !(generic_mask & 1024))
     TR(TR_CONV2, launch_gemm_fulln(c1, 2L * d, e->c2w, e->c2b, e->pos, x, (long)B * (T + 1), d, 3 * d, EPI_CONV2, T + 1, s));
   else

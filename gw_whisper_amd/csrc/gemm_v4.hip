@@ -74,6 +74,15 @@ __device__ __forceinline__ void vm_wait() {
 template <int I>
 using ic = std::integral_constant<int, I>;
 
+// EPI_CONV2 on the COMPACT stem (encoder.hip, "constant tail"): the same tile stream and arithmetic, and the row
+// t == tmpl_t of every segment is stored in parts.  The full kernel's epilogue is out = fma(x, r, pos[t]) with x = acc + bias
+// and r = the sigmoid factor of gelu_sig4 (hipcc contracts gelu_sig4(x) + pos into ONE v_pk_fma_f32: x * r is never rounded on
+// its own).  k_stem_fill adds a different position row to that token ~1 400 times, so it needs x and r themselves to
+// reproduce the single rounding: the template row's x goes where the token would have gone, its r into tmpl_r[b, :].
+// Every thread issues both stores of a tile (the ring waits count them); rows that are no template send the second one to
+// the scratch row.  Local to this file: never passed in from outside.
+constexpr int EPI_CONV2T = 16;
+
 }  // namespace
 
 template <int EPI>
@@ -82,7 +91,8 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_v4(const unsigned short* _
                                                          const float* __restrict__ bias, const float* resid,
                                                          void* C, long M, int N, int K, int n_split, int tpi, int n_items,
                                                          const float* __restrict__ pos, int rows_per_batch, int n_real,
-                                                         float* dump) {
+                                                         float* dump, const int* __restrict__ run_flag, int run_if,
+                                                         float* tmpl_r, int tmpl_t) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[2 * BUF4 + BIAS4 * 4];
   float* lds_bias = reinterpret_cast<float*>(lds + 2 * BUF4);   // the whole bias vector (N <= BIAS4)
   typedef __attribute__((address_space(3))) void* lds_ptr;
@@ -92,12 +102,18 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_v4(const unsigned short* _
   // per-segment garbage row t = rows_per_batch - 1 and the rows past M go to the scratch row `dump` (every store is
   // issued: the ring waits count them); the weight panel is padded to N % 256 == 0 with zero rows, n_real = the true
   // width -- a W half that is all padding gets no MFMAs and no stores
-  constexpr bool CONV2 = EPI == EPI_CONV2;
+  constexpr bool CONV2T = EPI == EPI_CONV2T;
+  constexpr bool CONV2 = EPI == EPI_CONV2 || CONV2T;
   constexpr bool BF16OUT = EPI != EPI_RESID && !CONV2;
   constexpr bool PRELOAD = EPI == EPI_RESID;
   unsigned short* __restrict__ const Cb = reinterpret_cast<unsigned short*>(C);
   float* const Cf = reinterpret_cast<float*>(C);   // (EPI_RESID: may alias resid)
-  constexpr int SQ = BF16OUT ? 4 : 8;              // stores per thread and output QUADRANT
+  constexpr int SQ = BF16OUT ? 4 : (CONV2T ? 16 : 8);   // stores per thread and output QUADRANT
+  // conv2 only: the stem enqueues the full and the compact form behind each other and a device flag (k_stem_detect) says
+  // which of them runs.  Block-uniform (one scalar load), in front of every barrier and LDS-DMA request.
+  if constexpr (CONV2) {
+    if (run_flag && *run_flag != run_if) return;
+  }
 
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -265,14 +281,37 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_v4(const unsigned short* _
         f32x4 pv[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) pv[j] = *reinterpret_cast<const f32x4*>(prow + col0 + j * 16);
+        if constexpr (CONV2T) {
+          // the full form's arithmetic spelled out: x = acc + bias, r = gelu_sig4_sigma(x), out = fma(x, r, pos)
+          const bool is_t = live && t == tmpl_t;
+          float* const rrow = is_t ? tmpl_r + (long)b * n_real : dump;
+          f32x4 rr[4];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const f32x4 bj = *reinterpret_cast<const f32x4*>(lds_bias + nn * 256 + wh * 128 + wc * 64 + (lane >> 4) * 4 + j * 16);
-          const f32x4 a = acc[ah][wh][i][j] + bj;
-          acc[ah][wh][i][j] = f32x4{gelu_sig4(a[0]), gelu_sig4(a[1]), gelu_sig4(a[2]), gelu_sig4(a[3])};
+          for (int j = 0; j < 4; ++j) {
+            const f32x4 bj = *reinterpret_cast<const f32x4*>(lds_bias + nn * 256 + wh * 128 + wc * 64 + (lane >> 4) * 4 + j * 16);
+            const f32x4 a = acc[ah][wh][i][j] + bj;
+            acc[ah][wh][i][j] = a;
+            rr[j] = f32x4{gelu_sig4_sigma(a[0]), gelu_sig4_sigma(a[1]), gelu_sig4_sigma(a[2]), gelu_sig4_sigma(a[3])};
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const f32x4 a = acc[ah][wh][i][j];
+            f32x4 v;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = is_t ? a[k] : __builtin_fmaf(a[k], rr[j][k], pv[j][k]);
+            *reinterpret_cast<f32x4*>(orow + col0 + j * 16) = v;
+            *reinterpret_cast<f32x4*>(rrow + col0 + j * 16) = rr[j];
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const f32x4 bj = *reinterpret_cast<const f32x4*>(lds_bias + nn * 256 + wh * 128 + wc * 64 + (lane >> 4) * 4 + j * 16);
+            const f32x4 a = acc[ah][wh][i][j] + bj;
+            acc[ah][wh][i][j] = f32x4{gelu_sig4(a[0]), gelu_sig4(a[1]), gelu_sig4(a[2]), gelu_sig4(a[3])};
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(orow + col0 + j * 16) = acc[ah][wh][i][j] + pv[j];
         }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) *reinterpret_cast<f32x4*>(orow + col0 + j * 16) = acc[ah][wh][i][j] + pv[j];
       } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -525,12 +564,14 @@ __global__ __launch_bounds__(512, 1) void k_gemm_bf16_v4(const unsigned short* _
 // split-invariance test checks bit for bit
 int launch_gemm_bf16_v4(const void* A, long lda, const void* W, const float* bias, const float* resid, void* C, long M,
                         int N, int K, int epi, hipStream_t s, int force_split, const float* pos, int rows_per_batch,
-                        int n_real, float* dump) {
+                        int n_real, float* dump, const int* run_flag, int run_if, float* tmpl_r, int tmpl_t) {
   // (no lower bound on M: a segment's rows must not depend on how many segments share the launch -- the batch-independence
   // property the tests check bit for bit -- so the kernel choice may depend on N and K only)
   if (N % 256 != 0 || K % 128 != 0 || N > BIAS4 || M < 1) return -1;
   if (!(epi == EPI_BIAS || epi == EPI_GELU || epi == EPI_RESID || epi == EPI_CONV2)) return -1;
   if (epi == EPI_CONV2) {
+    GWW_REQUIRE(!tmpl_r || (tmpl_t >= 0 && tmpl_t < rows_per_batch - 1), "gemm_bf16_v4: conv2 template row %d outside the segment", tmpl_t);
+    if (tmpl_r) epi = EPI_CONV2T;
     GWW_REQUIRE(M < 2147483647L, "gemm_bf16_v4: conv2 row count too large");
     GWW_REQUIRE(pos && rows_per_batch > 1 && n_real > 0 && n_real <= N && N - n_real < 256 && n_real % 128 == 0 && dump,
                 "gemm_bf16_v4: conv2 epilogue needs pos, rows_per_batch, n_real (N - 255 .. N, a multiple of 128) and a scratch row");
@@ -579,10 +620,11 @@ int launch_gemm_bf16_v4(const void* A, long lda, const void* W, const float* bia
   case E:                                                                                             \
     hipLaunchKernelGGL((k_gemm_bf16_v4<E>), grid, block, 0, s, (const unsigned short*)A, lda,         \
                        (const unsigned short*)W, bias, resid, C, M, N, K, n_split, tpi, (int)n_items, pos,     \
-                       rows_per_batch, n_real, dump);                                                     \
+                       rows_per_batch, n_real, dump, run_flag, run_if, tmpl_r, tmpl_t);                   \
     break;
   switch (epi) {
     GWW_GEMM4_CASE(EPI_BIAS) GWW_GEMM4_CASE(EPI_GELU) GWW_GEMM4_CASE(EPI_RESID) GWW_GEMM4_CASE(EPI_CONV2)
+    GWW_GEMM4_CASE(EPI_CONV2T)
     default:
       return -1;
   }
@@ -598,7 +640,7 @@ extern "C" int gww_gemm_bf16_v4_split(const void* A, const void* W, const float*
   GWW_REQUIRE(epilogue >= 0 && epilogue <= 2, "gww_gemm_bf16_v4_split: epilogue must be 0, 1 or 2");
   GWW_REQUIRE(M % 256 == 0, "gww_gemm_bf16_v4_split: M must be a multiple of 256 (got %ld)", M);
   GWW_REQUIRE(epilogue != 2 || resid != nullptr, "gww_gemm_bf16_v4_split: residual epilogue needs resid");
-  const int rc = gww::launch_gemm_bf16_v4(A, K, W, bias, resid, C, M, N, K, epilogue, (hipStream_t)stream, n_split, nullptr, 0, 0, nullptr);
+  const int rc = gww::launch_gemm_bf16_v4(A, K, W, bias, resid, C, M, N, K, epilogue, (hipStream_t)stream, n_split, nullptr, 0, 0, nullptr, nullptr, 0, nullptr, 0);
   if (rc == -1) return gww::fail(GWW_ERR_ARG, "gww_gemm_bf16_v4_split: not a shape of the 256 x 256 x 64 kernel (N=%d K=%d)", N, K);
   return rc;
 }

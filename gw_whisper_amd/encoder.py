@@ -456,6 +456,23 @@ class WhisperEncoder(_Tracked):
         check(lib().gww_encoder_set_split(self._ensure_handle(), int(on)), "gww_encoder_set_split")
         self._ws = None
 
+    def set_stem_shortcut(self, on: bool = True):
+        """Constant-tail shortcut of the bf16 inference stem (see gww_encoder_set_stem_shortcut); on by default."""
+        check(lib().gww_encoder_set_stem_shortcut(self._ensure_handle(), int(on)), "gww_encoder_set_stem_shortcut")
+
+    def stem_shortcut_flags(self, batch: int) -> tuple:
+        """What the last inference forward of ``batch`` segments decided on the device, per half batch: 1 = shortcut
+        taken, 0 = full stem, -1 = does not apply (synchronises)."""
+        if self._ws is None:
+            raise _lib.GwwError("stem_shortcut_flags: no forward has run yet")
+        prec = {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
+        flags = (C.c_int * 2)()
+        with torch.cuda.device(self._ws.device):
+            torch.cuda.synchronize()
+            check(lib().gww_encoder_stem_shortcut_flags(self._ensure_handle(), int(batch), prec, self._ws.data_ptr(), flags),
+                  "gww_encoder_stem_shortcut_flags")
+        return int(flags[0]), int(flags[1])
+
     # ---- per-kernel event trace (bench.py roofline)
     def trace_enable(self, on: bool = True):
         check(lib().gww_encoder_trace_enable(self._ensure_handle(), int(on)), "gww_encoder_trace_enable")

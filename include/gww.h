@@ -149,6 +149,18 @@ int gww_encoder_forward_outputs(gww_encoder* enc, const float* mel, int batch, i
  * Changes gww_encoder_workspace_bytes; results are bit-identical (segments are independent). */
 int gww_encoder_set_split(gww_encoder* enc, int on);
 
+/* Constant-tail shortcut of the bf16 inference stem (on by default where it applies: 80 mels, d = 384 / 512 / 768 /
+ * 1024, t_in = 3000).  The log-mel of a short segment zero-padded to 30 s is one constant per mel bin behind its live
+ * frames; every forward tests that on the device (bitwise, frames 250 .. t_in - 1 of every mel row) and then runs the conv
+ * stem on the first 256 frames only, expanding the shared token row under the position table.  Features that do not
+ * qualify take the full stem; the choice is made per forward (per half batch with the split on) without a host
+ * synchronisation, and last_hidden / last_token are bit-identical either way.  `on` = 0 always runs the full stem.
+ * gww_encoder_stem_shortcut_flags reads back what the last forward in `workspace` (same batch and precision) decided:
+ * flags[0 .. 1] = 1 (shortcut taken), 0 (full stem) or -1 (does not apply / no second half batch).  It blocks;
+ * synchronise the forward's stream first. */
+int gww_encoder_set_stem_shortcut(gww_encoder* enc, int on);
+int gww_encoder_stem_shortcut_flags(const gww_encoder* enc, int batch, int precision, const void* workspace, int* flags);
+
 /* Optional per-kernel timing of the forward (hipEvents on the caller's stream around every
  * launch; ~30 events per forward).  Classes: gww_encoder_trace_classes() entries named by
  * gww_encoder_trace_class_name(i).  gww_encoder_trace_read sums elapsed ms and launch counts per
