@@ -132,6 +132,13 @@ __device__ __forceinline__ float dgelu_fast(float z) {
 
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
+// Byte offsets of consecutive buffers carved out of one allocation, each on a 256-byte boundary
+struct Arena {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
+  size_t total() const { return off; }
+};
+
 // Laboratory switches (kernel variants kept for A/B measurements, tuning aids): read from the environment ONLY in the
 // -DGWW_LAB build that tools/ use (make LAB=1 -> libgww_lab.so).  In the product library they are compile-time constants:
 // no environment variable changes what libgww.so computes or launches (no global mutable state).
@@ -141,30 +148,8 @@ long lab_int(const char* name, long dflt);   // encoder.hip
 constexpr long lab_int(const char*, long dflt) { return dflt; }
 #endif
 
-// ---- kernels launched from more than one translation unit ------------------
-// (definitions in the .hip files; every launcher returns a gww status code)
-int launch_layernorm(const float* x, const float* w, const float* b, void* y, int out_bf16,
-                     long M, int d, hipStream_t s, const void* delta_bf16 = nullptr);
-int launch_layernorm_rows(const float* x, long row_stride, const float* w, const float* b, float* y,
-                          long M, int d, hipStream_t s, const void* delta_bf16 = nullptr);
-int launch_ln_fold(const float* w, const float* g, const float* bl, const float* bias, float scale, int N, int K,
-                   void* wp, float* u, float* cb, hipStream_t s);
-int launch_gemm_astat(const void* A, long lda, const void* delta, float* x_out, const float* ln_u,
-                      const float* ln_cb, const void* W, const float* bias, void* C, long M, int N, int K,
-                      int epi, int rows_per_batch, hipStream_t s, long c_panel_rows = 0);
-int launch_cast_f32_bf16(const float* x, void* y, long n, hipStream_t s);
-bool conv1_mel_supported(int n_mels, int d, int kpad);
-int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s,
-                     int t_stride = 0, const int* run_flag = nullptr, int run_if = 0);
 // the constant tail of a padded log-mel (stem_tail.hip): the stem on the first kStemTc frames, kStemTt compact tokens
 constexpr int kStemTc = 256, kStemTt = kStemTc / 2;
-bool stem_tail_supported(int t_in, int d);
-int launch_stem_detect(const float* mel, int* flag, long rows, int t_in, hipStream_t s);
-int launch_stem_fill(const float* xs, const float* tr, const float* pos, float* x, const int* flag, int B, int T, int d,
-                     hipStream_t s);
-int launch_pack_weight(const float* w, void* out, int out_bf16, int N, int C, int taps, int Kpad,
-                       float scale, hipStream_t s);
-int launch_scale_copy(const float* in, float* out, int n, float scale, hipStream_t s);
 
 // Batched weight preparation (elementwise.hip::k_prep_batch): the small row-wise kernels of a weight update collected
 // into one launch per dependency phase.  Ops of ONE batch must not read each other's outputs; flush() between phases.
@@ -184,7 +169,6 @@ struct PrepArgs {
   int first[kPrepMaxOps + 1];  // first workgroup of op i; first[n] = grid size
   PrepOp op[kPrepMaxOps];
 };
-int launch_prep_batch(const PrepArgs& P, hipStream_t s);
 struct PrepBatch {
   std::vector<PrepArgs> args;  // nothing is launched before flush(): a full table opens the next one
   hipStream_t s;
@@ -199,27 +183,6 @@ struct PrepBatch {
   int dora(const float* w0, const float* a, const float* b, const float* m, float scaling, int d_out, int d_in, int r,
            float* w_eff, float* norm_out);
 };
-int launch_gemm_bf16(const void* A, long lda, const void* W, const float* bias, const float* resid,
-                     const float* pos, void* C, long M, int N, int K, int epi, int rows_per_batch,
-                     hipStream_t s, int rows_padded_256 = 0);
-int launch_gemm_bf16_v4(const void* A, long lda, const void* W, const float* bias, const float* resid, void* C, long M,
-                        int N, int K, int epi, hipStream_t s, int force_split = 0, const float* pos = nullptr,
-                        int rows_per_batch = 0, int n_real = 0, float* dump = nullptr, const int* run_flag = nullptr,
-                        int run_if = 0, float* tmpl_r = nullptr, int tmpl_t = 0);
-int launch_gemm_fulln(const void* A, long lda, const void* W, const float* bias, const float* pos, void* C,
-                      long M, int N, int K, int epi, int rows_per_batch, hipStream_t s);
-int launch_gemm_f32(const float* A, long lda, const float* W, const float* bias, const float* resid,
-                    const float* pos, float* C, long M, int N, int K, int epi, int rows_per_batch,
-                    hipStream_t s);
-int launch_attention_bf16(const void* qkv, void* ctx, int B, int T, int H, hipStream_t s, float* lse = nullptr,
-                          bool last_tile_only = false, bool q_log2 = false);
-int launch_attention_w64_bf16(const void* qkv, void* ctx, int B, int T, int H, hipStream_t s, float* lse);
-bool attention_log2q_enabled();   // the inference path packs q in log2 units (attention.hip)
-int launch_attention_f32(const float* qkv, float* ctx, int B, int T, int H, hipStream_t s);
-int launch_conv1_bf16(const float* mel, const void* w_packed, const float* bias, void* out,
-                      int B, int T, int n_mels, int d, hipStream_t s);
-int launch_conv1_f32(const float* mel, const float* w_packed, const float* bias, float* out,
-                     int B, int T, int n_mels, int d, hipStream_t s);
 
 // GEMM epilogues
 enum : int {
@@ -230,3 +193,5 @@ enum : int {
 };
 
 }  // namespace gww
+
+#include "launchers.h"   // every cross-file launcher, declared once

@@ -417,14 +417,13 @@ AdapterPlan adapter_plan(long M, int d_in, int d_out, int r) {
   rs = std::min(rs, std::min(std::max(p.Mp / 32, 1L), 128L));
   p.n_rs = (int)std::max(rs, 1L);
   p.E = (long)p.RP * (d_in + d_out) + 2L * d_out;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  p.wu = take((size_t)p.RP * d_in * 2);
-  p.wv = take((size_t)p.RP * d_out * 2);
-  p.u = take((size_t)p.RP * p.Mp * 2);
-  p.v = take((size_t)p.RP * p.Mp * 2);
-  p.slab = take((size_t)p.n_rs * p.E * 4);
-  p.total = off;
+  Arena a;
+  p.wu = a.take((size_t)p.RP * d_in * 2);
+  p.wv = a.take((size_t)p.RP * d_out * 2);
+  p.u = a.take((size_t)p.RP * p.Mp * 2);
+  p.v = a.take((size_t)p.RP * p.Mp * 2);
+  p.slab = a.take((size_t)p.n_rs * p.E * 4);
+  p.total = a.total();
   return p;
 }
 }  // namespace

@@ -174,7 +174,7 @@ __global__ __launch_bounds__(256) void k_cast_f32_bf16(const float* __restrict__
   }
 }
 
-int launch_cast_f32_bf16(const float* x, void* y, long n, hipStream_t s) {
+static int launch_cast_f32_bf16(const float* x, void* y, long n, hipStream_t s) {
   if (n == 0) return GWW_OK;
   GWW_REQUIRE((((uintptr_t)x) & 15) == 0 && (((uintptr_t)y) & 7) == 0, "cast: pointers must be 16/8-byte aligned");
   long blocks = cdiv(cdiv(n, 4), 256);
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(256) void k_scale_copy(const float* __restrict__ in
   if (i < n) out[i] = in ? in[i] * scale : 0.f;
 }
 
-int launch_scale_copy(const float* in, float* out, int n, float scale, hipStream_t s) {
+static int launch_scale_copy(const float* in, float* out, int n, float scale, hipStream_t s) {
   hipLaunchKernelGGL(k_scale_copy, dim3((unsigned)cdiv(n, 256)), dim3(256), 0, s, in, out, n, scale);
   GWW_LAUNCH_CHECK();
   return GWW_OK;
@@ -276,7 +276,7 @@ __global__ __launch_bounds__(256) void k_ln_fold(const float* __restrict__ w, co
   ln_fold_body(w, g, bl, bias, scale, K, wp, u, cb, (int)blockIdx.x, red);
 }
 
-int launch_ln_fold(const float* w, const float* g, const float* bl, const float* bias, float scale, int N, int K,
+static int launch_ln_fold(const float* w, const float* g, const float* bl, const float* bias, float scale, int N, int K,
                    void* wp, float* u, float* cb, hipStream_t s) {
   hipLaunchKernelGGL(k_ln_fold, dim3((unsigned)N), dim3(256), 0, s, w, g, bl, bias, scale, K,
                      reinterpret_cast<unsigned short*>(wp), u, cb);
@@ -371,7 +371,7 @@ __global__ __launch_bounds__(256) void k_prep_batch(const PrepArgs P) {
   }
 }
 
-int launch_prep_batch(const PrepArgs& P, hipStream_t s) {
+static int launch_prep_batch(const PrepArgs& P, hipStream_t s) {
   if (P.n == 0 || P.first[P.n] == 0) return GWW_OK;
   hipLaunchKernelGGL(k_prep_batch, dim3((unsigned)P.first[P.n]), dim3(256), 0, s, P);
   GWW_LAUNCH_CHECK();

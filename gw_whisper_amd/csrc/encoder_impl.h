@@ -1,0 +1,79 @@
+// What the three host drivers of the encoder share: the handle and its packed weights (encoder.hip: create / pack /
+// inference forward, encoder_train.hip: the bf16 training step, encoder_train_f32.hip: the exact-fp32 one).
+// Internal: not installed, nothing of it is part of the C ABI.
+#pragma once
+
+#include "common.h"
+#include "epilogue.h"
+
+#include <stdlib.h>
+#include <algorithm>
+#include <vector>
+
+namespace gww {
+
+struct LayerW {
+  // bf16 panels
+  unsigned short *wqkv, *wo, *w1, *w2;
+  // fp32 panels (parity path)
+  float *wqkv32, *wo32, *w132, *w232;
+  float *bqkv, *bo, *b1, *b2, *ln1w, *ln1b, *ln2w, *ln2b;
+  float* bqkv16;   // q | k | v bias of the bf16 panels: the q part carries log2(e) like the packed bf16 q weights
+  // LayerNorm-folded panels for the A-stationary GEMMs (gain folded into W, see gemm_astat.hip)
+  unsigned short *wqkv_ln, *w1_ln;
+  unsigned short* wmlp;   // fused-MLP weight stream (d = 384): mlp_fused.hip
+  unsigned short* wqkv_st; // the folded q / k / v panel alone as a tile stream (layer 0: launch_lnqkv_fused)
+  unsigned short* wmlp_op; // the fused-MLP stream with the W_o tiles in front (inference: out_proj fused into the block)
+  float *uqkv, *cbqkv, *u1, *cb1;
+  // transposed bf16 panels [K][N] for the dX GEMMs of the training backward
+  unsigned short *wqkvT, *woT, *w1T, *w2T;
+};
+
+// conv1's K (3 taps x n_mels) padded to a multiple of 64: 256 for 80 mels, 384 for 128 (whisper-large-v3)
+constexpr int conv1_kpad(int n_mels) { return (3 * n_mels + 63) / 64 * 64; }
+
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// Rows of a row-indexed activation of M = B * T tokens: padded so that the large-M GEMMs store whole 256-row panels
+// unconditionally (rows past M are scratch); + 512 covers conv2's remapped garbage rows
+inline size_t padded_rows(size_t M) { return (M + 255) / 256 * 256 + 512; }
+
+// The head of both training arenas (caller-owned): L layer records of layer_stride bytes, x_in[l] at `x_in` inside
+// record l, and behind them x_in[L], the input of the final LayerNorm.
+struct SavedArena {
+  size_t layer_stride, x_in, total;
+  int n_layers;
+  float* x_in_at(void* saved, int l) const {
+    return (float*)((char*)saved + (l < n_layers ? (size_t)l * layer_stride + x_in : (size_t)n_layers * layer_stride));
+  }
+  const float* x_in_at(const void* saved, int l) const { return x_in_at(const_cast<void*>(saved), l); }
+};
+
+}  // namespace gww
+
+// kernel classes of one forward, for the optional per-kernel event trace (bench.py roofline)
+enum : int { TR_MEL = 0, TR_CONV1, TR_CONV2, TR_QKV, TR_ATTN, TR_OUT, TR_FC1, TR_FC2, TR_LN, TR_MLP, TR_MLPQKV, TR_LNROWS, TR_MLPFIN, TR_COUNT };
+
+struct TraceSpan { int cls; hipEvent_t a, b; };
+
+struct gww_encoder {
+  gww_enc_cfg cfg{};
+  bool ready = false;
+  bool trace = false;
+  bool stem_shortcut = true;        // the constant-tail shortcut of the bf16 inference stem (gww_encoder_set_stem_shortcut)
+  std::vector<TraceSpan> spans;     // recorded since the last read
+  std::vector<hipEvent_t> pool;     // reusable events
+  // dual-stream split: two half batches on two library-owned streams, so HBM-bound kernels of one
+  // half overlap MFMA-bound kernels of the other on different CUs
+  int split = 0;                    // 0: off, 1: on for batch >= 2 * kSplitMin
+  hipStream_t s2[2] = {nullptr, nullptr};
+  hipEvent_t ev_fork = nullptr, ev_skew = nullptr, ev_join[2] = {nullptr, nullptr};
+  char* blob = nullptr;
+  size_t blob_bytes = 0;
+  unsigned short *c1w = nullptr, *c2w = nullptr;
+  unsigned short *c1wT = nullptr, *c2wT = nullptr;   // [Kpad, d] / [3 d, d]: input-gradient GEMMs of the stem
+  float *c1w32 = nullptr, *c2w32 = nullptr;
+  float *c1b = nullptr, *c2b = nullptr, *pos = nullptr, *lnw = nullptr, *lnb = nullptr;
+  float* pos_c = nullptr;           // [kStemTt, d] positions of the compact stem: pos[0 .. Tt - 3], a zero row, pos[T - 1]
+  std::vector<gww::LayerW> layers;
+};

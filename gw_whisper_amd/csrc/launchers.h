@@ -1,0 +1,117 @@
+// Every launcher, size function and support predicate that one translation unit defines and another calls, declared
+// ONCE, default arguments included.  common.h includes this file at its end, so every .hip sees it -- the defining one
+// too: a definition whose signature drifts from its declaration, or that repeats a default, does not compile.
+// Every launcher returns a gww status code.
+#pragma once
+
+namespace gww {
+
+// ---- elementwise.hip
+int launch_layernorm(const float* x, const float* w, const float* b, void* y, int out_bf16,
+                     long M, int d, hipStream_t s, const void* delta_bf16 = nullptr);
+int launch_layernorm_rows(const float* x, long row_stride, const float* w, const float* b, float* y,
+                          long M, int d, hipStream_t s, const void* delta_bf16 = nullptr);
+int launch_pack_weight(const float* w, void* out, int out_bf16, int N, int C, int taps, int Kpad,
+                       float scale, hipStream_t s);
+
+// ---- the conv stem: conv1_mel.hip, stem_tail.hip, gemm_bf16.hip
+bool conv1_mel_supported(int n_mels, int d, int kpad);
+int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s,
+                     int t_stride = 0, const int* run_flag = nullptr, int run_if = 0);
+bool stem_tail_supported(int t_in, int d);
+int launch_stem_detect(const float* mel, int* flag, long rows, int t_in, hipStream_t s);
+int launch_stem_fill(const float* xs, const float* tr, const float* pos, float* x, const int* flag, int B, int T, int d,
+                     hipStream_t s);
+int launch_mel_to_tokens(const float* mel, void* out, int out_bf16, int B, int C, int T, hipStream_t s);
+
+// ---- GEMMs: gemm_astat.hip, gemm_bf16.hip, gemm_v4.hip, gemm_fulln.hip, gemm_f32.hip
+int launch_gemm_astat(const void* A, long lda, const void* delta, float* x_out, const float* ln_u,
+                      const float* ln_cb, const void* W, const float* bias, void* C, long M, int N, int K,
+                      int epi, int rows_per_batch, hipStream_t s, long c_panel_rows = 0);
+int launch_gemm_bf16(const void* A, long lda, const void* W, const float* bias, const float* resid,
+                     const float* pos, void* C, long M, int N, int K, int epi, int rows_per_batch,
+                     hipStream_t s, int rows_padded_256 = 0);
+int launch_gemm_bf16_v4(const void* A, long lda, const void* W, const float* bias, const float* resid, void* C, long M,
+                        int N, int K, int epi, hipStream_t s, int force_split = 0, const float* pos = nullptr,
+                        int rows_per_batch = 0, int n_real = 0, float* dump = nullptr, const int* run_flag = nullptr,
+                        int run_if = 0, float* tmpl_r = nullptr, int tmpl_t = 0);
+int launch_gemm_fulln(const void* A, long lda, const void* W, const float* bias, const float* pos, void* C,
+                      long M, int N, int K, int epi, int rows_per_batch, hipStream_t s);
+int launch_gemm_f32(const float* A, long lda, const float* W, const float* bias, const float* resid,
+                    const float* pos, float* C, long M, int N, int K, int epi, int rows_per_batch,
+                    hipStream_t s);
+
+// ---- attention.hip, attention_w64.hip (laboratory build), attention_probs.hip, attention_bwd.hip
+int launch_attention_bf16(const void* qkv, void* ctx, int B, int T, int H, hipStream_t s, float* lse = nullptr,
+                          bool last_tile_only = false, bool q_log2 = false);
+int launch_attention_w64_bf16(const void* qkv, void* ctx, int B, int T, int H, hipStream_t s, float* lse);
+bool attention_log2q_enabled();   // the inference path packs q in log2 units (attention.hip)
+int launch_attention_f32(const float* qkv, float* ctx, int B, int T, int H, hipStream_t s);
+int launch_attention_probs(const void* qkv, bool bf16, bool q_log2, float* probs, int B, int T, int H, hipStream_t s);
+int launch_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx, const float* lse, float* D,
+                              void* dqkv, int B, int T, int H, hipStream_t s, bool q_log2);
+
+// ---- mlp_fused.hip
+int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_folded, void* out, int d, int F, int NQ,
+                    hipStream_t s, const void* wo = nullptr);
+int launch_mlp_fused(const float* x, const void* delta, float* x_out, const float* ln_u, const float* ln_cb,
+                     const void* Wt, const float* b2, void* C, long M, int d, int F, hipStream_t s,
+                     const float* q_u = nullptr, const float* q_cb = nullptr, void* q_out = nullptr, int NQ = 0,
+                     float* x_next_out = nullptr, const float* bo = nullptr, bool keep_x_new = true);
+int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const float* ln_u, const float* ln_cb,
+                           const void* Wt, const float* b2, const float* bo, const float* lnf_w, const float* lnf_b, float* y,
+                           long M, int d, int F, hipStream_t s, bool keep_x_new = true);
+int launch_lnqkv_fused(const float* x, const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d,
+                       int NQ, hipStream_t s);
+
+// ---- the bf16 training step: train_ops.hip, dora_grads.hip, wgrad.hip
+int launch_ln_bwd(const float* x, const float* gamma, const void* dy, int dy_f32, float* dx, int accumulate,
+                  void* dx_bf16, long M, int d, hipStream_t s);
+int launch_gelu_bf16(const void* z, const void* df, void* out, long n, hipStream_t s);
+int launch_sub_f32_bf16(const float* a, const float* b, void* out, long n, hipStream_t s);
+int launch_add_delta_f32(const float* x, const void* delta_bf16, float* out, long n, hipStream_t s);
+int launch_stem_dz2(const void* dxb, const void* z2, void* out, int B, int T, int d, hipStream_t s);
+int launch_stem_dz1(const void* col, const void* z1, void* out, int B, int T, int Tin, int d, hipStream_t s);
+int launch_stem_dmel(const void* col1, float* dmel, int B, int Tin, int C, int Kp, hipStream_t s);
+int launch_ln_param_grads(const float* x, const void* dy, int dy_f32, long M, int d, float* dgamma, float* dbeta,
+                          void* workspace, size_t ws_bytes, hipStream_t s);
+size_t ln_param_grads_workspace_bytes(long M, int d);
+int launch_pos_grad(const float* dx0, float* dpos, int B, int T, int d, hipStream_t s);
+int launch_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                      float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                      const float* nrm, float* dA, float* dB, float* dm, long M, int d, int r, hipStream_t s,
+                      void* scratch = nullptr, size_t scratch_bytes = 0);
+int launch_dora_grads_multi(const void* X, long ldx, const void* dY, const void* Y, long ldy, int np,
+                            const long* col_off, const float* const* bias_st, const float* yscale,
+                            const float* scaling, const float* const* A, const float* const* Bm,
+                            const float* const* mag, const float* const* nrm, float* const* dA, float* const* dB,
+                            float* const* dm, long M, int d, hipStream_t s, void* scratch, size_t scratch_bytes);
+size_t dora_grads_scratch_bytes(int np, int d);
+int launch_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
+                         float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                         const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                         hipStream_t s, void* scratch, size_t scratch_bytes);
+size_t adapter_grads_scratch_bytes(long M, int d_in, int d_out, int r);
+int launch_wgrad(const void* dY, long ldy, const void* X, long ldx, long M, int N, int K, float alpha, float* dW,
+                 float* db, int conv_cin, void* workspace, size_t ws_bytes, hipStream_t s);
+size_t wgrad_workspace_bytes(long M, int N, int K);
+
+// ---- the exact-fp32 training step: attention.hip, attention_bwd_f32.hip, train_f32.hip
+int launch_attention_lse_f32(const float* qkv, float* ctx, float* lse, int B, int T, int H, bool last_tile_only,
+                             hipStream_t s);
+int launch_attention_bwd_f32(const float* qkv, const float* ctx, const float* dctx, const float* lse, float* scratch,
+                             float* dqkv, int B, int T, int H, hipStream_t s);
+size_t attention_bwd_f32_scratch_words(int B, int T, int H);
+int launch_gemm_f32_dx(const float* A, long lda, const float* W, float* C, long ldc, long M, int N, int K, hipStream_t s);
+int launch_adapter_grads_f32(const float* X, long ldx, const float* dY, const float* Y, long ldy, const float* bias,
+                             float yscale, float scaling, const float* A, const float* Bm, const float* mag,
+                             const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
+                             hipStream_t s, void* scratch, size_t scratch_bytes);
+size_t adapter_grads_f32_scratch_bytes(long M, int d_in, int d_out, int r);
+int launch_gelu_f32(const float* z, const float* g, float* out, long n, hipStream_t s);
+int launch_sub_f32(const float* a, const float* b, float* out, long n, hipStream_t s);
+int launch_stem_dz2_f32(const float* dx0, const float* z2, float* out, int B, int T, int d, hipStream_t s);
+int launch_stem_dz1_f32(const float* col, const float* z1, float* out, int B, int T, int Tin, int d, hipStream_t s);
+int launch_stem_dmel_f32(const float* col1, float* dmel, int B, int Tin, int C, int Kp, hipStream_t s);
+
+}  // namespace gww

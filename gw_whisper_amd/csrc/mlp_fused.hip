@@ -1754,7 +1754,7 @@ int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_fold
 int launch_mlp_fused(const float* x, const void* delta, float* x_out, const float* ln_u, const float* ln_cb,
                      const void* Wt, const float* b2, void* C, long M, int d, int F, hipStream_t s,
                      const float* q_u, const float* q_cb, void* q_out, int NQ, float* x_next_out, const float* bo,
-                     bool keep_x_new = true) {
+                     bool keep_x_new) {
   GWW_REQUIRE(x && delta && x_out && ln_u && ln_cb && Wt && b2, "mlp_fused: NULL operand");
   GWW_REQUIRE(d == MF_D, "mlp_fused: built for d_model = 384 (got %d)", d);
   GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused: ffn = %d must be a multiple of 128, <= 1536", F);
@@ -1796,7 +1796,7 @@ int launch_mlp_fused(const float* x, const void* delta, float* x_out, const floa
 // != x, != y) receives the block's intermediate residual stream.  Wt = launch_mlp_pack(w1_folded, w2, NULL, ., wo).
 int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const float* ln_u, const float* ln_cb,
                            const void* Wt, const float* b2, const float* bo, const float* lnf_w, const float* lnf_b, float* y,
-                           long M, int d, int F, hipStream_t s, bool keep_x_new = true) {
+                           long M, int d, int F, hipStream_t s, bool keep_x_new) {
   GWW_REQUIRE(x && ctx && x_mid && ln_u && ln_cb && Wt && b2 && bo && lnf_w && lnf_b && y, "mlp_fused_final: NULL operand");
   GWW_REQUIRE(d == MF_D, "mlp_fused_final: built for d_model = 384 (got %d)", d);
   GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused_final: ffn = %d must be a multiple of 128, <= 1536", F);

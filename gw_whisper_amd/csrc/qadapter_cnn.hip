@@ -524,16 +524,15 @@ struct QcnnPacked {   // offsets (bytes) into the packed blob
 };
 QcnnPacked qcnn_layout(int c1, int c2, int c3) {
   QcnnPacked p{};
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 255) / 256 * 256; return at; };
-  p.w1 = take((size_t)c1 * 9 * 4);
-  p.b1 = take((size_t)c1 * 4);
-  p.w2 = take((size_t)(c2 / 32) * 9 * (c1 / 16) * 2 * 1024);
-  p.b2 = take((size_t)c2 * 4);
-  p.w3 = take((size_t)(c3 / 32) * 9 * (c2 / 16) * 2 * 1024);
-  p.b3 = take((size_t)c3 * 4);
-  p.w4 = take((size_t)(c3 + 1) * 4);   // w4 [c3] followed by b4
-  p.total = o;
+  Arena a;
+  p.w1 = a.take((size_t)c1 * 9 * 4);
+  p.b1 = a.take((size_t)c1 * 4);
+  p.w2 = a.take((size_t)(c2 / 32) * 9 * (c1 / 16) * 2 * 1024);
+  p.b2 = a.take((size_t)c2 * 4);
+  p.w3 = a.take((size_t)(c3 / 32) * 9 * (c2 / 16) * 2 * 1024);
+  p.b3 = a.take((size_t)c3 * 4);
+  p.w4 = a.take((size_t)(c3 + 1) * 4);   // w4 [c3] followed by b4
+  p.total = a.total();
   return p;
 }
 bool qcnn_supported(int c1, int c2, int c3) {
@@ -622,20 +621,19 @@ struct QcnnBwdWs {
 };
 QcnnBwdWs qcnn_bwd_layout(int B, int H, int W, int c1, int c2, int c3) {
   QcnnBwdWs w{};
-  size_t o = 0;
-  auto take = [&](size_t n) { size_t at = o; o += (n + 255) / 256 * 256; return at; };
+  Arena a;
   const size_t p1 = (size_t)B * (H / 2) * (W / 2), p2 = (size_t)B * (H / 4) * (W / 4);
   const int c1p = c1 < 32 ? 32 : c1, c2p = c2 < 32 ? 32 : c2;
-  w.a1 = take(p1 * c1 * 4);
-  w.a2 = take(p2 * c2 * 4);
-  w.dz3 = take(p2 * c3 * 4);
-  w.rz3 = take(p2 * c3 * 4);
-  w.da2 = take(p2 * c2 * 4);
-  w.dz2 = take(p1 * c2 * 4);
-  w.da1 = take(p1 * c1 * 4);
-  w.w3t = take((size_t)(c2p / 32) * 9 * (c3 / 16) * 2 * 1024);
-  w.w2t = take((size_t)(c1p / 32) * 9 * (c2 / 16) * 2 * 1024);
-  w.total = o;
+  w.a1 = a.take(p1 * c1 * 4);
+  w.a2 = a.take(p2 * c2 * 4);
+  w.dz3 = a.take(p2 * c3 * 4);
+  w.rz3 = a.take(p2 * c3 * 4);
+  w.da2 = a.take(p2 * c2 * 4);
+  w.dz2 = a.take(p1 * c2 * 4);
+  w.da1 = a.take(p1 * c1 * 4);
+  w.w3t = a.take((size_t)(c2p / 32) * 9 * (c3 / 16) * 2 * 1024);
+  w.w2t = a.take((size_t)(c1p / 32) * 9 * (c2 / 16) * 2 * 1024);
+  w.total = a.total();
   return w;
 }
 }  // namespace

@@ -1,4 +1,4 @@
-// Kernels of the exact-fp32 DoRA / LoRA training step (encoder.hip: gww_encoder_train_forward_f32 / _backward_f32).
+// Kernels of the exact-fp32 DoRA / LoRA training step (encoder_train_f32.hip: gww_encoder_train_forward_f32 / _backward_f32).
 // Every contraction runs on v_mfma_f32_16x16x4_f32 (bit-for-bit a k-ordered fmaf chain), every reduction in a fixed
 // order: no float atomics, two identical calls give identical bits.
 //

@@ -282,7 +282,7 @@ __global__ __launch_bounds__(256) void k_transpose_bf16(const unsigned short* __
   }
 }
 
-int launch_transpose_bf16(const void* in, void* out, int R, int Cn, hipStream_t s) {
+static int launch_transpose_bf16(const void* in, void* out, int R, int Cn, hipStream_t s) {
   dim3 grid((unsigned)cdiv(Cn, 64), (unsigned)cdiv(R, 64));
   hipLaunchKernelGGL(k_transpose_bf16, grid, dim3(256), 0, s, (const unsigned short*)in, (unsigned short*)out, R, Cn);
   GWW_LAUNCH_CHECK();
@@ -291,8 +291,8 @@ int launch_transpose_bf16(const void* in, void* out, int R, int Cn, hipStream_t 
 
 // ---------------------------------------------------------------- conv stem backward (gradient w.r.t. the mel input)
 // HF:modeling_whisper.py:618-619: x0 = gelu(conv2(gelu(conv1(mel)))) + pos.  Both convolutions run as GEMMs over
-// overlapping rows of token-major padded buffers (encoder.hip), so their input gradients are a GEMM against
-// the transposed panel ("col" rows = taps side by side) followed by a gather over the taps -- no atomics.
+// overlapping rows of token-major padded buffers (driver: encoder_train.hip; layout: the header of encoder.hip), so
+// their input gradients are a GEMM against the transposed panel ("col" rows = taps side by side) followed by a gather over the taps -- no atomics.
 __device__ __forceinline__ float gelu_grad(float z) {   // Phi(z) + z phi(z)
   return dgelu_fast(z);
 }
@@ -719,17 +719,6 @@ __global__ __launch_bounds__(256) void k_dora_grads_rb(const unsigned short* __r
     }
   }
 }
-
-int launch_dora_grads_multi(const void* X, long ldx, const void* dY, const void* Y, long ldy, int np,
-                            const long* col_off, const float* const* bias_st, const float* yscale,
-                            const float* scaling, const float* const* A, const float* const* Bm,
-                            const float* const* mag, const float* const* nrm, float* const* dA, float* const* dB,
-                            float* const* dm, long M, int d, hipStream_t s, void* scratch, size_t scratch_bytes);
-size_t dora_grads_scratch_bytes(int np, int d);
-int launch_adapter_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
-                         float yscale, float scaling, const float* A, const float* Bm, const float* mag,
-                         const float* nrm, float* dA, float* dB, float* dm, long M, int d_in, int d_out, int r,
-                         hipStream_t s, void* scratch, size_t scratch_bytes);
 
 int launch_dora_grads(const void* X, long ldx, const void* dY, const void* Y, long ldy, const float* bias_st,
                       float yscale, float scaling, const float* A, const float* Bm, const float* mag,

@@ -37,7 +37,7 @@ import torch as _torch
 
 FILLS = (0xFF, 0x7F, 0x00)
 ALIGN = 512
-PANEL_ROWS = 512            # two 256-row panels: the slack csrc/encoder.hip itself reasons in
+PANEL_ROWS = 512            # two 256-row panels: the slack csrc/encoder_impl.h (padded_rows) itself reasons in
 MIN_BAND = 1 << 20
 
 PACKAGE_MODULES = tuple("gw_whisper_amd." + m for m in

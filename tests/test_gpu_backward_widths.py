@@ -148,7 +148,7 @@ def _dora_ref(T, x, dy_st, y_st, W0, bias_st, A, Bm, m, s, ysc):
 @pytest.mark.parametrize("M", [31, 777, 3000])
 @pytest.mark.parametrize("d", [128, 384, 512, 768, 1024, 1280])
 def test_dora_grads_on_packed_qkv_sections(T, gww, d, M):
-    """``gww_dora_grads`` as encoder.hip calls it: x = LN1(h) [M, d], dy / y the q / k / v column sections (offsets 0,
+    """``gww_dora_grads`` as encoder_train.hip calls it: x = LN1(h) [M, d], dy / y the q / k / v column sections (offsets 0,
     d, 2 d) of packed [M, 3 d] dqkv / qkv with ldy = 3 d, and the q section stored in log2 units (yscale =
     0.125 log2 e).  dA / dB at the bounds of test_dora_parameter_gradients.  dm against the same sums of the stored bf16
     y: products of bf16 values are exact in fp32, so only the fp32 summation over M rows and the atomics remain --
