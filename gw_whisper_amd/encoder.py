@@ -26,6 +26,7 @@ Calling the module with CPU tensors raises -- there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 import sys
 import weakref
 from dataclasses import dataclass
@@ -88,39 +89,81 @@ class BaseModelOutput:
         return self.to_tuple()[i]
 
 
-# Structure epoch: bumped whenever a sub-module or parameter is (re)assigned on one of the encoder's own module classes -- which is
-# how adapters get attached (peft's / the shim's ``setattr(parent, leaf, wrapper)``).  The per-step host work of a training
-# forward used to walk the module tree five times (``parameters()`` / ``named_parameters()`` are recursive generators: ~0.3 ms
-# per step with the GPU idle behind the loop's per-step sync); the parameter lists are now cached per epoch and only the cheap
-# per-parameter fields (requires_grad, data_ptr, _version) are read fresh.
-_EPOCH = [0]
+# THE description of the encoder's weights (include/gww.h); every list of them in this file and in training.py derives from it.
+# One row per module of a layer, in the field order of gww_enc_layer / gww_enc_layer_grads: path below the layer, weight field,
+# bias field (k_proj has no bias), dirty bit of gww_encoder_update_weights (bit 0 q/k/v + LN1, bit 1 out_proj, bit 2 fc1 + LN2,
+# bit 3 fc2), gww_dora_target.proj of a linear layer (None: a LayerNorm).
+_LAYER = (("self_attn_layer_norm", "ln1_w", "ln1_b", 1, None),
+          ("self_attn.q_proj", "q_w", "q_b", 1, 0),
+          ("self_attn.k_proj", "k_w", None, 1, 1),
+          ("self_attn.v_proj", "v_w", "v_b", 1, 2),
+          ("self_attn.out_proj", "o_w", "o_b", 2, 3),
+          ("final_layer_norm", "ln2_w", "ln2_b", 4, None),
+          ("fc1", "fc1_w", "fc1_b", 4, 4),
+          ("fc2", "fc2_w", "fc2_b", 8, 5))
+# ... and per global module, in the field order of gww_enc_globals / gww_enc_grads: path, weight field, bias field
+_GLOBALS = (("conv1", "conv1_w", "conv1_b"), ("conv2", "conv2_w", "conv2_b"), ("embed_positions", "pos", None),
+            ("layer_norm", "ln_w", "ln_b"))
 
 
-class _Tracked(nn.Module):
-    def __setattr__(self, name, value):
-        if isinstance(value, (nn.Module, nn.Parameter)) or name in self.__dict__.get("_modules", ()) \
-                or name in self.__dict__.get("_parameters", ()):
-            _EPOCH[0] += 1
-        super().__setattr__(name, value)
-
-    def __delattr__(self, name):
-        _EPOCH[0] += 1
-        super().__delattr__(name)
-
-    def add_module(self, name, module):
-        _EPOCH[0] += 1
-        super().add_module(name, module)
-
-    def register_module(self, name, module):
-        _EPOCH[0] += 1
-        super().register_module(name, module)
-
-    def register_parameter(self, name, param):
-        _EPOCH[0] += 1
-        super().register_parameter(name, param)
+def _fields(rows):
+    """[(struct field, module path, "weight" | "bias")] of a table, in the struct's order."""
+    return [(f, r[0], attr) for r in rows for f, attr in ((r[1], "weight"), (r[2], "bias")) if f]
 
 
-class _Attention(_Tracked):
+class _ParamCache:
+    """What one walk of the module tree below an encoder found.  The per-step host work of a training forward used to walk
+    the tree five times (``parameters()`` / ``named_parameters()`` are recursive generators: ~0.3 ms per step with the GPU
+    idle behind the loop's per-step sync); the lists are kept instead, and before they are trusted ``valid()`` compares
+    every ``_modules`` / ``_parameters`` entry below the encoder with the object seen at build time (whisper-tiny with
+    DoRA on q / k / v: 260 entries, ~25 us).  Only the cheap per-parameter fields (requires_grad, data_ptr, _version) are
+    read fresh."""
+
+    def __init__(self, enc):
+        n = len(enc.layers)
+        self.named = []                                   # list(enc.named_parameters())
+        self.globals = []                                 # parameters of the weight groups: the globals' ...
+        self.layers = [([], [], [], []) for _ in range(n)]   # ... and per layer one list per dirty bit
+        group_of = {r[0]: self.globals for r in _GLOBALS}
+        group_of.update({f"layers.{i}.{r[0]}": self.layers[i][r[3].bit_length() - 1] for i in range(n) for r in _LAYER})
+        self._dicts, self._in, self._key, self._obj = [], [], [], []   # every _parameters / _modules dict, and its entries
+        seen = set()
+
+        def walk(mod, prefix, group):
+            for d in (mod._parameters, mod._modules):
+                self._dicts.append(d)
+                self._in += [d] * len(d)
+                self._key += d.keys()
+                self._obj += d.values()
+            for k, p in mod._parameters.items():
+                if p is not None:
+                    if group is not None:
+                        group.append(p)
+                    if id(p) not in seen:                 # (named_parameters() names a shared parameter once)
+                        seen.add(id(p))
+                        self.named.append((prefix + k, p))
+            for k, m in mod._modules.items():
+                if m is not None:
+                    walk(m, prefix + k + ".", group_of.get(prefix + k, group))
+
+        walk(enc, "", None)
+        self.base = [(name, p) for name, p in self.named if "lora_" not in name]
+        self.adapters = [p for name, p in self.named if "lora_" in name]
+        # the modules of the rows of _LAYER, per layer; the A matrices of the adapted ones
+        self.modules = [[layer.get_submodule(r[0]) for r in _LAYER] for layer in enc.layers]
+        self.lora_A = [p for mods in self.modules for m in mods if hasattr(m, "lora_A") for p in m.lora_A.parameters()]
+
+    def valid(self) -> bool:
+        """Every entry is the object seen at build time and none was added (flat lists: a nested loop over the modules
+        costs five times as much)."""
+        try:
+            return sum(map(len, self._dicts)) == len(self._obj) and \
+                all(map(operator.is_, map(operator.getitem, self._in, self._key), self._obj))
+        except KeyError:
+            return False
+
+
+class _Attention(nn.Module):
     def __init__(self, d):
         super().__init__()
         self.k_proj = nn.Linear(d, d, bias=False)
@@ -129,7 +172,7 @@ class _Attention(_Tracked):
         self.out_proj = nn.Linear(d, d, bias=True)
 
 
-class _EncoderLayer(_Tracked):
+class _EncoderLayer(nn.Module):
     def __init__(self, d, ffn):
         super().__init__()
         self.self_attn = _Attention(d)
@@ -150,15 +193,18 @@ _HOOKED = False
 
 
 def _post_step_sync(*_args, **_kw):
+    if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+        return   # (the sync allocates tensors and records an event: both illegal inside a graph capture)
     for enc in list(_TRAINED):
         try:
-            if enc._handle is None or not (enc._has_trainable_adapters() or enc.full_finetune):
+            if enc._handle is None:
                 continue
-            dev = enc._param_cache()[1][0][1].device
-            if dev.type != "cuda":
+            c = enc._param_cache()
+            dev = c.named[0][1].device
+            if dev.type != "cuda" or not (enc._has_trainable_adapters(c) or enc.full_finetune):
                 continue
             with torch.no_grad(), torch.cuda.device(dev):
-                enc._sync_weights()
+                enc._sync_weights(c)
         except Exception:
             pass   # (a failed early sync is not an error: the next forward syncs and reports)
 
@@ -184,7 +230,7 @@ def _bias(linear):
     return base.bias
 
 
-class WhisperEncoder(_Tracked):
+class WhisperEncoder(nn.Module):
     """Parameter container + launcher for the HIP encoder forward."""
 
     def __init__(self, config: WhisperConfig, precision: str = "bf16"):
@@ -230,7 +276,7 @@ class WhisperEncoder(_Tracked):
         return self
 
     def _has_adapters(self) -> bool:
-        return any("lora_" in n for n, _ in self._param_cache()[1])
+        return bool(self._param_cache().adapters)
 
     def save_pretrained(self, save_directory: str):
         """HF ``WhisperEncoder.save_pretrained`` layout (Signal_vs_Noise/src/train.py:196 saves a fully fine-tuned
@@ -297,97 +343,77 @@ class WhisperEncoder(_Tracked):
             self._handle = h
         return self._handle
 
-    def _param_cache(self):
-        """(all (name, parameter) pairs, parameter lists per weight group) -- rebuilt when the module structure changed."""
+    def _param_cache(self) -> _ParamCache:
+        """The parameter lists of this encoder, rebuilt by one walk of the module tree when any module or parameter below it
+        was assigned, replaced, added or removed since they were built.  Every entry into the encoder validates once and
+        hands the result down; the helpers below validate only when they are called on their own."""
         c = self.__dict__.get("_pcache")
-        if c is not None and c[0] == _EPOCH[0]:
-            return c
-        plist = lambda *mods: [p for m in mods for p in m.parameters()]
-        groups = [plist(self.conv1, self.conv2, self.embed_positions, self.layer_norm)]
-        for L in self.layers:
-            a = L.self_attn
-            groups.append((plist(a.q_proj, a.k_proj, a.v_proj, L.self_attn_layer_norm), plist(a.out_proj),
-                           plist(L.fc1, L.final_layer_norm), plist(L.fc2)))
-        c = (_EPOCH[0], list(self.named_parameters()), groups)
-        self.__dict__["_pcache"] = c
+        if c is None or not c.valid():
+            c = self.__dict__["_pcache"] = _ParamCache(self)
         return c
 
-    def _group_keys(self):
+    def _group_keys(self, c=None):
         """Change keys per weight group -- (data_ptr, version) of every parameter of the group, DoRA wrappers included:
-        globals, and per layer the four groups of gww_encoder_update_weights (bit 0 q/k/v + LN1, bit 1 out_proj, bit 2 fc1 + LN2,
-        bit 3 fc2)."""
-        groups = self._param_cache()[2]
+        globals, and per layer the four groups of gww_encoder_update_weights (the dirty bits of _LAYER)."""
+        c = self._param_cache() if c is None else c
         key = lambda ps: tuple((p.data_ptr(), p._version) for p in ps)
-        return key(groups[0]), [tuple(key(ps) for ps in g) for g in groups[1:]]
+        return key(c.globals), [tuple(key(ps) for ps in g) for g in c.layers]
 
-    def _sync_weights(self):
+    def _sync_weights(self, c=None):
         """Re-pack into the library's bf16/fp32 panels what changed since the last call (optimizer step,
         load_state_dict, DoRA update): everything the first time, afterwards only the dirty weight groups
         (a DoRA step touches the attention projections: the frozen fc1 / fc2 / stem panels are packed once)."""
-        gkey, lkeys = self._group_keys()
+        c = self._param_cache() if c is None else c
+        # The panels may have been packed on ANOTHER stream (the optimizer post-step hook runs on whatever stream
+        # optimizer.step() ran on): order this stream behind that work before anything packs into or reads a panel.
+        stream = torch.cuda.current_stream()
+        ev = self.__dict__.get("_packed_event")
+        if ev is not None and ev[0] != stream.cuda_stream:
+            stream.wait_event(ev[1])
+        gkey, lkeys = self._group_keys(c)
         old = self._packed_key
-        if old is not None and old == (gkey, lkeys):
-            # The panels may have been packed on ANOTHER stream (the optimizer post-step hook runs on whatever stream
-            # optimizer.step() ran on): order this stream behind that work once.
-            ev = self.__dict__.get("_packed_event")
-            if ev is not None and ev[0] != torch.cuda.current_stream().cuda_stream:
-                torch.cuda.current_stream().wait_event(ev[1])
+        if old == (gkey, lkeys):
             return
         full = old is None
-        g_dirty = full or old[0] != gkey
         masks = [15 if full else sum((1 << b) for b in range(4) if old[1][i][b] != lkeys[i][b])
-                 for i in range(len(self.layers))]
-        f32 = lambda t: t.detach().to(torch.float32).contiguous()
+                 for i in range(len(lkeys))]
         keep = []   # keep temporaries alive until the async packing kernels are enqueued
 
         def ptr(t):
-            t = f32(t)
+            t = t.detach().to(torch.float32).contiguous()
             keep.append(t)
             return t.data_ptr()
 
         # every DoRA-wrapped projection of a dirty group merged by one launch
-        wrapped = []
-        for L, m in zip(self.layers, masks):
-            a = L.self_attn
-            for bit, mods in ((1, (a.q_proj, a.k_proj, a.v_proj)), (2, (a.out_proj,)), (4, (L.fc1,)), (8, (L.fc2,))):
-                if m & bit:
-                    wrapped += [x for x in mods if hasattr(x, "effective_weights")]
+        wrapped = [x for mods, m in zip(c.modules, masks) for x, r in zip(mods, _LAYER)
+                   if m & r[3] and hasattr(x, "effective_weights")]
         merged = {}
         if wrapped:
             merged = {id(x): w for x, w in zip(wrapped, type(wrapped[0]).effective_weights(wrapped))}
         eff = lambda lin: merged[id(lin)] if id(lin) in merged else _effective_weight(lin)
 
         g = None
-        if g_dirty:
-            g = _lib.EncGlobals(ptr(self.conv1.weight), ptr(self.conv1.bias), ptr(self.conv2.weight),
-                                ptr(self.conv2.bias), ptr(self.embed_positions.weight), ptr(self.layer_norm.weight),
-                                ptr(self.layer_norm.bias))
-        n = len(self.layers)
+        if full or old[0] != gkey:
+            g = _lib.EncGlobals(**{f: ptr(getattr(self.get_submodule(path), attr)) for f, path, attr in _fields(_GLOBALS)})
+        n = len(lkeys)
         arr = (_lib.EncLayer * n)()
-        for i, L in enumerate(self.layers):
-            a, m = L.self_attn, masks[i]
-            z = lambda cond, fn: fn() if cond else None       # clean groups: pointers are not read
-            arr[i] = _lib.EncLayer(
-                z(m & 1, lambda: ptr(L.self_attn_layer_norm.weight)), z(m & 1, lambda: ptr(L.self_attn_layer_norm.bias)),
-                z(m & 1, lambda: ptr(eff(a.q_proj))), z(m & 1, lambda: ptr(_bias(a.q_proj))),
-                z(m & 1, lambda: ptr(eff(a.k_proj))),
-                z(m & 1, lambda: ptr(eff(a.v_proj))), z(m & 1, lambda: ptr(_bias(a.v_proj))),
-                z(m & 2, lambda: ptr(eff(a.out_proj))), z(m & 2, lambda: ptr(_bias(a.out_proj))),
-                z(m & 4, lambda: ptr(L.final_layer_norm.weight)), z(m & 4, lambda: ptr(L.final_layer_norm.bias)),
-                z(m & 4, lambda: ptr(eff(L.fc1))), z(m & 4, lambda: ptr(_bias(L.fc1))),
-                z(m & 8, lambda: ptr(eff(L.fc2))), z(m & 8, lambda: ptr(_bias(L.fc2))))
-        stream = torch.cuda.current_stream().cuda_stream
+        for lay, mods, m in zip(arr, c.modules, masks):
+            for mod, (_, w_field, b_field, bit, _) in zip(mods, _LAYER):
+                if m & bit:                                   # clean groups: pointers are not read
+                    setattr(lay, w_field, ptr(eff(mod)))
+                    if b_field:
+                        setattr(lay, b_field, ptr(_bias(mod)))
         if full:
-            check(lib().gww_encoder_set_weights(self._ensure_handle(), C.byref(g), arr, n, stream),
+            check(lib().gww_encoder_set_weights(self._ensure_handle(), C.byref(g), arr, n, stream.cuda_stream),
                   "gww_encoder_set_weights")
         else:
             dirty = (C.c_uint * n)(*masks)
             check(lib().gww_encoder_update_weights(self._ensure_handle(), C.byref(g) if g is not None else None, arr, n,
-                                                   dirty, stream), "gww_encoder_update_weights")
+                                                   dirty, stream.cuda_stream), "gww_encoder_update_weights")
         self._packed_key = (gkey, lkeys)
         ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream())
-        self.__dict__["_packed_event"] = (stream, ev)
+        ev.record(stream)
+        self.__dict__["_packed_event"] = (stream.cuda_stream, ev)
 
     def _workspace(self, batch: int, prec: int, device) -> torch.Tensor:
         need = lib().gww_encoder_workspace_bytes(self._ensure_handle(), batch, prec)
@@ -396,49 +422,56 @@ class WhisperEncoder(_Tracked):
             self._ws = torch.empty((need,), dtype=torch.uint8, device=device)
         return self._ws
 
-    def _launch_input(self, input_features: torch.Tensor):
-        """Checked fp32 contiguous input of a HIP forward and the library precision code."""
-        x = input_features
+    @property
+    def _prec(self) -> int:
+        """The library's precision code."""
+        return {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
+
+    def _enter(self, x) -> _ParamCache:
+        """Every entry into the encoder starts here: the validated parameter cache, and the input checked against it."""
+        c = self._param_cache()
         if not x.is_cuda:
             raise _lib.GwwError("WhisperEncoder.forward needs GPU tensors: gw_whisper_amd has no CPU fallback "
                                 f"(got input on {x.device})")
-        c = self.config
-        t_in = 2 * c.max_source_positions
-        if x.dim() != 3 or x.shape[1] != c.num_mel_bins or x.shape[-1] != t_in:
+        t_in = 2 * self.config.max_source_positions
+        if x.dim() != 3 or x.shape[1] != self.config.num_mel_bins or x.shape[-1] != t_in:
             raise ValueError(f"Whisper expects the mel input features to be of length {t_in}, but found "
                              f"{x.shape[-1]}. Make sure to pad the input mel features to {t_in}.")
-        if next(self.parameters()).device != x.device:
+        if c.named[0][1].device != x.device:
             raise _lib.GwwError("encoder parameters and input are on different devices")
-        x = x.to(torch.float32).contiguous()
-        return x, {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
+        return c
 
-    def forward_raw(self, input_features: torch.Tensor, want_hidden: bool = True, want_last: bool = False):
-        """Launch the HIP forward; returns (last_hidden_state | None, last_token | None)."""
-        x, prec = self._launch_input(input_features)
-        c = self.config
+    def forward_raw(self, input_features: torch.Tensor, want_hidden: bool = True, want_last: bool = False, cache=None):
+        """Launch the HIP forward; returns (last_hidden_state | None, last_token | None).  ``cache``: what ``_enter``
+        returned to a caller that has checked this input already."""
+        c = self._enter(input_features) if cache is None else cache
+        x, prec = input_features.to(torch.float32).contiguous(), self._prec
+        cfg = self.config
         B = x.shape[0]
         with torch.cuda.device(x.device):
-            self._sync_weights()
+            self._sync_weights(c)
             ws = self._workspace(B, prec, x.device)
-            hidden = torch.empty((B, c.max_source_positions, c.d_model), dtype=torch.float32,
+            hidden = torch.empty((B, cfg.max_source_positions, cfg.d_model), dtype=torch.float32,
                                  device=x.device) if want_hidden else None
-            last = torch.empty((B, c.d_model), dtype=torch.float32, device=x.device) if want_last else None
+            last = torch.empty((B, cfg.d_model), dtype=torch.float32, device=x.device) if want_last else None
             check(lib().gww_encoder_forward(self._handle, x.data_ptr(), B, prec, ws.data_ptr(), ws.numel(),
                                             hidden.data_ptr() if want_hidden else None,
                                             last.data_ptr() if want_last else None,
                                             torch.cuda.current_stream().cuda_stream), "gww_encoder_forward")
         return hidden, last
 
-    def forward_outputs_raw(self, input_features: torch.Tensor, want_hidden_states: bool, want_attentions: bool):
+    def forward_outputs_raw(self, input_features: torch.Tensor, want_hidden_states: bool, want_attentions: bool,
+                            cache=None):
         """Launch the HIP forward with HF's per-layer outputs (gww_encoder_forward_outputs); returns
         (last_hidden_state, hidden_states | None, attentions | None).  Each output is a view of one fp32 slab;
         ``hidden_states[-1]`` is ``last_hidden_state`` itself."""
-        x, prec = self._launch_input(input_features)
-        c = self.config
-        B, T, d, L, H = x.shape[0], c.max_source_positions, c.d_model, c.encoder_layers, c.encoder_attention_heads
+        c = self._enter(input_features) if cache is None else cache
+        x, prec = input_features.to(torch.float32).contiguous(), self._prec
+        cfg = self.config
+        B, T, d, L, H = x.shape[0], cfg.max_source_positions, cfg.d_model, cfg.encoder_layers, cfg.encoder_attention_heads
         f32 = dict(dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            self._sync_weights()
+            self._sync_weights(c)
             ws = self._workspace(B, prec, x.device)
             hs = torch.empty((L + 1, B, T, d), **f32) if want_hidden_states else None
             last = hs[L] if want_hidden_states else torch.empty((B, T, d), **f32)
@@ -465,11 +498,10 @@ class WhisperEncoder(_Tracked):
         taken, 0 = full stem, -1 = does not apply (synchronises)."""
         if self._ws is None:
             raise _lib.GwwError("stem_shortcut_flags: no forward has run yet")
-        prec = {"bf16": _lib.PREC_BF16, "fp32": _lib.PREC_F32}[self.precision]
         flags = (C.c_int * 2)()
         with torch.cuda.device(self._ws.device):
             torch.cuda.synchronize()
-            check(lib().gww_encoder_stem_shortcut_flags(self._ensure_handle(), int(batch), prec, self._ws.data_ptr(), flags),
+            check(lib().gww_encoder_stem_shortcut_flags(self._ensure_handle(), int(batch), self._prec, self._ws.data_ptr(), flags),
                   "gww_encoder_stem_shortcut_flags")
         return int(flags[0]), int(flags[1])
 
@@ -494,68 +526,55 @@ class WhisperEncoder(_Tracked):
         want_h = c.output_hidden_states if output_hidden_states is None else bool(output_hidden_states)
         want_a = c.output_attentions if output_attentions is None else bool(output_attentions)
         as_dict = c.return_dict if return_dict is None else bool(return_dict)
-        self._check_input(input_features)
-        if self._wants_grad(input_features):
+        cache = self._enter(input_features)
+        if self._wants_grad(input_features, cache):
             if want_h or want_a:
                 raise _lib.GwwError("WhisperEncoder: output_hidden_states / output_attentions are inference only (no "
                                     "gradient flows through them): run under torch.no_grad() or freeze the adapters")
             # DoRA training step: HIP forward that keeps activations + HIP backward (training.py)
             from .training import encoder_train_forward
-            out = BaseModelOutput(last_hidden_state=encoder_train_forward(self, input_features))
+            out = BaseModelOutput(last_hidden_state=encoder_train_forward(self, input_features, cache=cache))
         elif want_h or want_a:
-            last, hs, at = self.forward_outputs_raw(input_features, want_h, want_a)
+            last, hs, at = self.forward_outputs_raw(input_features, want_h, want_a, cache=cache)
             out = BaseModelOutput(last_hidden_state=last, hidden_states=hs, attentions=at)
         else:
-            hidden, _ = self.forward_raw(input_features, want_hidden=True, want_last=False)
+            hidden, _ = self.forward_raw(input_features, want_hidden=True, want_last=False, cache=cache)
             out = BaseModelOutput(last_hidden_state=hidden)
         return out if as_dict else out.to_tuple()
 
-    def _wants_grad(self, input_features) -> bool:
+    def _wants_grad(self, input_features, c=None) -> bool:
         if not torch.is_grad_enabled():
             return False
         # Only the frozen-base + DoRA backward exists (and the input gradient).  A base parameter that was un-frozen on
         # purpose -- the reference's `full_finetune` method, Signal_vs_Noise/src/train.py:244-250 -- would silently get no
-        # gradient: refuse.  (Cheap path first: nothing trainable at all is the inference case.)
-        named = self._param_cache()[1]
-        if not any(p.requires_grad for _, p in named):
-            return torch.is_tensor(input_features) and input_features.requires_grad
-        base_trainable = [n for n, p in named if p.requires_grad and "lora_" not in n]
+        # gradient: refuse.  (Nothing trainable at all is the inference case.)
+        c = self._param_cache() if c is None else c
+        input_grad = torch.is_tensor(input_features) and input_features.requires_grad
+        base_trainable = [n for n, p in c.base if p.requires_grad]
+        if not base_trainable and not any(p.requires_grad for p in c.adapters):
+            return input_grad
         if self.full_finetune:
-            if self._has_adapters():
+            if c.adapters:
                 raise _lib.GwwError("WhisperEncoder: full fine-tuning is enabled and DoRA / LoRA adapters are attached: "
                                     "the two do not combine")
-            return bool(base_trainable) or (torch.is_tensor(input_features) and input_features.requires_grad)
+            return True   # (no adapters, so a base parameter trains)
         if base_trainable:
             raise _lib.GwwError(
                 "WhisperEncoder: autograd is on and base parameters require grad (e.g. " + base_trainable[0] + "): only "
                 "the frozen-base + DoRA training step (and the input gradient) is implemented -- freeze the encoder "
                 "(get_peft_model does) or run under torch.no_grad()")
-        return self._has_trainable_adapters() or (torch.is_tensor(input_features) and input_features.requires_grad)
+        return self._has_trainable_adapters(c) or input_grad
 
-    def _has_trainable_adapters(self) -> bool:
-        for layer in self.layers:
-            mods = [getattr(layer.self_attn, n) for n in ("q_proj", "k_proj", "v_proj", "out_proj")] + [layer.fc1, layer.fc2]
-            for mod in mods:
-                if hasattr(mod, "lora_A") and any(p.requires_grad for p in mod.lora_A.parameters()):
-                    return True
-        return False
-
-    def _check_input(self, x):
-        c = self.config
-        t_in = 2 * c.max_source_positions
-        if not x.is_cuda:
-            raise _lib.GwwError("WhisperEncoder.forward needs GPU tensors: gw_whisper_amd has no CPU fallback "
-                                f"(got input on {x.device})")
-        if x.dim() != 3 or x.shape[1] != c.num_mel_bins or x.shape[-1] != t_in:
-            raise ValueError(f"Whisper expects the mel input features to be of length {t_in}, but found "
-                             f"{x.shape[-1]}. Make sure to pad the input mel features to {t_in}.")
+    def _has_trainable_adapters(self, c=None) -> bool:
+        """Whether an adapter on one of the linear layers of _LAYER trains (its A matrix requires grad)."""
+        return any(p.requires_grad for p in (self._param_cache() if c is None else c).lora_A)
 
     def last_token(self, input_features) -> torch.Tensor:
         """``self(mel).last_hidden_state[:, -1, :]`` without materialising the other
         1499 rows of the final LayerNorm (reference ``src/model.py:25-26``).  Differentiable: with trainable
         adapters (or an input that requires grad) this is the pooled training step of ``training.py``."""
-        self._check_input(input_features)
-        if self._wants_grad(input_features):
+        cache = self._enter(input_features)
+        if self._wants_grad(input_features, cache):
             from .training import encoder_train_forward
-            return encoder_train_forward(self, input_features, pooled=True)
-        return self.forward_raw(input_features, want_hidden=False, want_last=True)[1]
+            return encoder_train_forward(self, input_features, pooled=True, cache=cache)
+        return self.forward_raw(input_features, want_hidden=False, want_last=True, cache=cache)[1]

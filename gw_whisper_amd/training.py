@@ -29,90 +29,78 @@ from . import encoder as _encoder
 from ._lib import check, lib
 from .peft import DoraLinear
 
-_PROJ = {"q_proj": 0, "k_proj": 1, "v_proj": 2, "out_proj": 3}
-_MLP = {"fc1": 4, "fc2": 5}   # gww_dora_target.proj of the MLP projections (include/gww.h)
 
-
-# base parameters in the order of gww_enc_grads / gww_enc_layer_grads (include/gww.h)
-_GLOBAL_GRADS = (("conv1_w", "conv1.weight"), ("conv1_b", "conv1.bias"), ("conv2_w", "conv2.weight"),
-                 ("conv2_b", "conv2.bias"), ("pos", "embed_positions.weight"), ("ln_w", "layer_norm.weight"),
-                 ("ln_b", "layer_norm.bias"))
-_LAYER_GRADS = (("ln1_w", "self_attn_layer_norm.weight"), ("ln1_b", "self_attn_layer_norm.bias"),
-                ("q_w", "self_attn.q_proj.weight"), ("q_b", "self_attn.q_proj.bias"), ("k_w", "self_attn.k_proj.weight"),
-                ("v_w", "self_attn.v_proj.weight"), ("v_b", "self_attn.v_proj.bias"),
-                ("o_w", "self_attn.out_proj.weight"), ("o_b", "self_attn.out_proj.bias"),
-                ("ln2_w", "final_layer_norm.weight"), ("ln2_b", "final_layer_norm.bias"),
-                ("fc1_w", "fc1.weight"), ("fc1_b", "fc1.bias"), ("fc2_w", "fc2.weight"), ("fc2_b", "fc2.bias"))
-
-
-def base_targets(encoder):
-    """[(field, layer index or None, parameter)] of the trainable base parameters (full fine-tuning only)."""
+def base_targets(encoder, cache=None):
+    """[(field, layer index or None, parameter)] of the trainable base parameters (full fine-tuning only), in the field
+    order of gww_enc_grads / gww_enc_layer_grads (encoder._GLOBALS / _LAYER)."""
     if not encoder.full_finetune:
         return []
-    out = []
-    get = lambda mod, path: mod.get_parameter(path)
-    for field, path in _GLOBAL_GRADS:
-        p = get(encoder, path)
-        if p.requires_grad:
-            out.append((field, None, p))
-    for li, layer in enumerate(encoder.layers):
-        for field, path in _LAYER_GRADS:
-            p = get(layer, path)
-            if p.requires_grad:
-                out.append((field, li, p))
-    return out
+    c = cache or encoder._param_cache()
+    out = [(f, None, getattr(encoder.get_submodule(path), attr)) for f, path, attr in _encoder._fields(_encoder._GLOBALS)]
+    for li, mods in enumerate(c.modules):
+        for mod, (_, w_field, b_field, _, _) in zip(mods, _encoder._LAYER):
+            out += [(w_field, li, mod.weight)] + ([(b_field, li, mod.bias)] if b_field else [])
+    return [t for t in out if t[2].requires_grad]
 
 
-def dora_targets(encoder):
-    """[(layer index, proj id, DoraLinear)] of the adapted linear layers: q / k / v / out_proj (0..3), fc1 / fc2 (4, 5)."""
-    out = []
-    for li, layer in enumerate(encoder.layers):
-        mods = [(getattr(layer.self_attn, name), pid) for name, pid in _PROJ.items()]
-        mods += [(getattr(layer, name), pid) for name, pid in _MLP.items()]
-        for mod, pid in mods:
-            if isinstance(mod, DoraLinear):
-                out.append((li, pid, mod))   # use_dora=False (plain LoRA, the reference's --method LoRA) included
-    return out
+def dora_targets(encoder, cache=None):
+    """[(layer index, proj id, DoraLinear)] of the adapted linear layers, layer-major and by proj id: q / k / v / out_proj
+    (0..3), fc1 / fc2 (4, 5)."""
+    c = cache or encoder._param_cache()
+    # (use_dora=False, plain LoRA, the reference's --method LoRA, included)
+    return [(li, r[4], mod) for li, mods in enumerate(c.modules) for mod, r in zip(mods, _encoder._LAYER)
+            if r[4] is not None and isinstance(mod, DoraLinear)]
+
+
+class _Plan:
+    """What one training step runs, decided once per forward from (precision, base targets, wide adapter targets): the
+    targets, the autograd inputs in the order the backward returns their gradients, the workspace query, the backward."""
+
+    def __init__(self, enc, cache):
+        self.cache, self.targets, self.base = cache, dora_targets(enc, cache), base_targets(enc, cache)
+        self.f32 = enc.precision == "fp32"   # the exact-fp32 step (gww_encoder_train_forward_f32): its own arena sizes
+        if self.f32 and self.base:           # (enable_full_finetune refuses fp32 already)
+            raise _lib.GwwError("full fine-tuning is implemented for precision='bf16'")
+        # fc1 / fc2 targets or ranks other than 8 run on the adapter-gradient kernel, whose scratch the attention-only
+        # rank-8 step does not need
+        wide = [t[2].r for t in self.targets if t[1] > 3 or t[2].r != 8]
+        kind = "_f32" if self.f32 else "_full" if self.base else ""
+        self.backward = "gww_encoder_train_backward" + kind
+        if kind or not wide:
+            self.ws_query, self.ws_args = "gww_train_workspace_bytes" + kind, ()
+        else:
+            self.ws_query, self.ws_args = "gww_train_workspace_bytes_adapters", (max(wide),)
+        self.params = []
+        for _, _, mod in self.targets:
+            self.params += [mod.lora_A[mod.adapter].weight, mod.lora_B[mod.adapter].weight]
+            if mod.use_dora:
+                self.params.append(mod.lora_magnitude_vector[mod.adapter].weight)
+        self.params += [p for _, _, p in self.base]   # full fine-tuning (enable_full_finetune)
 
 
 class _EncoderTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, encoder, mel, pooled, *params):
+    def forward(ctx, encoder, mel, pooled, plan, *params):
         enc = encoder
         c = enc.config
         x = mel.to(torch.float32).contiguous()
         B = x.shape[0]
         dev = x.device
+        sfx = "_f32" if plan.f32 else ""
         with torch.cuda.device(dev):
-            enc._sync_weights()
+            enc._sync_weights(plan.cache)
             _encoder._note_training(enc)   # from now on the packed weights follow every optimizer step at once
             h = enc._ensure_handle()
-            f32 = enc.precision == "fp32"   # the exact-fp32 step (gww_encoder_train_forward_f32): its own arena sizes
-            full = bool(base_targets(enc))
-            # fc1 / fc2 targets or ranks other than 8 run on the adapter-gradient kernel, whose scratch the attention-only
-            # rank-8 step does not need
-            wide = [t for t in dora_targets(enc) if t[1] > 3 or t[2].r != 8]
-            if f32:
-                ws_bytes = lib().gww_train_workspace_bytes_f32(h, B)
-            elif full:
-                ws_bytes = lib().gww_train_workspace_bytes_full(h, B)
-            elif wide:
-                ws_bytes = lib().gww_train_workspace_bytes_adapters(h, B, max(t[2].r for t in wide))
-            else:
-                ws_bytes = lib().gww_train_workspace_bytes(h, B)
-            ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-            saved_bytes = lib().gww_train_saved_bytes_f32(h, B) if f32 else lib().gww_train_saved_bytes(h, B)
-            saved = torch.empty((saved_bytes,), dtype=torch.uint8, device=dev)
+            ws = torch.empty((getattr(lib(), plan.ws_query)(h, B, *plan.ws_args),), dtype=torch.uint8, device=dev)
+            saved = torch.empty((getattr(lib(), "gww_train_saved_bytes" + sfx)(h, B),), dtype=torch.uint8, device=dev)
             shape = (B, c.d_model) if pooled else (B, c.max_source_positions, c.d_model)
             hidden = torch.empty(shape, dtype=torch.float32, device=dev)
-            fwd = lib().gww_encoder_train_forward_f32 if f32 else lib().gww_encoder_train_forward
-            check(fwd(h, x.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(),
-                      int(pooled), torch.cuda.current_stream().cuda_stream),
-                  "gww_encoder_train_forward" + ("_f32" if f32 else ""))
+            fwd = "gww_encoder_train_forward" + sfx
+            check(getattr(lib(), fwd)(h, x.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(),
+                                      hidden.data_ptr(), int(pooled), torch.cuda.current_stream().cuda_stream), fwd)
         # the backward gets THIS workspace back: d_mel and the conv-stem gradients are formed from what the forward left
         # at its front (include/gww.h); everything else in it is scratch
-        ctx.enc, ctx.B, ctx.ws, ctx.saved, ctx.pooled = enc, B, ws, saved, bool(pooled)
-        ctx.n_params = len(params)
+        ctx.enc, ctx.B, ctx.ws, ctx.saved, ctx.pooled, ctx.plan = enc, B, ws, saved, bool(pooled), plan
         ctx.mel_shape = tuple(x.shape)
         return hidden
 
@@ -121,7 +109,7 @@ class _EncoderTrain(torch.autograd.Function):
         enc, B = ctx.enc, ctx.B
         dev = d_hidden.device
         d_hidden = d_hidden.to(torch.float32).contiguous()
-        targets = dora_targets(enc)
+        targets, base = ctx.plan.targets, ctx.plan.base
         arr = (_lib.DoraTarget * max(len(targets), 1))()
         grads, keep = [], []
         def grad_buffer(param, like):
@@ -157,7 +145,6 @@ class _EncoderTrain(torch.autograd.Function):
                                      nrm.data_ptr(), dA.data_ptr(), dB.data_ptr(), dm.data_ptr())
         # gradient w.r.t. the input features (conv stem backward) only when autograd asks for it
         d_mel = torch.empty(ctx.mel_shape, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
-        base = base_targets(enc)
         base_ret = []
         if base:
             gl = _lib.EncGrads()
@@ -172,35 +159,24 @@ class _EncoderTrain(torch.autograd.Function):
             args = (enc._ensure_handle(), B, ctx.ws.data_ptr(), ctx.ws.numel(), ctx.saved.data_ptr(), ctx.saved.numel(),
                     d_hidden.data_ptr(), arr, len(targets), None, d_mel.data_ptr() if d_mel is not None else None,
                     int(ctx.pooled))
-            stream = torch.cuda.current_stream().cuda_stream
-            if enc.precision == "fp32":
-                check(lib().gww_encoder_train_backward_f32(*args, stream), "gww_encoder_train_backward_f32")
-            elif base:
-                check(lib().gww_encoder_train_backward_full(*args, C.byref(gl), stream), "gww_encoder_train_backward_full")
-            else:
-                check(lib().gww_encoder_train_backward(*args, stream), "gww_encoder_train_backward")
+            if base:
+                args += (C.byref(gl),)
+            check(getattr(lib(), ctx.plan.backward)(*args, torch.cuda.current_stream().cuda_stream), ctx.plan.backward)
         flat = []
         for g in grads:
             flat += list(g)
         flat += base_ret
-        assert len(flat) == ctx.n_params
+        assert len(flat) == len(ctx.plan.params)
         ctx.ws = ctx.saved = None
-        return (None, d_mel, None, *flat)
+        return (None, d_mel, None, None, *flat)
 
 
-def encoder_train_forward(encoder, mel: torch.Tensor, pooled: bool = False) -> torch.Tensor:
+def encoder_train_forward(encoder, mel: torch.Tensor, pooled: bool = False, cache=None) -> torch.Tensor:
     """last_hidden_state [B, 1500, d] -- or, with ``pooled``, its last token [B, d] (what every classifier of the
     reference reads, ``Signal_vs_Noise/src/model.py:25-26``; the last layer's row-wise ops and their backward then run
     on B rows instead of B * 1500) -- with autograd through the DoRA parameters and, when ``mel.requires_grad``,
-    through the conv stem to the input features."""
+    through the conv stem to the input features.  ``cache``: the encoder's parameter cache, when the caller validated it."""
     if encoder.precision not in ("bf16", "fp32"):
         raise _lib.GwwError(f"no training step for precision={encoder.precision!r}")
-    if encoder.precision == "fp32" and base_targets(encoder):   # (enable_full_finetune refuses fp32 already)
-        raise _lib.GwwError("full fine-tuning is implemented for precision='bf16'")
-    params = []
-    for _, _, mod in dora_targets(encoder):
-        params += [mod.lora_A[mod.adapter].weight, mod.lora_B[mod.adapter].weight]
-        if mod.use_dora:
-            params.append(mod.lora_magnitude_vector[mod.adapter].weight)
-    params += [p for _, _, p in base_targets(encoder)]   # full fine-tuning (enable_full_finetune)
-    return _EncoderTrain.apply(encoder, mel, bool(pooled), *params)
+    plan = _Plan(encoder, cache or encoder._param_cache())
+    return _EncoderTrain.apply(encoder, mel, bool(pooled), plan, *plan.params)

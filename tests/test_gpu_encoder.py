@@ -332,3 +332,29 @@ def test_tiny_batch_256_rows_equal_the_batch_64_rows(T, gww, golden):
     print(f"B = 256: max |last_token[:64] - HF golden| = {err:.3e}")
     assert err < 8e-2
     assert (pooled - big_l).abs().max().item() < 2e-2
+
+
+@pytest.mark.parametrize("mutation", ["leaf_parameter", "load_state_dict_assign", "replaced_layer"])
+def test_reassigned_weights_reach_the_packed_panels(T, gww, mutation):
+    """Weights re-assigned below the encoder's own module classes, after a forward has packed the panels and filled the
+    parameter cache: the next forward runs on the new weights -- bit for bit the output of a freshly built encoder with
+    the resulting state dict (same kernels, same inputs, no float atomics on the inference path) -- and not on the old."""
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    cfg = WhisperConfig(128, 2, 2, 512)
+    enc, other = (WhisperEncoder.from_numpy_state_dict(synth.encoder_state_dict(128, 2, 2, 512, seed=s), cfg,
+                                                       precision="bf16").cuda() for s in (3, 4))
+    mel = T.from_numpy(olm.log_mel(synth.strain_segments(2, seed=9))).cuda()
+    with T.no_grad():
+        first = enc(mel).last_hidden_state
+        if mutation == "leaf_parameter":
+            enc.layers[0].fc1.weight = T.nn.Parameter(other.layers[0].fc1.weight.detach().clone(), requires_grad=False)
+        elif mutation == "load_state_dict_assign":
+            enc.load_state_dict({k: v.clone() for k, v in other.state_dict().items()}, assign=True)
+        else:
+            enc.layers[1] = other.layers[1]
+        second = enc(mel).last_hidden_state
+        fresh = WhisperEncoder(cfg, precision="bf16")
+        fresh.load_state_dict({k: v.cpu() for k, v in enc.state_dict().items()})
+        expect = fresh.cuda()(mel).last_hidden_state
+    assert T.equal(second, expect)
+    assert not T.equal(second, first)

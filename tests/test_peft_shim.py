@@ -163,12 +163,13 @@ def test_datasets_directory_round_trip_through_the_harness_loader(tmp_path):
 
 
 def test_cached_parameter_lists_follow_the_module_structure():
-    """The encoder caches its parameter lists per structure epoch (encoder._EPOCH: the per-step host work of a training forward
-    used to walk the module tree five times).  Attaching adapters, replacing a sub-module or re-assigning a parameter must
-    invalidate the cache; requires_grad, data_ptr and _version are always read fresh."""
-    from gw_whisper_amd import encoder as E, _lib
+    """The encoder caches its parameter lists and validates the cache against the live module tree by identity before it
+    trusts it (the per-step host work of a training forward used to walk the module tree five times).  Attaching adapters,
+    replacing a sub-module or re-assigning a parameter must rebuild the cache; requires_grad, data_ptr and _version are
+    always read fresh."""
+    from gw_whisper_amd import _lib
     enc = WhisperEncoder(WhisperConfig(d_model=128, encoder_layers=2, encoder_attention_heads=2, encoder_ffn_dim=256))
-    named0 = enc._param_cache()[1]
+    named0 = enc._param_cache().named
     assert [n for n, _ in named0] == [n for n, _ in enc.named_parameters()]
     assert enc._param_cache() is enc._param_cache()                    # cached while nothing changes
     g0, l0 = enc._group_keys()
@@ -178,7 +179,7 @@ def test_cached_parameter_lists_follow_the_module_structure():
     assert g1 == g0 and l1[0] == l0[0] and l1[1][2] != l0[1][2] and l1[1][0] == l0[1][0]
     targets = _targets(enc, ["layers.*.self_attn.q_proj", "layers.*.self_attn.v_proj"])
     peft = get_peft_model(enc, LoraConfig(use_dora=True, r=4, lora_alpha=8, target_modules=targets))
-    names = [n for n, _ in enc._param_cache()[1]]
+    names = [n for n, _ in enc._param_cache().named]
     assert names == [n for n, _ in enc.named_parameters()] and any("lora_A" in n for n in names)
     assert len(enc._group_keys()[1][0][0]) > len(l0[0][0])              # the wrappers' parameters joined the q/k/v group
     for n, p in peft.named_parameters():
@@ -191,7 +192,136 @@ def test_cached_parameter_lists_follow_the_module_structure():
     with pytest.raises(_lib.GwwError):
         enc._wants_grad(x)
     enc.layers[0].fc2.weight.requires_grad = False
-    e = E._EPOCH[0]
-    enc.layers[0].fc2 = torch.nn.Linear(256, 128)                       # a replaced sub-module: new epoch, new lists
-    assert E._EPOCH[0] > e and enc._param_cache()[1][0][1] is not None
-    assert any(p is enc.layers[0].fc2.weight for _, p in enc._param_cache()[1])
+    before = enc._param_cache()
+    enc.layers[0].fc2 = torch.nn.Linear(256, 128)                       # a replaced sub-module: a new cache, new lists
+    assert enc._param_cache() is not before and enc._param_cache().named[0][1] is not None
+    assert any(p is enc.layers[0].fc2.weight for _, p in enc._param_cache().named)
+
+
+# ---- the cache validates itself: changes below the encoder that no encoder class sees (each after a first _group_keys())
+
+def _small_encoder(seed=0):
+    torch.manual_seed(seed)
+    enc = WhisperEncoder(WhisperConfig(128, 2, 2, 256))
+    with torch.no_grad():
+        for p in enc.parameters():
+            p.add_(0.01 * torch.randn_like(p))
+    return enc
+
+
+def _changed(before, after):
+    """Which change keys differ: "g" for the globals, (layer, bit index) for the four groups of a layer."""
+    (g0, l0), (g1, l1) = before, after
+    assert len(l0) == len(l1) == 2
+    return ({"g"} if g0 != g1 else set()) | {(i, b) for i in range(2) for b in range(4) if l0[i][b] != l1[i][b]}
+
+
+ALL_KEYS = {"g"} | {(i, b) for i in range(2) for b in range(4)}
+
+
+def test_cache_follows_load_state_dict_assign():
+    enc, sd = _small_encoder(), _small_encoder(seed=1).state_dict()
+    k0 = enc._group_keys()
+    enc.load_state_dict(sd, assign=True)
+    live = dict(enc.named_parameters())
+    named = enc._param_cache().named
+    assert [n for n, _ in named] == list(live) and all(p is live[n] for n, p in named)
+    assert _changed(k0, enc._group_keys()) == ALL_KEYS
+
+
+def test_cache_follows_a_parameter_assigned_on_a_leaf():
+    enc = _small_encoder()
+    k0 = enc._group_keys()
+    enc.layers[0].fc1.weight = torch.nn.Parameter(torch.randn(256, 128), requires_grad=False)
+    assert _changed(k0, enc._group_keys()) == {(0, 2)}                  # layer 0, bit 2 (fc1 + LN2), and no other
+    assert any(p is enc.layers[0].fc1.weight for _, p in enc._param_cache().named)
+
+
+def test_a_trainable_base_parameter_assigned_on_a_leaf_is_refused():
+    from gw_whisper_amd import _lib
+    enc = _small_encoder()
+    enc._group_keys()
+    x = torch.zeros(1, 80, 3000)
+    assert not enc._wants_grad(x)
+    enc.layers[0].fc1.weight = torch.nn.Parameter(torch.randn(256, 128), requires_grad=True)
+    with pytest.raises(_lib.GwwError, match="base parameters require grad"):
+        enc._wants_grad(x)
+
+
+def test_cache_follows_a_replaced_layer():
+    from gw_whisper_amd import encoder as E
+    enc, layer = _small_encoder(), E._EncoderLayer(128, 256).requires_grad_(False)
+    k0 = enc._group_keys()
+    enc.layers[1] = layer
+    assert _changed(k0, enc._group_keys()) == {(1, b) for b in range(4)}   # layer 1's keys, layer 0's and the globals' not
+    assert any(p is enc.layers[1].fc2.bias for _, p in enc._param_cache().named)
+
+
+def test_cache_follows_a_second_adapter_in_a_wrapper():
+    enc = _small_encoder()
+    get_peft_model(enc, LoraConfig(use_dora=True, r=4, lora_alpha=8,
+                                   target_modules=_targets(enc, ["layers.*.self_attn.q_proj"])))
+    k0 = enc._group_keys()
+    w = enc.layers[0].self_attn.q_proj
+    w.lora_A["second"] = torch.nn.Linear(128, 4, bias=False)
+    w.lora_B["second"] = torch.nn.Linear(4, 128, bias=False)
+    live = list(enc.named_parameters())
+    named = enc._param_cache().named
+    assert [n for n, _ in named] == [n for n, _ in live] and all(p is q for (_, p), (_, q) in zip(named, live))
+    assert any("lora_A.second" in n for n, _ in named)
+    k1 = enc._group_keys()
+    assert len(k1[1][0][0]) == len(k0[1][0][0]) + 2 and len(k1[1][1][0]) == len(k0[1][1][0])
+
+
+def test_cache_is_kept_while_nothing_changes():
+    enc = _small_encoder()
+    enc._group_keys()
+    assert enc._param_cache() is enc._param_cache()
+    with torch.no_grad():
+        enc.layers[0].fc1.weight.mul_(2.0)                              # values, versions, requires_grad: not structure
+    enc.layers[0].fc1.weight.requires_grad = False
+    assert enc._param_cache() is enc._param_cache()
+
+
+def test_post_step_hook_does_nothing_inside_a_stream_capture(monkeypatch):
+    """The hook allocates tensors and records an event, both illegal while optimizer.step() is being captured into a graph:
+    it returns at once."""
+    from gw_whisper_amd import encoder as E
+    enc = _small_encoder()
+    peft = get_peft_model(enc, LoraConfig(use_dora=True, r=4, lora_alpha=8,
+                                          target_modules=_targets(enc, ["layers.*.self_attn.q_proj"])))
+    for n, p in peft.named_parameters():
+        p.requires_grad = "lora" in n
+    calls = []
+    for name in ("_sync_weights", "_param_cache", "_group_keys", "_has_trainable_adapters"):
+        monkeypatch.setattr(enc, name, lambda *a, _n=name, **k: calls.append(_n))
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
+    monkeypatch.setitem(enc.__dict__, "_handle", object())              # as after a first forward
+    E._TRAINED.add(enc)
+    try:
+        E._post_step_sync()
+    finally:
+        E._TRAINED.discard(enc)
+        enc.__dict__["_handle"] = None                                  # (nothing to destroy)
+    assert calls == []
+
+
+def test_weight_table_matches_the_abi():
+    """encoder._LAYER / _GLOBALS are the one description of the encoder's weights: their fields are those of the C structs,
+    in the structs' order, each produced once; the proj ids are gww_dora_target.proj and the bits those of
+    gww_encoder_update_weights."""
+    from gw_whisper_amd import _lib, encoder as E
+    assert [f for f, _, _ in E._fields(E._LAYER)] == [f for f, _ in _lib.EncLayer._fields_]
+    assert [f for f, _ in _lib.EncLayerGrads._fields_] == [f for f, _ in _lib.EncLayer._fields_]
+    assert [f for f, _, _ in E._fields(E._GLOBALS)] == [f for f, _ in _lib.EncGlobals._fields_]
+    assert [f for f, _, _ in E._fields(E._GLOBALS)] == [f for f, _ in _lib.EncGrads._fields_ if f != "layers"]
+    rows = {path: (bit, proj) for path, _, _, bit, proj in E._LAYER}
+    assert rows == {"self_attn_layer_norm": (1, None), "self_attn.q_proj": (1, 0), "self_attn.k_proj": (1, 1),
+                    "self_attn.v_proj": (1, 2), "self_attn.out_proj": (2, 3), "final_layer_norm": (4, None),
+                    "fc1": (4, 4), "fc2": (8, 5)}
+    enc = WhisperEncoder(WhisperConfig(128, 1, 2, 256))
+    for _, path, attr in E._fields(E._LAYER):                           # every path names a parameter of a layer
+        assert isinstance(enc.layers[0].get_parameter(f"{path}.{attr}"), torch.nn.Parameter)
+    for _, path, attr in E._fields(E._GLOBALS):
+        assert isinstance(enc.get_parameter(f"{path}.{attr}"), torch.nn.Parameter)
