@@ -168,6 +168,11 @@ SIGNATURES = {
     "gww_mlp_pack_op_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "gww_lnqkv_fused_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_int,
                                        C.c_void_p]),
+    "gww_stem_fill_f32": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "gww_lnqkv_fused_x0_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_long, C.c_int, C.c_int,
+                                          C.c_void_p]),
+    "gww_attn_out_mlp_fused_x0_bf16": (C.c_int, [C.c_void_p] * 5 + [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_long, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gww_qscan_energy_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p,
                                        C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p]),
     "gww_qscan_interp_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,

@@ -523,6 +523,13 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   void* const c1s = st_base + st.c1s;
   float* const xs = (float*)(st_base + st.xs);
   float* const st_tr = (float*)(st_base + st.tr);
+  // Layer 0 forms the residual stream itself (k_mlp_fused_x0: its LN1 + q / k / v launch in registers, its block in the
+  // accumulators) where both of its launches are the fused ones and nothing else reads x before the block has rewritten it:
+  // the fill launch, its 0.59 GB store and the two 0.59 GB reads of it are gone.  Per-layer hidden states (tap_hidden reads x
+  // in HBM), a last or pooled layer 0 and the generic paths keep the fill.  xs / tr live in x2, the block's x_new buffer: they
+  // survive until layer 0's block has read them because no launch on this path keeps x_new (launch_mlp_fused_x0 never does,
+  // and the later blocks run with keep_x_new = false).
+  const bool x0_layer0 = shortcut && mlp_fused && fuse_qkv && !(generic_mask & (64 | 128)) && !hidden_slab && e->cfg.n_layers > 1;
   auto stem_conv1 = [&]() -> int {
     if (shortcut) {
       GWW_TRY(launch_stem_detect(mel, st_flag, (long)B * C, Tin, s));
@@ -535,7 +542,7 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
     if (shortcut) {
       GWW_TRY(launch_gemm_bf16_v4(c1s, 2L * d, e->c2w, e->c2b, nullptr, xs, (long)B * (kStemTt + 1), Np, 3 * d, EPI_CONV2, s, 0,
                                   e->pos_c, kStemTt + 1, d, (float*)(st_base + st.dump), st_flag, 1, st_tr, kStemTt - 2));
-      GWW_TRY(launch_stem_fill(xs, st_tr, e->pos, x, st_flag, B, T, d, s));
+      if (!x0_layer0) GWW_TRY(launch_stem_fill(xs, st_tr, e->pos, x, st_flag, B, T, d, s));
     }
     return launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), Np, 3 * d, EPI_CONV2, s, 0, e->pos,
                                T + 1, d, x + (((size_t)B * T + 255) / 256 * 256) * d, shortcut ? st_flag : nullptr, 0);
@@ -587,7 +594,11 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
       if (!qkv_done) {
         if (i == 0 && !pending && fuse_qkv && !(generic_mask & 64)) {
           // layer 0 (no delta pending behind the conv stem): the fused kernel's panel prologue + q / k / v tail
-          TR(TR_QKV, launch_lnqkv_fused(xc, L.uqkv, L.cbqkv, L.wqkv_st, qkv, M, d, 3 * d, s));
+          if (x0_layer0)
+            TR(TR_QKV, launch_lnqkv_fused_x0(xs, st_tr, e->pos, st_flag, xc, T, kStemTt, L.uqkv, L.cbqkv, L.wqkv_st, qkv, M, d,
+                                             3 * d, s));
+          else
+            TR(TR_QKV, launch_lnqkv_fused(xc, L.uqkv, L.cbqkv, L.wqkv_st, qkv, M, d, 3 * d, s));
         } else {
           TR(TR_QKV, launch_gemm_astat(xc, d, pending, pending ? xn : nullptr, L.uqkv, L.cbqkv, L.wqkv_ln, nullptr, qkv, M,
                                        3 * d, d, EPI_BIAS, 0, s));
@@ -610,6 +621,10 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
         // ... and the next layer's LN1 + q / k / v projection appended: xn receives x_next (no delta pending)
         const LayerW& Ln = e->layers[i + 1];
         // (x_next comes back in xc itself: xn only holds x_new, the block's intermediate residual stream)
+        if (i == 0 && x0_layer0 && op)   // (x0_layer0 implies op: no delta is pending behind launch_lnqkv_fused_x0)
+          TR(TR_MLPQKV, launch_mlp_fused_x0(xs, st_tr, e->pos, st_flag, xc, T, kStemTt, ctx, L.bo, L.u1, L.cb1, L.wmlp_op, L.b2, M, d,
+                                            F, Ln.uqkv, Ln.cbqkv, qkv, 3 * d, s));
+        else
         TR(TR_MLPQKV, launch_mlp_fused(xc, op ? ctx : d1, xn, L.u1, L.cb1, op ? L.wmlp_op : L.wmlp, L.b2, nullptr, M, d, F, s,
                                        Ln.uqkv, Ln.cbqkv, qkv, 3 * d, nullptr, op ? L.bo : nullptr, /*keep_x_new=*/false));
         pending = nullptr;

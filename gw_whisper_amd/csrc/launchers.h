@@ -21,7 +21,7 @@ int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c
 bool stem_tail_supported(int t_in, int d);
 int launch_stem_detect(const float* mel, int* flag, long rows, int t_in, hipStream_t s);
 int launch_stem_fill(const float* xs, const float* tr, const float* pos, float* x, const int* flag, int B, int T, int d,
-                     hipStream_t s);
+                     hipStream_t s, int Tt = kStemTt);
 int launch_mel_to_tokens(const float* mel, void* out, int out_bf16, int B, int C, int T, hipStream_t s);
 
 // ---- GEMMs: gemm_astat.hip, gemm_bf16.hip, gemm_v4.hip, gemm_fulln.hip, gemm_f32.hip
@@ -63,6 +63,13 @@ int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const 
                            long M, int d, int F, hipStream_t s, bool keep_x_new = true);
 int launch_lnqkv_fused(const float* x, const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d,
                        int NQ, hipStream_t s);
+// layer 0 behind the compact stem: the panel formed from xs / tr / pos where *flag == 1, read from x where it is 0
+int launch_lnqkv_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T, int Tt,
+                          const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d, int NQ,
+                          hipStream_t s);
+int launch_mlp_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T, int Tt,
+                        const void* ctx, const float* bo, const float* ln_u, const float* ln_cb, const void* Wt, const float* b2,
+                        long M, int d, int F, const float* q_u, const float* q_cb, void* q_out, int NQ, hipStream_t s);
 
 // ---- the bf16 training step: train_ops.hip, dora_grads.hip, wgrad.hip
 int launch_ln_bwd(const float* x, const float* gamma, const void* dy, int dy_f32, float* dx, int accumulate,

@@ -226,7 +226,35 @@ __device__ unsigned long long g_stamp_mlp[24];
 // [M, 384]) and the stream starts with the 18 tiles of W_o; ctx is the A operand of a GEMM into the (still idle) output
 // accumulators, whose result + bo meets the residual stream in the seam code (x_new = x + bf16(ctx W_o^T + bo)).  The
 // stand-alone out_proj kernel and the bf16 delta round trip through HBM disappear.
-template <int MODE, bool OP>
+// X0 (layer 0 behind the compact stem, stem_tail.hip): the panel is FORMED from what the constant-tail shortcut left -- xs [B, Tt,
+// 384], tr [B, 384] and the position table -- instead of being read from a residual stream that k_stem_fill expanded in HBM:
+//   token j <= Tt - 3: xs[b, j] (bitwise);  Tt - 2 <= j <= T - 2: fma(xs[b, Tt - 2], tr[b], pos[j]) (k_stem_fill's arithmetic,
+//   one rounding);  j = T - 1: xs[b, Tt - 1] (bitwise).
+// The loads of a row take a per-lane source (a 128-row panel straddles segments); the shared row's x and r of the at most two
+// segments of a panel are staged in the u table of the LDS (unused otherwise: GWW_MF_NORM).  *flag == 0 (the forward took the
+// full stem): the same loads read X, nothing is staged or fixed up.
+struct MfX0 {
+  const float* xs;
+  const float* tr;
+  const float* pos;
+  const int* flag;
+  int T, Tt;
+};
+
+// source of row g of the residual stream (x0: the device flag); tail: the row is the shared row under pos[j]; seg: its segment
+__device__ __forceinline__ const float* mf_x0_row(const MfX0& z, const float* X, long g, bool x0, bool& tail, int& seg) {
+  tail = false; seg = 0;
+  if (!x0) return X + g * MF_D;
+  const unsigned b = (unsigned)g / (unsigned)z.T, j = (unsigned)g - b * (unsigned)z.T;
+  seg = (int)b;
+  tail = (int)j >= z.Tt - 2 && (int)j <= z.T - 2;
+  if (tail) return z.pos + (long)j * MF_D;
+  return z.xs + ((long)b * z.Tt + ((int)j == z.T - 1 ? z.Tt - 1 : (int)j)) * MF_D;
+}
+
+struct MfNoX0 {};
+// (X0 only changes the TYPE of the last kernel argument: the instantiations without it keep their code as it was)
+template <int MODE, bool OP, bool X0 = false>
 __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, const unsigned short* delta, float* x_out,
                                                             const float* __restrict__ ln_u,
                                                             const float* __restrict__ ln_cb,
@@ -236,9 +264,11 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
                                                             int stagger_ticks, const float* __restrict__ q_u,
                                                             const float* __restrict__ q_cb,
                                                             unsigned short* __restrict__ q_out, int NQ,
-                                                            float* x_next, const float* __restrict__ bo, int keep_x_new) {
+                                                            float* x_next, const float* __restrict__ bo, int keep_x_new,
+                                                            const std::conditional_t<X0, MfX0, MfNoX0> z) {
   __shared__ __attribute__((aligned(16))) unsigned char lds[MF_LDS];
   constexpr bool QKV = MODE == 1 || MODE == 2, LNQ = MODE == 2, FIN = MODE == 3;
+  static_assert(!X0 || (GWW_MF_NORM && GWW_MF_XACC && (MODE == 2 || (MODE == 1 && OP))), "X0: layer 0's two launches; stages in the u table");
   constexpr bool XACC = GWW_MF_XACC && GWW_MF_NORM && GWW_MF_SCHED && OP && (MODE == 1 || MODE == 3);
   constexpr int MF_NST = MF_AHEAD + 1;
   float* lds_cb = reinterpret_cast<float*>(lds + MF_OFF_CB);
@@ -340,7 +370,48 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   const long xrow_l = m_base + r < M ? m_base + r : M - 1;
   const unsigned xoff = (unsigned)xrow_l * (unsigned)(MF_D * 4) + 16u * (unsigned)hh;
   f32x4 xp[XACC ? MF_OT : 1][4];
-  if constexpr (XACC) {
+  // ---- X0: the device flag (block-uniform), the panel's first segment, and what every thread stages of the shared rows: 16-byte
+  // piece q of [2 segments][xs[b, Tt - 2] | tr[b]][96] (the panel's segments are seg0 and, clamped to the last one, seg0 + 1)
+  bool x0 = false;
+  int x0_seg0 = 0;
+  f32x4* const lds_x0 = reinterpret_cast<f32x4*>(lds + MF_OFF_U);
+  const float* x0_stage[2] = {nullptr, nullptr};
+  f32x4 x0_sg[2];
+  bool x0_tail = false;   // (XACC) the lane's row is a shared row
+  int x0_seg = 0;
+  if constexpr (X0) {
+    x0 = __builtin_amdgcn_readfirstlane(*z.flag) != 0;
+    const unsigned g0 = (unsigned)blockIdx.x * (unsigned)MF_BM;
+    x0_seg0 = (int)(g0 / (unsigned)z.T);
+    const int seg_last = (int)((unsigned)(M - 1) / (unsigned)z.T);
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int q = tid + 256 * k < 4 * (MF_D / 4) ? tid + 256 * k : tid;   // (384 pieces: the upper half of the block repeats its first)
+      const int sg = q / (2 * (MF_D / 4)), wh = (q / (MF_D / 4)) & 1, c = q % (MF_D / 4);
+      const long b = x0_seg0 + sg < seg_last ? x0_seg0 + sg : seg_last;
+      x0_stage[k] = (wh ? z.tr + b * MF_D : z.xs + (b * z.Tt + (z.Tt - 2)) * MF_D) + 4 * c;
+    }
+  }
+  // the staged pieces -> LDS, visible to the whole block (call behind the wait that proves sg has landed)
+  auto x0_publish = [&](f32x4 (&sg)[2]) {
+    lds_x0[tid] = sg[0];
+    if (tid + 256 < 4 * (MF_D / 4)) lds_x0[tid + 256] = sg[1];
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // (a raw barrier: __syncthreads would also wait for the loads in flight)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  };
+  if constexpr (XACC && X0) {
+    // The 48 requests of a lane take a per-lane 64-bit source: the lane's row of xs (taken bitwise), of pos (the shared row's
+    // fma follows in the prologue below), or -- flag 0 -- of X.  Queue: 48 x pieces, 2 staged pieces, then the 24 ctx pieces.
+    const float* xsrc = mf_x0_row(z, X, xrow_l, x0, x0_tail, x0_seg) + 4 * hh;
+#pragma unroll
+    for (int t = 0; t < MF_OT; ++t)
+#pragma unroll
+      for (int cc = 0; cc < 4; ++cc)
+        asm volatile("global_load_dwordx4 %0, %1, off offset:%2" MF_XNT : "=a"(xp[t][cc]) : "v"(xsrc), "n"((32 * t + 8 * cc) * 4) : "memory");
+#pragma unroll
+    for (int k = 0; k < 2; ++k) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0_sg[k]) : "v"(x0_stage[k]) : "memory");
+  } else if constexpr (XACC) {
     // The residual stream goes straight INTO the accumulator file (48 loads of 16 bytes per lane, 32-byte row pieces
     // per lane pair), in front of the ctx loads: loads retire in issue order, so the first counted ctx wait below also
     // proves every x piece has landed -- long before the out_proj GEMM's first MFMA reads them as its C operand.  The four
@@ -373,6 +444,27 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(af[4 * S + j]) : "v"(coff), "s"(delta), "n"((64 * S + 8 * j) * 2) : "memory");
+    if constexpr (X0) {
+      if (x0) {
+        // x and the staged pieces have landed once only the 24 ctx requests are outstanding; the shared row's fma runs on the
+        // accumulator registers while ctx is still arriving:  x[b, j] = fma(xs[b, Tt - 2], tr[b], pos[j])  (k_stem_fill)
+        asm volatile("s_waitcnt vmcnt(24)" : "+v"(x0_sg[0]), "+v"(x0_sg[1]) : : "memory");
+#pragma unroll
+        for (int t = 0; t < MF_OT; ++t) asm volatile("" : "+a"(xp[t][0]), "+a"(xp[t][1]), "+a"(xp[t][2]), "+a"(xp[t][3]));
+        x0_publish(x0_sg);
+        if (x0_tail) {
+          const f32x4* const st = lds_x0 + (x0_seg - x0_seg0) * (2 * (MF_D / 4)) + hh;
+#pragma unroll
+          for (int t = 0; t < MF_OT; ++t)
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) {
+              const f32x4 xt = st[8 * t + 2 * cc], rt = st[MF_D / 4 + 8 * t + 2 * cc];
+#pragma unroll
+              for (int k = 0; k < 4; ++k) xp[t][cc][k] = __builtin_fmaf(xt[k], rt[k], xp[t][cc][k]);
+            }
+        }
+      }
+    }
     stage_tables();
     // one wait for the panel: ring tiles, x, ctx and the tables (loads retire in issue order; hipcc's own waits for the table
     // values already imply it -- this one is for the reader).  The fences keep the fragments' first use behind it.
@@ -426,6 +518,21 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
       xrow[i] = X + grow[i] * MF_D + 4 * cchunk;
       drow[i] = LNQ ? nullptr : delta + grow[i] * MF_D + 4 * cchunk;
     }
+    // X0: a row's loads go to ITS source (xs, pos or -- flag 0 -- X); tl: the row is a shared row, st_row: its segment's staged
+    // xs[b, Tt - 2] | tr[b] at this lane's column.  The two staged pieces are requested in front of the panel: older than every
+    // load counted below, so those counts stand as they are.
+    bool tl[4] = {false, false, false, false};
+    const f32x4* st_row[4] = {lds_x0, lds_x0, lds_x0, lds_x0};
+    if constexpr (X0) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        int seg;
+        xrow[i] = mf_x0_row(z, X, grow[i], x0, tl[i], seg) + 4 * cchunk;
+        st_row[i] = lds_x0 + (seg - x0_seg0) * (2 * (MF_D / 4)) + cchunk;
+      }
+#pragma unroll
+      for (int k = 0; k < 2; ++k) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(x0_sg[k]) : "v"(x0_stage[k]) : "memory");
+    }
 #pragma unroll
     for (int S3 = 0; S3 < MF_KT; S3 += 3) {
       f32x4 xv[3][2][4];
@@ -436,12 +543,22 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
         for (int h2 = 0; h2 < 2; ++h2)
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
+            if constexpr (X0)   // (no streaming hint: every segment reads the same position rows)
+              asm volatile("global_load_dwordx4 %0, %1, off offset:%2"
+                           : "=v"(xv[S][h2][i]) : "v"(xrow[i]), "n"((64 * (S3 + S) + 32 * h2) * 4) : "memory");
+            else
             asm volatile("global_load_dwordx4 %0, %1, off offset:%2" MF_NT
                          : "=v"(xv[S][h2][i]) : "v"(xrow[i]), "n"((64 * (S3 + S) + 32 * h2) * 4) : "memory");
             if (!LNQ)
               asm volatile("global_load_dwordx2 %0, %1, off offset:%2" MF_NT
                            : "=v"(dv[S][h2][i]) : "v"(drow[i]), "n"((64 * (S3 + S) + 32 * h2) * 2) : "memory");
           }
+      if constexpr (X0) {
+        if (S3 == 0 && x0) {   // the staged pieces have landed once only the 24 loads of the first batch are outstanding
+          asm volatile("s_waitcnt vmcnt(24)" : "+v"(x0_sg[0]), "+v"(x0_sg[1]) : : "memory");
+          x0_publish(x0_sg);
+        }
+      }
 #pragma unroll
       for (int Sl = 0; Sl < 3; ++Sl) {
         const int S = S3 + Sl;
@@ -453,6 +570,13 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
             if (LNQ) {   // no delta, no write-back: load k of the batch of 24 is complete once 23 - k younger loads are outstanding
               asm volatile("s_waitcnt vmcnt(%1)" : "+v"(xv[Sl][h2][i]) : "n"(23 - (8 * Sl + 4 * h2 + i)));
               v = xv[Sl][h2][i];
+              if constexpr (X0) {
+                if (tl[i]) {   // the shared row under pos[j]: k_stem_fill's fma, one rounding
+                  const f32x4 xt = st_row[i][16 * S + 8 * h2], rt = st_row[i][MF_D / 4 + 16 * S + 8 * h2];
+#pragma unroll
+                  for (int k = 0; k < 4; ++k) v[k] = __builtin_fmaf(xt[k], rt[k], v[k]);
+                }
+              }
             } else {
               asm volatile("s_waitcnt vmcnt(%2)" : "+v"(xv[Sl][h2][i]), "+v"(dv[Sl][h2][i]) : "n"(46 - (8 * Sl + 4 * h2 + i)));
               v = xv[Sl][h2][i];
@@ -1773,7 +1897,7 @@ int launch_mlp_fused(const float* x, const void* delta, float* x_out, const floa
   const int stagger = panels >= 512 ? stagger_env : 0;
 #define GWW_MF_LAUNCH(QQ, OO, ...)                                                                                        \
   hipLaunchKernelGGL((k_mlp_fused<QQ, OO>), dim3((unsigned)panels), dim3(MF_THREADS), 0, s, x, (const unsigned short*)delta, \
-                     x_out, ln_u, ln_cb, (const unsigned short*)Wt, b2, (unsigned short*)C, M, F, stagger, __VA_ARGS__, bo, keep_x_new ? 1 : 0)
+                     x_out, ln_u, ln_cb, (const unsigned short*)Wt, b2, (unsigned short*)C, M, F, stagger, __VA_ARGS__, bo, keep_x_new ? 1 : 0, MfNoX0{})
   if (qkv) {
     // x_next goes to its own buffer (training: the saved activations) or back over x, whose rows each workgroup has
     // finished reading long before it writes them; never over x_out: the seam's unmasked stores of the clamped rows past M
@@ -1807,7 +1931,7 @@ int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const 
   if (M == 0) return GWW_OK;
   hipLaunchKernelGGL((k_mlp_fused<3, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, x, (const unsigned short*)ctx,
                      x_mid, ln_u, ln_cb, (const unsigned short*)Wt, b2, reinterpret_cast<unsigned short*>(y), M, F, 0, lnf_w,
-                     lnf_b, (unsigned short*)nullptr, 0, (float*)nullptr, bo, keep_x_new ? 1 : 0);
+                     lnf_b, (unsigned short*)nullptr, 0, (float*)nullptr, bo, keep_x_new ? 1 : 0, MfNoX0{});
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
@@ -1826,7 +1950,59 @@ int launch_lnqkv_fused(const float* x, const float* q_u, const float* q_cb, cons
   hipLaunchKernelGGL((k_mlp_fused<2, false>), dim3((unsigned)panels), dim3(MF_THREADS), 0, s, x, (const unsigned short*)nullptr,
                      (float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const unsigned short*)Wt,
                      (const float*)nullptr, (unsigned short*)nullptr, M, 0, 0, q_u, q_cb, (unsigned short*)q_out, NQ,
-                     (float*)nullptr, (const float*)nullptr, 0);
+                     (float*)nullptr, (const float*)nullptr, 0, MfNoX0{});
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// ---- layer 0 behind the compact stem (stem_tail.hip): both launches form their panel from xs [B, Tt, 384], tr [B, 384] and
+// pos [T, 384] when *flag == 1 and read x [M, 384] when it is 0 (decided in the kernel: no host synchronisation).  M = B T.
+static int x0_check(const char* who, const float* xs, const float* tr, const float* pos, const int* flag, const float* x, long M,
+                    int T, int Tt) {
+  GWW_REQUIRE(xs && tr && pos && flag && x, "%s: NULL operand", who);
+  // (T >= 128: a 128-row panel then holds rows of at most two segments, which is what the kernel stages)
+  GWW_REQUIRE(T >= MF_BM && Tt >= 3 && Tt < T && M % T == 0, "%s: bad shape M=%ld T=%d Tt=%d", who, M, T, Tt);
+  GWW_REQUIRE(((((uintptr_t)xs) | ((uintptr_t)tr) | ((uintptr_t)pos) | ((uintptr_t)x)) & 15) == 0 && (((uintptr_t)flag) & 3) == 0,
+              "%s: operands must be 16-byte aligned", who);
+  return GWW_OK;
+}
+
+// launch_lnqkv_fused on the stream the compact stem describes: x is only read, and only when *flag == 0
+int launch_lnqkv_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T, int Tt,
+                          const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d, int NQ,
+                          hipStream_t s) {
+  GWW_REQUIRE(q_u && q_cb && Wt && q_out, "lnqkv_fused_x0: NULL operand");
+  GWW_REQUIRE(d == MF_D, "lnqkv_fused_x0: built for d_model = 384 (got %d)", d);
+  GWW_REQUIRE(NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX, "lnqkv_fused_x0: NQ = %d must be a multiple of 128, <= 1536", NQ);
+  GWW_REQUIRE(((((uintptr_t)Wt) | ((uintptr_t)q_out)) & 15) == 0, "lnqkv_fused_x0: operands must be 16-byte aligned");
+  if (M == 0) return GWW_OK;
+  GWW_TRY(x0_check("lnqkv_fused_x0", xs, tr, pos, flag, x, M, T, Tt));
+  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "lnqkv_fused_x0: M = %ld rows exceed 32-bit row indices", M);
+  hipLaunchKernelGGL((k_mlp_fused<2, false, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, x,
+                     (const unsigned short*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
+                     (const unsigned short*)Wt, (const float*)nullptr, (unsigned short*)nullptr, M, 0, 0, q_u, q_cb,
+                     (unsigned short*)q_out, NQ, (float*)nullptr, (const float*)nullptr, 0, MfX0{xs, tr, pos, flag, T, Tt});
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// launch_mlp_fused with the out_proj in front and the next layer's q / k / v behind (k_mlp_fused<1, true>), the block's x formed
+// in its accumulators; x_next is written to x (flag 1: x is not read at all), x_new is not kept
+int launch_mlp_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T, int Tt,
+                        const void* ctx, const float* bo, const float* ln_u, const float* ln_cb, const void* Wt, const float* b2,
+                        long M, int d, int F, const float* q_u, const float* q_cb, void* q_out, int NQ, hipStream_t s) {
+  GWW_REQUIRE(ctx && bo && ln_u && ln_cb && Wt && b2 && q_u && q_cb && q_out, "mlp_fused_x0: NULL operand");
+  GWW_REQUIRE(d == MF_D, "mlp_fused_x0: built for d_model = 384 (got %d)", d);
+  GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused_x0: ffn = %d must be a multiple of 128, <= 1536", F);
+  GWW_REQUIRE(NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX, "mlp_fused_x0: NQ = %d must be a multiple of 128, <= 1536", NQ);
+  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "mlp_fused_x0: M = %ld rows exceed the 32-bit row offsets of the seams", M);
+  GWW_REQUIRE(((((uintptr_t)ctx) | ((uintptr_t)Wt) | ((uintptr_t)q_out)) & 15) == 0, "mlp_fused_x0: operands must be 16-byte aligned");
+  if (M == 0) return GWW_OK;
+  GWW_TRY(x0_check("mlp_fused_x0", xs, tr, pos, flag, x, M, T, Tt));
+  hipLaunchKernelGGL((k_mlp_fused<1, true, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, (const float*)x,
+                     (const unsigned short*)ctx, (float*)nullptr, ln_u, ln_cb, (const unsigned short*)Wt, b2,
+                     (unsigned short*)nullptr, M, F, 0, q_u, q_cb, (unsigned short*)q_out, NQ, x, bo, 0,
+                     MfX0{xs, tr, pos, flag, T, Tt});
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
@@ -1884,4 +2060,18 @@ extern "C" int gww_mlp_fused_bf16(float* x, const void* delta, float* x_out, con
                                   void* stream) {
   return launch_mlp_fused(x, delta, x_out, ln_u, ln_cb, Wt, b2, C, M, d, F, (hipStream_t)stream, qkv_u, qkv_cb, qkv_out,
                           NQ, nullptr, nullptr);
+}
+
+extern "C" int gww_lnqkv_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T,
+                                       int Tt, const float* qkv_u, const float* qkv_cb, const void* Wt, void* qkv_out, long M,
+                                       int d, int NQ, void* stream) {
+  return launch_lnqkv_fused_x0(xs, tr, pos, flag, x, T, Tt, qkv_u, qkv_cb, Wt, qkv_out, M, d, NQ, (hipStream_t)stream);
+}
+
+extern "C" int gww_attn_out_mlp_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T,
+                                              int Tt, const void* ctx, const float* bo, const float* ln_u, const float* ln_cb,
+                                              const void* Wt, const float* b2, long M, int d, int F, const float* qkv_u,
+                                              const float* qkv_cb, void* qkv_out, int NQ, void* stream) {
+  return launch_mlp_fused_x0(xs, tr, pos, flag, x, T, Tt, ctx, bo, ln_u, ln_cb, Wt, b2, M, d, F, qkv_u, qkv_cb, qkv_out, NQ,
+                             (hipStream_t)stream);
 }

@@ -123,16 +123,24 @@ int launch_stem_detect(const float* mel, int* flag, long rows, int t_in, hipStre
 }
 
 int launch_stem_fill(const float* xs, const float* tr, const float* pos, float* x, const int* flag, int B, int T, int d,
-                     hipStream_t s) {
+                     hipStream_t s, int Tt) {
   GWW_REQUIRE(xs && tr && pos && x && flag, "stem_fill: NULL operand");
-  GWW_REQUIRE(d % 4 == 0 && d / 4 <= 256 && T > kStemTt && B <= 65535, "stem_fill: bad shape B=%d T=%d d=%d", B, T, d);
+  GWW_REQUIRE(d % 4 == 0 && d / 4 <= 256 && Tt >= 3 && T > Tt && B <= 65535, "stem_fill: bad shape B=%d T=%d d=%d", B, T, d);
   if (B == 0) return GWW_OK;
   const int d4 = d / 4, ny = 256 / d4 > 0 ? 256 / d4 : 1;
   const int rpb = 60;
   hipLaunchKernelGGL(k_stem_fill, dim3((unsigned)cdiv(T, rpb), (unsigned)B), dim3(d4, ny), 0, s, (const f32x4*)xs,
-                     (const f32x4*)tr, (const f32x4*)pos, (f32x4*)x, flag, T, kStemTt, d4, rpb);
+                     (const f32x4*)tr, (const f32x4*)pos, (f32x4*)x, flag, T, Tt, d4, rpb);
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
 
 }  // namespace gww
+
+// x fp32 [B, T, d] <- the residual stream the compact stem describes (k_stem_fill; a no-op where *flag == 0)
+extern "C" int gww_stem_fill_f32(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int B, int T, int Tt,
+                                 int d, void* stream) {
+  GWW_REQUIRE(B >= 0 && ((((uintptr_t)xs) | ((uintptr_t)tr) | ((uintptr_t)pos) | ((uintptr_t)x)) & 15) == 0,
+              "gww_stem_fill_f32: B < 0 or operands not 16-byte aligned");
+  return gww::launch_stem_fill(xs, tr, pos, x, flag, B, T, d, (hipStream_t)stream, Tt);
+}

@@ -319,6 +319,74 @@ def lnqkv_fused(x, wt, qkv_u, qkv_cb):
     return qo[:M]
 
 
+def _x0_operands(xs, tr, pos, flag, x=None):
+    """The compact stem's description of layer 0's residual stream: xs fp32 [B, Tt, 384], tr fp32 [B, 384], pos fp32 [T, 384],
+    flag int32 [1] (on the device), x fp32 [B * T, 384] or None (allocated uninitialised: unread where flag == 1)."""
+    xs, tr, pos = _dev(xs, torch.float32, "xs"), _dev(tr, torch.float32, "tr"), _dev(pos, torch.float32, "pos")
+    if flag.dtype != torch.int32 or not flag.is_cuda or flag.numel() != 1:
+        raise _lib.GwwError("flag must be one int32 on the device")
+    B, Tt, d = xs.shape
+    T = pos.shape[0]
+    if tr.shape != (B, d) or pos.shape[1] != d:
+        raise _lib.GwwError("tr must be [B, d] and pos [T, d]")
+    if x is None:
+        x = torch.empty((B * T, d), dtype=torch.float32, device=xs.device)
+    else:
+        x = _dev(x, torch.float32, "x")
+        if x.numel() != B * T * d:
+            raise _lib.GwwError("x must hold B * T rows")
+    return xs, tr, pos, flag, x, B, T, Tt, d
+
+
+def stem_fill(xs, tr, pos, flag, x=None):
+    """x fp32 [B * T, d]: the residual stream behind the compact conv stem written out (``gww_stem_fill_f32``):
+    x[b, j] = xs[b, j] (j <= Tt - 3), fma(xs[b, Tt - 2], tr[b], pos[j]) (Tt - 2 <= j <= T - 2), xs[b, Tt - 1] (j = T - 1).
+    Leaves ``x`` as it is where the device flag is 0."""
+    xs, tr, pos, flag, x, B, T, Tt, d = _x0_operands(xs, tr, pos, flag, x)
+    with torch.cuda.device(xs.device):
+        check(lib().gww_stem_fill_f32(xs.data_ptr(), tr.data_ptr(), pos.data_ptr(), flag.data_ptr(), x.data_ptr(), B, T, Tt, d,
+                                      _stream()), "gww_stem_fill_f32")
+    return x
+
+
+def lnqkv_fused_x0(xs, tr, pos, flag, wt, qkv_u, qkv_cb, x=None):
+    """``lnqkv_fused`` on the stream ``stem_fill`` would write, formed in registers instead (flag 1: ``x`` is not read;
+    flag 0: the kernel reads ``x``).  Bitwise ``lnqkv_fused(stem_fill(...))``."""
+    xs, tr, pos, flag, x, B, T, Tt, d = _x0_operands(xs, tr, pos, flag, x)
+    wt = _dev(wt, torch.bfloat16, "Wt")
+    qu, qc = _dev(qkv_u, torch.float32), _dev(qkv_cb, torch.float32)
+    NQ, M = qu.numel(), B * T
+    qo = torch.empty(((M + 127) // 128 * 128, NQ), dtype=torch.bfloat16, device=xs.device)
+    with torch.cuda.device(xs.device):
+        check(lib().gww_lnqkv_fused_x0_bf16(xs.data_ptr(), tr.data_ptr(), pos.data_ptr(), flag.data_ptr(), x.data_ptr(), T, Tt,
+                                            qu.data_ptr(), qc.data_ptr(), wt.data_ptr(), qo.data_ptr(), M, d, NQ, _stream()),
+              "gww_lnqkv_fused_x0_bf16")
+    return qo[:M]
+
+
+def attn_out_mlp_fused_x0(xs, tr, pos, flag, ctx, wo, bo, w1_folded, w2, ln_u, ln_cb, b2, qkv, x=None):
+    """``attn_out_mlp_fused`` with the q / k / v tail on the stream ``stem_fill`` would write, formed in the kernel's accumulators
+    (flag 1: ``x`` is not read; flag 0: the kernel reads ``x``).  Returns (qkv, x_next); the caller's ``x`` stays untouched."""
+    xs, tr, pos, flag, x, B, T, Tt, d = _x0_operands(xs, tr, pos, flag, x)
+    x = x.clone().view(B * T, d)   # x_next is written over x
+    ctx = _dev(ctx, torch.bfloat16, "ctx")
+    wo, w1, w2 = _dev(wo, torch.bfloat16, "Wo"), _dev(w1_folded, torch.bfloat16, "W1"), _dev(w2, torch.bfloat16, "W2")
+    wq = _dev(qkv[0], torch.bfloat16, "Wqkv")
+    F, NQ, M = w1.shape[0], wq.shape[0], B * T
+    f = lambda t: _dev(t, torch.float32)
+    bo, u, cb, b2, qu, qc = f(bo), f(ln_u), f(ln_cb), f(b2), f(qkv[1]), f(qkv[2])
+    wt = torch.empty((d * d + 2 * d * F + NQ * d,), dtype=torch.bfloat16, device=x.device)
+    out = torch.empty(((M + 127) // 128 * 128, NQ), dtype=torch.bfloat16, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().gww_mlp_pack_op_bf16(wo.data_ptr(), w1.data_ptr(), w2.data_ptr(), wq.data_ptr(), wt.data_ptr(), d, F, NQ,
+                                         _stream()), "gww_mlp_pack_op_bf16")
+        check(lib().gww_attn_out_mlp_fused_x0_bf16(xs.data_ptr(), tr.data_ptr(), pos.data_ptr(), flag.data_ptr(), x.data_ptr(), T, Tt,
+                                                   ctx.data_ptr(), bo.data_ptr(), u.data_ptr(), cb.data_ptr(), wt.data_ptr(),
+                                                   b2.data_ptr(), M, d, F, qu.data_ptr(), qc.data_ptr(), out.data_ptr(), NQ,
+                                                   _stream()), "gww_attn_out_mlp_fused_x0_bf16")
+    return out[:M], x
+
+
 def mlp_fused(x, delta, wt, ln_u, ln_cb, b2, qkv=None):
     """(C bf16 [M, 384], x_new fp32 [M, 384]) = fused LayerNorm -> fc1 -> GELU -> fc2 of x + delta.
     ``qkv=(u, cb)`` of the next layer's folded q / k / v projection (panel appended to ``wt``): returns

@@ -405,6 +405,22 @@ int gww_mlp_pack_op_bf16(const void* wo, const void* w1_folded, const void* w2, 
  * NQ % 128 == 0, NQ <= 1536. */
 int gww_lnqkv_fused_bf16(const float* x, const float* qkv_u, const float* qkv_cb, const void* Wt, void* qkv_out, long M,
                          int d, int NQ, void* stream);
+/* Layer 0 behind the compact conv stem (the constant tail of a padded log-mel, gww_encoder_set_stem_shortcut).  The stem leaves
+ * xs fp32 [B,Tt,384] (compact conv2 output), tr fp32 [B,384] and the device flag; with pos fp32 [T,384] they describe the residual
+ * stream x fp32 [B,T,384]:  x[b,j] = xs[b,j] for j <= Tt-3,  fma(xs[b,Tt-2], tr[b], pos[j]) for Tt-2 <= j <= T-2,  xs[b,Tt-1] for
+ * j = T-1.  gww_stem_fill_f32 writes that stream to x (a no-op where *flag == 0).  The two x0 forms are gww_lnqkv_fused_bf16 and
+ * gww_attn_out_mlp_fused_bf16 (with the q / k / v tail; x_new is not kept) on that stream WITHOUT it being written first: where
+ * *flag == 1 they form their 128-row panels from xs / tr / pos in registers and never read x; where *flag == 0 they read x.
+ * Results are bitwise those of the fill followed by the plain entry.  The block writes x_next to x.  M = B T, T >= 128. */
+int gww_stem_fill_f32(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int B, int T, int Tt, int d,
+                      void* stream);
+int gww_lnqkv_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T, int Tt,
+                            const float* qkv_u, const float* qkv_cb, const void* Wt, void* qkv_out, long M, int d, int NQ,
+                            void* stream);
+int gww_attn_out_mlp_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T, int Tt,
+                                   const void* ctx, const float* bo, const float* ln_u, const float* ln_cb, const void* Wt,
+                                   const float* b2, long M, int d, int F, const float* qkv_u, const float* qkv_cb, void* qkv_out,
+                                   int NQ, void* stream);
 /* Q-transform front end #2 (ml4gw QScan as used by MLGWSC-1/train.py:117-122,135-154; PARITY UNPINNED: ml4gw is not
  * vendored, pinned or installed -- the kernels follow oracle/qscan.py).  The host builds the static tiling once
  * (gw_whisper_amd/qscan.py): rows = int [n_rows][6] (plane, ntiles, windowsize, first data index, energy offset,
