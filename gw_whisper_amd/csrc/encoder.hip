@@ -248,7 +248,7 @@ static int pack_weights(gww_encoder* e, const gww_enc_globals* g, const gww_enc_
   GWW_TRY(pb.flush());
   GWW_TRY(pt.flush());
   // the fused-MLP weight stream of layer i: folded fc1 panel, fc2 and the folded q / k / v panel of layer i + 1
-  if (d == 384 && F % 128 == 0 && F <= 1536) {
+  if (mlp_fused_supported(d, F)) {
     for (int i = 0; i < n_layers; ++i) {
       const unsigned m = dirty ? dirty[i] : 15u, mn = i + 1 < n_layers ? (dirty ? dirty[i + 1] : 15u) : 0u;
       if (!(m & 14u) && !(mn & 1u)) continue;   // (bit 1: out_proj, in front of the wmlp_op stream)
@@ -257,7 +257,7 @@ static int pack_weights(gww_encoder* e, const gww_enc_globals* g, const gww_enc_
       // Only the stream the active path consumes is packed: the inference and the training forward both run the block with
       // out_proj in front (wmlp_op); the stream without it serves the debug paths GWW_GENERIC_PATH bits 4 / 7 alone (a
       // DoRA step used to pay two full fc1 + fc2 + q/k/v stream packs per layer, 2 x 3.2 MB of writes, for one consumer).
-      static const bool plain_stream = (lab_int("GWW_GENERIC_PATH", 0) & (16 | 128)) != 0;
+      const bool plain_stream = (generic_path_mask() & (GP_QKV | GP_OUT_PROJ)) != 0;
       if (plain_stream && ((m & 12u) || (mn & 1u))) GWW_TRY(launch_mlp_pack(w.w1_ln, w.w2, wq_next, w.wmlp, d, F, 3 * d, s));
       GWW_TRY(launch_mlp_pack(w.w1_ln, w.w2, wq_next, w.wmlp_op, d, F, 3 * d, s, w.wo));
     }
@@ -330,14 +330,57 @@ StemTailLayout stem_tail_layout(int B, int d) {
   t.total = a.total();
   return t;
 }
-// where the shortcut applies: bf16, conv1 on k_conv1_mel, conv2 on k_gemm_bf16_v4 (bit 11 of GWW_GENERIC_PATH disables it)
-bool stem_shortcut_applies(const gww_encoder* e, int batch, int precision) {
-  static const int generic_mask = (int)lab_int("GWW_GENERIC_PATH", 0);
+
+// ---- the plan of one inference forward: EVERY choice of kernels, made once from the handle, the batch, the precision and the
+// outputs wanted (the lab mask included: generic_path_mask, encoder_impl.h).  The stem and the layer walks below only run it.
+enum Conv1Kind { CONV1_DIRECT, CONV1_ASTAT, CONV1_GENERIC };
+enum Conv2Kind { CONV2_V4, CONV2_FULLN, CONV2_GENERIC };
+struct FwdWants {
+  bool last_hidden, last_token, hidden_slab, attn_slab;
+};
+struct FwdPlan {
+  Conv1Kind conv1;   // k_conv1_mel on the [B, mels, T] features themselves | transposition + A-stationary GEMM | + generic GEMM
+  Conv2Kind conv2;   // the eight-phase 256 x 256 GEMM over overlapping rows (gemm_v4.hip) | k_gemm_fulln | generic GEMM
+  bool shortcut;     // the stem's constant-tail shortcut: its compact conv1 / conv2 run in front of the direct conv1 and v4 conv2
+  bool x0_layer0;    // ... and layer 0 forms x in registers from what they left (k_mlp_fused<., ., true>): no k_stem_fill
+  bool astat;        // the A-stationary walk (K = d <= 512), else the generic one
+  bool mlp_fused;    // LN2 + fc1 + GELU + fc2 in k_mlp_fused
+  bool fuse_qkv;     // ... with the next layer's LN1 + q / k / v behind it
+  bool lnqkv0;       // layer 0's LN1 + q / k / v on the fused kernel's prologue + tail
+  bool op;           // out_proj in front of the fused block
+  bool fuse_final;   // the last block ends in the encoder's final LayerNorm and writes last_hidden
+  bool pooled;       // only the last token wanted: the last layer runs on B rows above its attention
+  bool q_log2;       // the LN-folded q panel carries log2(e) (pack_weights)
+};
+FwdPlan plan_forward(const gww_encoder* e, int batch, int precision, FwdWants want) {
   const gww_enc_cfg& c = e->cfg;
-  if (!e->stem_shortcut || precision != GWW_PREC_BF16 || batch <= 0 || (generic_mask & (2 | 4 | 2048))) return false;
-  if (!conv1_mel_supported(c.n_mels, c.d_model, conv1_kpad(c.n_mels)) || !stem_tail_supported(c.t_in, c.d_model)) return false;
-  const WsLayout w = ws_layout(c, batch, precision);
-  return stem_tail_layout(batch, c.d_model).total <= w.h - w.x2;
+  const int m = generic_path_mask(), d = c.d_model, F = c.ffn, T = c.t_in / 2;
+  const bool bf = precision == GWW_PREC_BF16;
+  FwdPlan p{};
+  // bf16, the widths of whisper-tiny / -base / -small / -medium: conv1_mel.hip (no token-major copy of the input, W-stationary, one launch)
+  p.conv1 = !bf || (m & GP_CONV1) ? CONV1_GENERIC
+            : conv1_mel_supported(c.n_mels, d, conv1_kpad(c.n_mels)) ? CONV1_DIRECT : d % 128 == 0 ? CONV1_ASTAT : CONV1_GENERIC;
+  p.conv2 = bf && d % 128 == 0 && d <= 3072 && !(m & GP_CONV2) ? CONV2_V4
+            : bf && (d == 384 || d == 512) && !(m & GP_CONV2_FULLN) ? CONV2_FULLN : CONV2_GENERIC;
+  const auto x2_bytes = [&] { const WsLayout w = ws_layout(c, batch, precision); return w.h - w.x2; };
+  p.shortcut = p.conv1 == CONV1_DIRECT && p.conv2 == CONV2_V4 && e->stem_shortcut && batch > 0 && !(m & GP_STEM_SHORTCUT) &&
+               stem_tail_supported(c.t_in, d) && stem_tail_layout(batch, d).total <= x2_bytes();
+  // d = 512 (whisper-base): since round 3 the LayerNorm kernel + the 256 x 256 GEMM (k_gemm_bf16_v3) beat the LN-fused
+  // A-stationary layer GEMMs there (8.78 against 9.33 ms per 64 segments; bit 9 of the mask brings them back)
+  p.astat = bf && (d == 384 || (d == 512 && (m & GP_ASTAT_512))) && F % 128 == 0 && !(m & GP_LAYER_GEMMS);
+  p.mlp_fused = p.astat && mlp_fused_supported(d, F) && !(m & GP_MLP);
+  p.fuse_qkv = p.mlp_fused && !(m & GP_QKV);
+  p.lnqkv0 = p.fuse_qkv && !(m & GP_LNQKV0);
+  p.op = p.fuse_qkv && !(m & GP_OUT_PROJ);   // (fuse_qkv: every block then leaves xc complete, no delta pending in front of the next)
+  p.fuse_final = p.op && want.last_hidden && !(m & GP_FINAL_LN);
+  // per-layer outputs wanted: every layer runs on all rows
+  p.pooled = bf && !want.last_hidden && want.last_token && T >= 3 && !(m & GP_POOLED) && !want.hidden_slab && !want.attn_slab;
+  // Layer 0 forms the residual stream itself where both of its launches are the fused ones and nothing else reads x before the
+  // block has rewritten it: the fill launch, its 0.59 GB store and the two 0.59 GB reads of it are gone.  Per-layer hidden
+  // states (tap_hidden reads x in HBM), a last or pooled layer 0 and the generic paths keep the fill.
+  p.x0_layer0 = p.shortcut && p.lnqkv0 && p.op && !want.hidden_slab && c.n_layers > 1;
+  p.q_log2 = attention_log2q_enabled();
+  return p;
 }
 }  // namespace
 
@@ -374,7 +417,7 @@ extern "C" int gww_encoder_stem_shortcut_flags(const gww_encoder* e, int batch, 
   size_t off = 0;
   for (int i = 0; i < 2 && b[i] > 0; ++i) {
     const WsLayout w = ws_layout(e->cfg, b[i], precision);
-    if (stem_shortcut_applies(e, b[i], precision))
+    if (plan_forward(e, b[i], precision, FwdWants{}).shortcut)
       GWW_HIP(hipMemcpy(&flags[i], (const char*)workspace + off + w.melT, sizeof(int), hipMemcpyDeviceToHost));
     off += w.total;
   }
@@ -423,15 +466,111 @@ struct Tracer {
     GWW_TRY(tr.end());       \
   } while (0)
 
+// One inference forward of one (half) batch: the plan, the carved workspace, the outputs and the launches every part shares.
+// hidden_slab / attn_slab (gww_encoder_forward_outputs): per-layer outputs, layer l at + l * hs_stride / as_stride
+// elements.  They only ADD stores and launches: every launch that feeds last_hidden is the one the plain forward makes.
+struct Fwd {
+  gww_encoder* e;
+  FwdPlan p;
+  Tracer tr;
+  hipStream_t s;
+  bool bf;
+  int B, d, F, T, H, n_layers;
+  long M;
+  void *melT, *c1, *h, *d2, *qkv, *ctx, *f1;
+  float *x, *x2;
+  // the compact stem's buffers (in x2) and flag (shortcut)
+  int* st_flag;
+  void* c1s;
+  float *xs, *st_tr, *st_dump;
+  MfX0 x0;
+  float *last_hidden, *last_token, *hidden_slab, *attn_slab;
+  size_t hs_stride, as_stride;
+  hipEvent_t skew_event;
+
+  // generic GEMM dispatch on precision
+  int gemm(const void* A, long lda, const void* W16, const float* W32, const float* bias, const float* resid, const float* pos,
+           void* Cout, long Mr, int N, int K, int epi, int rpb) const {
+    return bf ? launch_gemm_bf16(A, lda, W16, bias, resid, pos, Cout, Mr, N, K, epi, rpb, s, /*rows_padded_256=*/1)
+              : launch_gemm_f32((const float*)A, lda, W32, bias, resid, pos, (float*)Cout, Mr, N, K, epi, rpb, s);
+  }
+  // per-layer outputs: hidden_states[l] = the residual stream entering layer l (complete: no delta pending where it is
+  // tapped), attentions[l] = softmax of the q / k in qkv, read before the next launch overwrites qkv;
+  // hidden_states[L] = last_hidden (a copy unless the caller placed last_hidden in the slab)
+  int tap_hidden(int l, const float* src) const {
+    if (hidden_slab)
+      GWW_HIP(hipMemcpyAsync(hidden_slab + (size_t)l * hs_stride, src, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+    return GWW_OK;
+  }
+  int tap_attn(int l) const {
+    if (attn_slab) GWW_TRY(launch_attention_probs(qkv, bf, bf && p.q_log2, attn_slab + (size_t)l * as_stride, B, T, H, s));
+    return GWW_OK;
+  }
+  int tap_final() const {
+    float* dst = hidden_slab ? hidden_slab + (size_t)n_layers * hs_stride : nullptr;
+    if (dst && dst != last_hidden)
+      GWW_HIP(hipMemcpyAsync(dst, last_hidden, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
+    return GWW_OK;
+  }
+  int stem(const float* mel);
+  int walk_astat();
+  int walk_generic();
+  int pooled_last_layer(const LayerW& L, const float* x, float* rows, void* hb);
+  int final_layernorm(const float* xc, const void* pending);
+};
+
+// ---- stem.  The constant tail of a padded log-mel (stem_tail.hip): detection, then the stem on the first kStemTc frames and
+// the fill of x, all predicated on the device flag; the full stem stays enqueued behind them and returns at once when the flag
+// is 1, so it never reads the (then stale) c1.  One span per trace class: bench.py indexes its table by their names.
+int Fwd::stem(const float* mel) {
+  const int Tin = e->cfg.t_in, C = e->cfg.n_mels, Kc1 = conv1_kpad(C);
+  const size_t es = bf ? 2 : 4;
+  auto conv1_direct = [&]() -> int {
+    if (p.shortcut) {
+      GWW_TRY(launch_stem_detect(mel, st_flag, (long)B * C, Tin, s));
+      GWW_TRY(launch_conv1_mel(mel, e->c1w, e->c1b, c1s, B, kStemTc, d, s, Tin, st_flag, 1));
+    }
+    return launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s, 0, p.shortcut ? st_flag : nullptr, 0);
+  };
+  auto conv2_v4 = [&]() -> int {
+    const int Np = (d + 255) / 256 * 256;
+    if (p.shortcut) {
+      GWW_TRY(launch_gemm_bf16_v4(c1s, 2L * d, e->c2w, e->c2b, nullptr, xs, (long)B * (kStemTt + 1), Np, 3 * d, EPI_CONV2, s, 0,
+                                  e->pos_c, kStemTt + 1, d, st_dump, st_flag, 1, st_tr, kStemTt - 2));
+      if (!p.x0_layer0) GWW_TRY(launch_stem_fill(xs, st_tr, e->pos, x, st_flag, B, T, d, s));
+    }
+    return launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), Np, 3 * d, EPI_CONV2, s, 0, e->pos,
+                               T + 1, d, x + (((size_t)B * T + 255) / 256 * 256) * d, p.shortcut ? st_flag : nullptr, 0);
+  };
+  if (p.conv1 != CONV1_DIRECT) {   // the transposition kernel + a GEMM over its rows
+    TR(TR_MEL, launch_mel_to_tokens(mel, melT, bf ? 1 : 0, B, C, Tin, s));
+    GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * es, 0, Kc1 * es, s));
+    GWW_HIP(hipMemsetAsync(c1, 0, (size_t)d * es, s));   // zero row 0 of batch 0 (token -1)
+  }
+  if (p.conv1 == CONV1_DIRECT)
+    TR(TR_CONV1, conv1_direct());
+  else if (p.conv1 == CONV1_ASTAT)
+    TR(TR_CONV1, launch_gemm_astat(melT, C, nullptr, nullptr, nullptr, nullptr, e->c1w, e->c1b, c1,
+                                   (long)B * (Tin + 2), d, Kc1, EPI_CONV1, Tin + 2, s));
+  else
+    TR(TR_CONV1, gemm(melT, C, e->c1w, e->c1w32, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, Kc1,
+                      EPI_CONV1, Tin + 2));
+  if (p.conv2 == CONV2_V4)
+    TR(TR_CONV2, conv2_v4());
+  else if (p.conv2 == CONV2_FULLN)
+    TR(TR_CONV2, launch_gemm_fulln(c1, 2L * d, e->c2w, e->c2b, e->pos, x, (long)B * (T + 1), d, 3 * d, EPI_CONV2, T + 1, s));
+  else
+    TR(TR_CONV2, gemm(c1, 2L * d, e->c2w, e->c2w32, e->c2b, nullptr, e->pos, x, (long)B * (T + 1), d, 3 * d, EPI_CONV2,
+                      T + 1));
+  return GWW_OK;
+}
+
 // The last layer when only the last token is wanted (Signal_vs_Noise/src/model.py:25-26): everything above the last
 // attention is row-wise.  Attention for the one query tile that holds token T-1, then out_proj / LN2 / fc1 / GELU / fc2 /
 // final LayerNorm on the B last-token rows.  x: the complete residual stream entering the layer; rows: 3 x [B, d] fp32
-// of scratch (x rows (b, T-1) | x_mid | layer output); h: [B, d] bf16 of scratch.
-static int pooled_last_layer(gww_encoder* e, Tracer& tr, const LayerW& L, const float* x, const void* qkv, void* ctx,
-                             float* rows, void* h, void* f1, float* last_token, int B, bool q_log2) {
-  hipStream_t s = tr.s;
-  const int d = e->cfg.d_model, F = e->cfg.ffn, T = e->cfg.t_in / 2, H = e->cfg.n_heads;
-  TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, /*last_tile_only=*/true, q_log2));
+// of scratch (x rows (b, T-1) | x_mid | layer output); hb: [B, d] bf16 of scratch.
+int Fwd::pooled_last_layer(const LayerW& L, const float* x, float* rows, void* hb) {
+  TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, /*last_tile_only=*/true, p.q_log2));
   float* xl = rows;
   float* xm = rows + (size_t)B * d;
   float* xf = rows + 2 * (size_t)B * d;
@@ -439,15 +578,129 @@ static int pooled_last_layer(gww_encoder* e, Tracer& tr, const LayerW& L, const 
                            hipMemcpyDeviceToDevice, s));
   TR(TR_OUT, launch_gemm_bf16((const unsigned short*)ctx + (size_t)(T - 1) * d, (long)T * d, L.wo, L.bo, xl, nullptr,
                               xm, B, d, d, EPI_RESID, 0, s, 0));
-  TR(TR_LNROWS, launch_layernorm(xm, L.ln2w, L.ln2b, h, 1, B, d, s));
-  TR(TR_FC1, launch_gemm_bf16(h, d, L.w1, L.b1, nullptr, nullptr, f1, B, F, d, EPI_GELU, 0, s, 0));
+  TR(TR_LNROWS, launch_layernorm(xm, L.ln2w, L.ln2b, hb, 1, B, d, s));
+  TR(TR_FC1, launch_gemm_bf16(hb, d, L.w1, L.b1, nullptr, nullptr, f1, B, F, d, EPI_GELU, 0, s, 0));
   TR(TR_FC2, launch_gemm_bf16(f1, F, L.w2, L.b2, xm, nullptr, xf, B, d, F, EPI_RESID, 0, s, 0));
   TR(TR_LNROWS, launch_layernorm_rows(xf, d, e->lnw, e->lnb, last_token, B, d, s, nullptr));
   return GWW_OK;
 }
 
-// hidden_slab / attn_slab (gww_encoder_forward_outputs): per-layer outputs, layer l at + l * hs_stride / as_stride
-// elements.  They only ADD stores and launches: every launch that feeds last_hidden is the one the plain forward makes.
+// ---- final LayerNorm (HF:modeling_whisper.py:642), with the last pending delta folded in;
+// callers pool token T-1 (Signal_vs_Noise/src/model.py:25-26): that row alone is a fast output
+int Fwd::final_layernorm(const float* xc, const void* pending) {
+  if (last_hidden) TR(TR_LN, launch_layernorm(xc, e->lnw, e->lnb, last_hidden, 0, M, d, s, pending));
+  if (last_token)
+    TR(TR_LNROWS, launch_layernorm_rows(xc + (long)(T - 1) * d, (long)T * d, e->lnw, e->lnb, last_token, B, d, s,
+                                        pending ? (const char*)pending + (size_t)(T - 1) * d * 2 : nullptr));
+  if (last_hidden) GWW_TRY(tap_final());
+  return GWW_OK;
+}
+
+// ---- the A-stationary walk (bf16, K = d <= 512: A panel in registers, fused residual-add + LayerNorm prologue).
+// Deferred residual: out_proj / fc2 emit a bf16 delta; the NEXT LayerNorm prologue does x_new = x + delta (written to the
+// spare buffer), LN(x_new) -> GEMM operand.  What survives an iteration:
+struct AstatState {
+  float* xc;             // the residual stream, complete but for `pending`
+  float* xn;             // the spare buffer: whoever adds a delta to xc writes the sum here (x_new), then swap()
+  const void* pending;   // bf16 delta not yet added to xc
+  bool qkv_ready;        // the previous block already left this layer's q / k / v in qkv (then nothing is pending)
+  void swap() { std::swap(xc, xn); }
+};
+
+int Fwd::walk_astat() {
+  AstatState st{x, x2, nullptr, false};
+  void* const d1 = h;   // out_proj delta, where it is a launch of its own
+  auto args = [&]() { MlpFusedArgs a; a.who = "gww_encoder_forward"; a.M = M; a.d = d; return a; };
+  auto with_qkv = [&](MlpFusedArgs& a, const LayerW& W) { a.qkv_u = W.uqkv; a.qkv_cb = W.cbqkv; a.qkv_out = qkv; a.NQ = 3 * d; };
+  for (int i = 0; i < n_layers; ++i) {
+    const LayerW& L = e->layers[i];
+    const bool last = i == n_layers - 1, from_x0 = i == 0 && p.x0_layer0;
+    // -- q / k / v, unless the previous block made it
+    if (!st.qkv_ready) {
+      if (i == 0 && p.lnqkv0) {
+        // layer 0 (no delta pending behind the conv stem): the fused kernel's panel prologue + q / k / v tail
+        MlpFusedArgs a = args();
+        a.x = st.xc; a.Wt = L.wqkv_st;
+        with_qkv(a, L);
+        if (from_x0) a.x0 = &x0;
+        TR(TR_QKV, launch_mlp_fused(a, s));
+      } else {
+        TR(TR_QKV, launch_gemm_astat(st.xc, d, st.pending, st.pending ? st.xn : nullptr, L.uqkv, L.cbqkv, L.wqkv_ln, nullptr, qkv,
+                                     M, 3 * d, d, EPI_BIAS, 0, s));
+        if (st.pending) st.swap();
+        st.pending = nullptr;
+      }
+    }
+    st.qkv_ready = false;
+    // (xc is complete here: the q / k / v step folded any pending delta in; the spare buffer is free)
+    GWW_TRY(tap_hidden(i, st.xc));
+    if (i == 0 && skew_event) GWW_HIP(hipEventRecord(skew_event, s));   // the other half batch starts here
+    if (p.pooled && last) return pooled_last_layer(L, st.xc, st.xn, d1);
+    // -- attention
+    TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, p.q_log2));
+    GWW_TRY(tap_attn(i));   // before the fused block below writes the next layer's q / k / v over qkv
+    // -- one block step.  p.op: out_proj fused in front of the MLP block (ctx is the A operand of a GEMM into the block's idle
+    // output accumulators; the bf16 delta never reaches HBM); it needs no delta pending on xc, which fuse_qkv guarantees
+    if (!p.op)
+      TR(TR_OUT, launch_gemm_astat(ctx, d, nullptr, nullptr, nullptr, nullptr, L.wo, L.bo, d1, M, d, d, EPI_BIAS, 0, s));
+    // (layer 0 behind the compact stem forms x in registers and has no x_new: xs / tr live in that buffer until it has run)
+    MlpFusedArgs a = args();
+    a.x = st.xc; a.x_new = from_x0 ? nullptr : st.xn; a.ln_u = L.u1; a.ln_cb = L.cb1; a.b2 = L.b2; a.F = F;
+    if (p.op) { a.ctx = ctx; a.bo = L.bo; a.Wt = L.wmlp_op; }
+    else { a.delta = d1; a.Wt = L.wmlp; }
+    if (p.fuse_qkv && !last) {
+      // fused + the next layer's LN1 + q / k / v: x_next comes back in xc itself (xn only held x_new), no delta is pending
+      with_qkv(a, e->layers[i + 1]);
+      if (from_x0) a.x0 = &x0;
+      TR(TR_MLPQKV, launch_mlp_fused(a, s));
+      st.qkv_ready = true;
+    } else if (p.fuse_final) {
+      // the LAST block with the encoder's final LayerNorm as its epilogue: last_hidden_state comes straight out of the
+      // kernel (no bf16 delta, no second read of the residual stream, no LayerNorm launch); the pooled token is row
+      // T - 1 of it
+      a.lnf_w = e->lnw; a.lnf_b = e->lnb; a.y = last_hidden;
+      TR(TR_MLPFIN, launch_mlp_fused(a, s));
+      if (last_token)
+        GWW_HIP(hipMemcpy2DAsync(last_token, (size_t)d * 4, last_hidden + (size_t)(T - 1) * d, (size_t)T * d * 4, (size_t)d * 4,
+                                 B, hipMemcpyDeviceToDevice, s));
+      return tap_final();
+    } else if (p.mlp_fused) {
+      // fused plain: LN2 + fc1 + GELU + fc2 in one kernel, the [M, ffn] activation never leaves the CU
+      a.C = d2; a.keep_x_new = true;   // (x_new becomes the residual stream)
+      TR(TR_MLP, launch_mlp_fused(a, s));
+      st.swap();
+      st.pending = d2;
+    } else {
+      TR(TR_FC1, launch_gemm_astat(st.xc, d, d1, st.xn, L.u1, L.cb1, L.w1_ln, nullptr, f1, M, F, d, EPI_GELU, 0, s));
+      st.swap();
+      TR(TR_FC2, launch_gemm_fulln(f1, F, L.w2, L.b2, nullptr, d2, M, d, F, EPI_BIAS, 0, s));
+      st.pending = d2;
+    }
+  }
+  return final_layernorm(st.xc, st.pending);
+}
+
+// ---- the generic walk: fp32, and the bf16 widths without A-stationary kernels (e.g. whisper-small)
+int Fwd::walk_generic() {
+  for (int i = 0; i < n_layers; ++i) {
+    const LayerW& L = e->layers[i];
+    GWW_TRY(tap_hidden(i, x));
+    TR(TR_LN, launch_layernorm(x, L.ln1w, L.ln1b, h, bf ? 1 : 0, M, d, s));
+    TR(TR_QKV, gemm(h, d, L.wqkv, L.wqkv32, bf ? L.bqkv16 : L.bqkv, nullptr, nullptr, qkv, M, 3 * d, d, EPI_BIAS, 0));
+    if (p.pooled && i == n_layers - 1) return pooled_last_layer(L, x, x2, h);
+    if (bf) TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, p.q_log2));
+    else TR(TR_ATTN, launch_attention_f32((const float*)qkv, (float*)ctx, B, T, H, s));
+    GWW_TRY(tap_attn(i));
+    TR(TR_OUT, gemm(ctx, d, L.wo, L.wo32, L.bo, x, nullptr, x, M, d, d, EPI_RESID, 0));
+    TR(TR_LN, launch_layernorm(x, L.ln2w, L.ln2b, h, bf ? 1 : 0, M, d, s));
+    TR(TR_FC1, gemm(h, d, L.w1, L.w132, L.b1, nullptr, nullptr, f1, M, F, d, EPI_GELU, 0));
+    TR(TR_FC2, gemm(f1, F, L.w2, L.w232, L.b2, x, nullptr, x, M, d, F, EPI_RESID, 0));
+  }
+  return final_layernorm(x, nullptr);
+}
+#undef TR
+
+// the argument checks and the workspace carve-up; the stem and the layer walks run the plan and decide nothing themselves
 static int forward_impl(gww_encoder* e, const float* mel, int batch, int precision, void* workspace,
                         size_t workspace_bytes, float* last_hidden, float* last_token, void* stream,
                         hipEvent_t skew_event = nullptr, float* hidden_slab = nullptr, float* attn_slab = nullptr,
@@ -465,227 +718,28 @@ static int forward_impl(gww_encoder* e, const float* mel, int batch, int precisi
   if (!workspace || workspace_bytes < w.total)
     return fail(GWW_ERR_WORKSPACE, "gww_encoder_forward: workspace %zu bytes < required %zu", workspace_bytes,
                 w.total);
-  hipStream_t s = (hipStream_t)stream;
-  const bool bf = precision == GWW_PREC_BF16;
-  const size_t es = bf ? 2 : 4;
-  const int d = e->cfg.d_model, F = e->cfg.ffn, Tin = e->cfg.t_in, T = Tin / 2, C = e->cfg.n_mels, H = e->cfg.n_heads;
-  const int Kc1 = conv1_kpad(C);
-  const int B = batch;
+  const gww_enc_cfg& c = e->cfg;
   char* base = (char*)workspace;
-  void* melT = base + w.melT;
-  void* c1 = base + w.c1;
-  float* x = (float*)(base + w.x);
-  void* h = base + w.h;
-  void* qkv = base + w.qkv;
-  void* ctx = base + w.ctx;
-  void* f1 = base + w.f1;
-  const long M = (long)B * T;
-
-  Tracer tr{e, s};
-
-  // generic GEMM dispatch on precision
-  auto gemm = [&](const void* A, long lda, const void* W16, const float* W32, const float* bias,
-                  const float* resid, const float* pos, void* Cout, long Mr, int N, int K, int epi,
-                  int rpb) -> int {
-    return bf ? launch_gemm_bf16(A, lda, W16, bias, resid, pos, Cout, Mr, N, K, epi, rpb, s, /*rows_padded_256=*/1)
-              : launch_gemm_f32((const float*)A, lda, W32, bias, resid, pos, (float*)Cout, Mr, N, K, epi, rpb, s);
-  };
-
-  // ---- stem
-  // bf16, 80 mels at the widths of whisper-tiny / -base / -small / -medium: conv1 reads the [B, 80, T] features itself (conv1_mel.hip:
-  // no token-major copy of the input, W-stationary, one launch); otherwise the transposition kernel + a GEMM over its rows
-  static const int generic_mask = (int)lab_int("GWW_GENERIC_PATH", 0);   // (0 in the product build)
-  const bool conv1_direct = bf && conv1_mel_supported(C, d, Kc1) && !(generic_mask & 2);
-  if (!conv1_direct) {
-    TR(TR_MEL, launch_mel_to_tokens(mel, melT, bf ? 1 : 0, B, C, Tin, s));
-    GWW_HIP(hipMemsetAsync((char*)melT + (size_t)B * (Tin + 2) * C * es, 0, Kc1 * es, s));
-    GWW_HIP(hipMemsetAsync(c1, 0, (size_t)d * es, s));   // zero row 0 of batch 0 (token -1)
-  }
-  // A-stationary kernels (A panel in registers, fused residual-add + LayerNorm prologue) for K = d <= 512
-  // GWW_GENERIC_PATH (debug aid): bit 0 = generic layer GEMMs, bit 1 = generic conv1, bit 2 = generic conv2, bit 3 = unfused MLP,
-  // bit 4 = stand-alone QKV, bit 5 = no pooled last layer, bit 6 = layer 0's LN1 + QKV by the LN-fused A-stationary GEMM, bit 7 = stand-alone out_proj, bit 8 = stand-alone final LayerNorm, bit 9 = A-stationary layer GEMMs at d = 512, bit 10 = conv2 on the generic GEMM where k_gemm_fulln would take it, bit 11 = no constant-tail shortcut of the stem
-  // d = 512 (whisper-base): since round 3 the LayerNorm kernel + the 256 x 256 GEMM (k_gemm_bf16_v3) beat the LN-fused
-  // A-stationary layer GEMMs there (8.78 against 9.33 ms per 64 segments; bit 9 of the mask brings them back)
-  const bool astat = bf && (d == 384 || (d == 512 && (generic_mask & 512))) && F % 128 == 0 && !(generic_mask & 1);
-  const bool mlp_fused = astat && d == 384 && F <= 1536 && !(generic_mask & 8);   // bit 3 = separate fc1 / fc2 kernels
-  const bool fuse_qkv = mlp_fused && !(generic_mask & 16);                          // bit 4 = stand-alone LN1 + QKV kernels
-  bool qkv_done = false;
-  // only the last token wanted: the last layer runs on B rows above its attention (bit 5 of the mask disables it)
-  const bool outs = hidden_slab || attn_slab;   // per-layer outputs wanted: every layer runs on all rows
-  const bool pooled = astat && !last_hidden && last_token && T >= 3 && !(generic_mask & 32) && !outs;
-  // The constant tail of a padded log-mel (stem_tail.hip): detection, then the stem on the first kStemTc frames and the fill
-  // of x, all predicated on the device flag; the full stem stays enqueued behind them and returns at once when the flag is 1,
-  // so it never reads the (then stale) c1.  One span per trace class: bench.py indexes its table by their names.
-  const bool shortcut = conv1_direct && stem_shortcut_applies(e, B, precision);
-  int* const st_flag = (int*)melT;
-  const StemTailLayout st = stem_tail_layout(B, d);
+  const StemTailLayout st = stem_tail_layout(batch, c.d_model);
   char* const st_base = base + w.x2;
-  void* const c1s = st_base + st.c1s;
-  float* const xs = (float*)(st_base + st.xs);
-  float* const st_tr = (float*)(st_base + st.tr);
-  // Layer 0 forms the residual stream itself (k_mlp_fused_x0: its LN1 + q / k / v launch in registers, its block in the
-  // accumulators) where both of its launches are the fused ones and nothing else reads x before the block has rewritten it:
-  // the fill launch, its 0.59 GB store and the two 0.59 GB reads of it are gone.  Per-layer hidden states (tap_hidden reads x
-  // in HBM), a last or pooled layer 0 and the generic paths keep the fill.  xs / tr live in x2, the block's x_new buffer: they
-  // survive until layer 0's block has read them because no launch on this path keeps x_new (launch_mlp_fused_x0 never does,
-  // and the later blocks run with keep_x_new = false).
-  const bool x0_layer0 = shortcut && mlp_fused && fuse_qkv && !(generic_mask & (64 | 128)) && !hidden_slab && e->cfg.n_layers > 1;
-  auto stem_conv1 = [&]() -> int {
-    if (shortcut) {
-      GWW_TRY(launch_stem_detect(mel, st_flag, (long)B * C, Tin, s));
-      GWW_TRY(launch_conv1_mel(mel, e->c1w, e->c1b, c1s, B, kStemTc, d, s, Tin, st_flag, 1));
-    }
-    return launch_conv1_mel(mel, e->c1w, e->c1b, c1, B, Tin, d, s, 0, shortcut ? st_flag : nullptr, 0);
-  };
-  auto stem_conv2 = [&]() -> int {
-    const int Np = (d + 255) / 256 * 256;
-    if (shortcut) {
-      GWW_TRY(launch_gemm_bf16_v4(c1s, 2L * d, e->c2w, e->c2b, nullptr, xs, (long)B * (kStemTt + 1), Np, 3 * d, EPI_CONV2, s, 0,
-                                  e->pos_c, kStemTt + 1, d, (float*)(st_base + st.dump), st_flag, 1, st_tr, kStemTt - 2));
-      if (!x0_layer0) GWW_TRY(launch_stem_fill(xs, st_tr, e->pos, x, st_flag, B, T, d, s));
-    }
-    return launch_gemm_bf16_v4(c1, 2L * d, e->c2w, e->c2b, nullptr, x, (long)B * (T + 1), Np, 3 * d, EPI_CONV2, s, 0, e->pos,
-                               T + 1, d, x + (((size_t)B * T + 255) / 256 * 256) * d, shortcut ? st_flag : nullptr, 0);
-  };
-  if (conv1_direct)
-    TR(TR_CONV1, stem_conv1());
-  else if (bf && d % 128 == 0 && !(generic_mask & 2))
-    TR(TR_CONV1, launch_gemm_astat(melT, C, nullptr, nullptr, nullptr, nullptr, e->c1w, e->c1b, c1,
-                                   (long)B * (Tin + 2), d, Kc1, EPI_CONV1, Tin + 2, s));
-  else
-    TR(TR_CONV1, gemm(melT, C, e->c1w, e->c1w32, e->c1b, nullptr, nullptr, c1, (long)B * (Tin + 2), d, Kc1,
-                      EPI_CONV1, Tin + 2));
-  if (bf && d % 128 == 0 && d <= 3072 && !(generic_mask & 4))   // the eight-phase 256 x 256 GEMM over overlapping rows (gemm_v4.hip)
-    TR(TR_CONV2, stem_conv2());
-  else if (bf && (d == 384 || d == 512) && !(generic_mask & 1024))
-    TR(TR_CONV2, launch_gemm_fulln(c1, 2L * d, e->c2w, e->c2b, e->pos, x, (long)B * (T + 1), d, 3 * d, EPI_CONV2, T + 1, s));
-  else
-    TR(TR_CONV2, gemm(c1, 2L * d, e->c2w, e->c2w32, e->c2b, nullptr, e->pos, x, (long)B * (T + 1), d, 3 * d, EPI_CONV2,
-                      T + 1));
-  const bool q_log2 = attention_log2q_enabled();   // the LN-folded q panel carries log2(e) (pack_weights)
-  float* xc = x;                       // current residual stream
-  // per-layer outputs: hidden_states[l] = the residual stream entering layer l (complete: no delta pending where it is
-  // tapped), attentions[l] = softmax of the q / k in qkv, read before the next launch overwrites qkv;
-  // hidden_states[L] = last_hidden (a copy unless the caller placed last_hidden in the slab)
-  auto tap_hidden = [&](int l, const float* src) -> int {
-    if (hidden_slab)
-      GWW_HIP(hipMemcpyAsync(hidden_slab + (size_t)l * hs_stride, src, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
-    return GWW_OK;
-  };
-  auto tap_attn = [&](int l) -> int {
-    if (attn_slab) GWW_TRY(launch_attention_probs(qkv, bf, bf && q_log2, attn_slab + (size_t)l * as_stride, B, T, H, s));
-    return GWW_OK;
-  };
-  auto tap_final = [&]() -> int {
-    float* dst = hidden_slab ? hidden_slab + (size_t)e->cfg.n_layers * hs_stride : nullptr;
-    if (dst && dst != last_hidden)
-      GWW_HIP(hipMemcpyAsync(dst, last_hidden, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
-    return GWW_OK;
-  };
-  const void* pending = nullptr;       // bf16 delta not yet added to xc (A-stationary path)
-  if (astat) {
-    // Deferred residual: out_proj / fc2 emit a bf16 delta; the NEXT LayerNorm prologue does
-    // x_new = x + delta (written to the ping-pong buffer), LN(x_new) -> GEMM operand.
-    float* xn = (float*)(base + w.x2);
-    void* d1 = h;
-    void* d2 = base + w.d2;
-    for (int i = 0; i < e->cfg.n_layers; ++i) {
-      const LayerW& L = e->layers[i];
-      if (!qkv_done) {
-        if (i == 0 && !pending && fuse_qkv && !(generic_mask & 64)) {
-          // layer 0 (no delta pending behind the conv stem): the fused kernel's panel prologue + q / k / v tail
-          if (x0_layer0)
-            TR(TR_QKV, launch_lnqkv_fused_x0(xs, st_tr, e->pos, st_flag, xc, T, kStemTt, L.uqkv, L.cbqkv, L.wqkv_st, qkv, M, d,
-                                             3 * d, s));
-          else
-            TR(TR_QKV, launch_lnqkv_fused(xc, L.uqkv, L.cbqkv, L.wqkv_st, qkv, M, d, 3 * d, s));
-        } else {
-          TR(TR_QKV, launch_gemm_astat(xc, d, pending, pending ? xn : nullptr, L.uqkv, L.cbqkv, L.wqkv_ln, nullptr, qkv, M,
-                                       3 * d, d, EPI_BIAS, 0, s));
-          if (pending) { float* t = xc; xc = xn; xn = t; }
-        }
-      }
-      qkv_done = false;
-      GWW_TRY(tap_hidden(i, xc));   // (the q / k / v step above folded any pending delta into xc)
-      if (i == 0 && skew_event) GWW_HIP(hipEventRecord(skew_event, s));   // the other half batch starts here
-      // (xc is complete here: the QKV prologue folded the pending delta in; the ping-pong buffer is free now)
-      if (pooled && i == e->cfg.n_layers - 1) return pooled_last_layer(e, tr, L, xc, qkv, ctx, xn, d1, f1, last_token, B, q_log2);
-      TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, q_log2));
-      GWW_TRY(tap_attn(i));   // before the fused block below writes the next layer's q / k / v over qkv
-      // out_proj fused in front of the MLP block (ctx is the A operand of a GEMM into the block's idle output
-      // accumulators; the bf16 delta never reaches HBM): needs no delta pending on xc, which holds on this path
-      const bool op = mlp_fused && fuse_qkv && !pending && !(generic_mask & 128);
-      if (!op)
-        TR(TR_OUT, launch_gemm_astat(ctx, d, nullptr, nullptr, nullptr, nullptr, L.wo, L.bo, d1, M, d, d, EPI_BIAS, 0, s));
-      if (mlp_fused && fuse_qkv && i + 1 < e->cfg.n_layers) {
-        // ... and the next layer's LN1 + q / k / v projection appended: xn receives x_next (no delta pending)
-        const LayerW& Ln = e->layers[i + 1];
-        // (x_next comes back in xc itself: xn only holds x_new, the block's intermediate residual stream)
-        if (i == 0 && x0_layer0 && op)   // (x0_layer0 implies op: no delta is pending behind launch_lnqkv_fused_x0)
-          TR(TR_MLPQKV, launch_mlp_fused_x0(xs, st_tr, e->pos, st_flag, xc, T, kStemTt, ctx, L.bo, L.u1, L.cb1, L.wmlp_op, L.b2, M, d,
-                                            F, Ln.uqkv, Ln.cbqkv, qkv, 3 * d, s));
-        else
-        TR(TR_MLPQKV, launch_mlp_fused(xc, op ? ctx : d1, xn, L.u1, L.cb1, op ? L.wmlp_op : L.wmlp, L.b2, nullptr, M, d, F, s,
-                                       Ln.uqkv, Ln.cbqkv, qkv, 3 * d, nullptr, op ? L.bo : nullptr, /*keep_x_new=*/false));
-        pending = nullptr;
-        qkv_done = true;
-        continue;
-      }
-      static const bool fuse_final = !(lab_int("GWW_GENERIC_PATH", 0) & 256);   // bit 8: stand-alone final LayerNorm
-      if (mlp_fused && op && fuse_final && i == e->cfg.n_layers - 1 && last_hidden) {
-        // the LAST block with the encoder's final LayerNorm as its epilogue: last_hidden_state comes straight out of the
-        // kernel (no bf16 delta, no second read of the residual stream, no LayerNorm launch); the pooled token is row
-        // T - 1 of it
-        TR(TR_MLPFIN, launch_mlp_fused_final(xc, ctx, xn, L.u1, L.cb1, L.wmlp_op, L.b2, L.bo, e->lnw, e->lnb, last_hidden, M, d,
-                                             F, s, /*keep_x_new=*/false));
-        if (last_token)
-          GWW_HIP(hipMemcpy2DAsync(last_token, (size_t)d * 4, last_hidden + (size_t)(T - 1) * d, (size_t)T * d * 4, (size_t)d * 4,
-                                   B, hipMemcpyDeviceToDevice, s));
-        GWW_TRY(tap_final());
-        return GWW_OK;
-      }
-      if (mlp_fused) {
-        // LN2 + fc1 + GELU + fc2 in one kernel: the [M, ffn] activation never leaves the CU
-        TR(TR_MLP, launch_mlp_fused(xc, op ? ctx : d1, xn, L.u1, L.cb1, op ? L.wmlp_op : L.wmlp, L.b2, d2, M, d, F, s, nullptr,
-                                    nullptr, nullptr, 0, nullptr, op ? L.bo : nullptr));
-        { float* t = xc; xc = xn; xn = t; }
-      } else {
-        TR(TR_FC1, launch_gemm_astat(xc, d, d1, xn, L.u1, L.cb1, L.w1_ln, nullptr, f1, M, F, d, EPI_GELU, 0, s));
-        { float* t = xc; xc = xn; xn = t; }
-        TR(TR_FC2, launch_gemm_fulln(f1, F, L.w2, L.b2, nullptr, d2, M, d, F, EPI_BIAS, 0, s));
-      }
-      pending = d2;
-    }
-  } else {
-    // only the last token wanted (bf16 generic path, e.g. whisper-small): same pooled last layer as above
-    const bool pooled_g = bf && !last_hidden && last_token && T >= 3 && !(generic_mask & 32) && !outs;
-    for (int i = 0; i < e->cfg.n_layers; ++i) {
-      const LayerW& L = e->layers[i];
-      GWW_TRY(tap_hidden(i, x));
-      TR(TR_LN, launch_layernorm(x, L.ln1w, L.ln1b, h, bf ? 1 : 0, M, d, s));
-      TR(TR_QKV, gemm(h, d, L.wqkv, L.wqkv32, bf ? L.bqkv16 : L.bqkv, nullptr, nullptr, qkv, M, 3 * d, d, EPI_BIAS, 0));
-      if (pooled_g && i == e->cfg.n_layers - 1)
-        return pooled_last_layer(e, tr, L, x, qkv, ctx, (float*)(base + w.x2), h, f1, last_token, B, q_log2);
-      if (bf) TR(TR_ATTN, launch_attention_bf16(qkv, ctx, B, T, H, s, nullptr, false, q_log2));
-      else TR(TR_ATTN, launch_attention_f32((const float*)qkv, (float*)ctx, B, T, H, s));
-      GWW_TRY(tap_attn(i));
-      TR(TR_OUT, gemm(ctx, d, L.wo, L.wo32, L.bo, x, nullptr, x, M, d, d, EPI_RESID, 0));
-      TR(TR_LN, launch_layernorm(x, L.ln2w, L.ln2b, h, bf ? 1 : 0, M, d, s));
-      TR(TR_FC1, gemm(h, d, L.w1, L.w132, L.b1, nullptr, nullptr, f1, M, F, d, EPI_GELU, 0));
-      TR(TR_FC2, gemm(f1, F, L.w2, L.w232, L.b2, x, nullptr, x, M, d, F, EPI_RESID, 0));
-    }
-  }
-  // ---- final LayerNorm (HF:modeling_whisper.py:642), with the last pending delta folded in;
-  // callers pool token T-1 (Signal_vs_Noise/src/model.py:25-26): that row alone is a fast output
-  if (last_hidden) TR(TR_LN, launch_layernorm(xc, e->lnw, e->lnb, last_hidden, 0, M, d, s, pending));
-  if (last_token)
-    TR(TR_LNROWS, launch_layernorm_rows(xc + (long)(T - 1) * d, (long)T * d, e->lnw, e->lnb, last_token, B, d, s,
-                                    pending ? (const char*)pending + (size_t)(T - 1) * d * 2 : nullptr));
-  if (last_hidden) GWW_TRY(tap_final());
-  return GWW_OK;
+  Fwd f{};
+  f.e = e;
+  f.p = plan_forward(e, batch, precision, {last_hidden != nullptr, last_token != nullptr, hidden_slab != nullptr, attn_slab != nullptr});
+  f.s = (hipStream_t)stream;
+  f.tr = Tracer{e, f.s};
+  f.bf = precision == GWW_PREC_BF16;
+  f.B = batch; f.d = c.d_model; f.F = c.ffn; f.T = c.t_in / 2; f.H = c.n_heads; f.n_layers = c.n_layers;
+  f.M = (long)batch * f.T;
+  f.melT = base + w.melT; f.c1 = base + w.c1; f.h = base + w.h; f.d2 = base + w.d2; f.qkv = base + w.qkv; f.ctx = base + w.ctx;
+  f.f1 = base + w.f1; f.x = (float*)(base + w.x); f.x2 = (float*)(base + w.x2);
+  f.st_flag = (int*)f.melT; f.c1s = st_base + st.c1s; f.xs = (float*)(st_base + st.xs); f.st_tr = (float*)(st_base + st.tr);
+  f.st_dump = (float*)(st_base + st.dump);
+  f.x0 = MfX0{f.xs, f.st_tr, e->pos, f.st_flag, f.T, kStemTt};
+  f.last_hidden = last_hidden; f.last_token = last_token; f.hidden_slab = hidden_slab; f.attn_slab = attn_slab;
+  f.hs_stride = hs_stride; f.as_stride = as_stride; f.skew_event = skew_event;
+  GWW_TRY(f.stem(mel));
+  return f.p.astat ? f.walk_astat() : f.walk_generic();
 }
-#undef TR
-
 
 // the plain forward and gww_encoder_forward_outputs: with the split on, both slabs are offset for the second half as
 // last_hidden is (their layer strides stay those of the full batch)

@@ -22,7 +22,7 @@ struct LayerW {
   // LayerNorm-folded panels for the A-stationary GEMMs (gain folded into W, see gemm_astat.hip)
   unsigned short *wqkv_ln, *w1_ln;
   unsigned short* wmlp;   // fused-MLP weight stream (d = 384): mlp_fused.hip
-  unsigned short* wqkv_st; // the folded q / k / v panel alone as a tile stream (layer 0: launch_lnqkv_fused)
+  unsigned short* wqkv_st; // the folded q / k / v panel alone as a tile stream (layer 0: LN1 + q / k / v alone)
   unsigned short* wmlp_op; // the fused-MLP stream with the W_o tiles in front (inference: out_proj fused into the block)
   float *uqkv, *cbqkv, *u1, *cb1;
   // transposed bf16 panels [K][N] for the dX GEMMs of the training backward
@@ -48,6 +48,27 @@ struct SavedArena {
   }
   const float* x_in_at(const void* saved, int l) const { return x_in_at(const_cast<void*>(saved), l); }
 };
+
+// GWW_GENERIC_PATH, the laboratory build's debug mask of the host drivers (0 in the product build, read once per process):
+// each bit takes one fast path out.  Read it through generic_path_mask() alone.
+enum : int {
+  GP_LAYER_GEMMS = 1,      // bit 0: generic layer GEMMs (no A-stationary kernels)
+  GP_CONV1 = 2,            // bit 1: generic conv1
+  GP_CONV2 = 4,            // bit 2: conv2 off k_gemm_bf16_v4
+  GP_MLP = 8,              // bit 3: unfused MLP (separate fc1 / fc2 kernels)
+  GP_QKV = 16,             // bit 4: stand-alone LN1 + q / k / v kernels
+  GP_POOLED = 32,          // bit 5: no pooled last layer
+  GP_LNQKV0 = 64,          // bit 6: layer 0's LN1 + q / k / v by the LN-fused A-stationary GEMM
+  GP_OUT_PROJ = 128,       // bit 7: stand-alone out_proj (inference, training forward; with bit 4: the packer's plain stream)
+  GP_FINAL_LN = 256,       // bit 8: stand-alone final LayerNorm
+  GP_ASTAT_512 = 512,      // bit 9: A-stationary layer GEMMs at d = 512
+  GP_CONV2_FULLN = 1024,   // bit 10: conv2 on the generic GEMM where k_gemm_fulln would take it
+  GP_STEM_SHORTCUT = 2048, // bit 11: no constant-tail shortcut of the stem
+};
+inline int generic_path_mask() {
+  static const int mask = (int)lab_int("GWW_GENERIC_PATH", 0);
+  return mask;
+}
 
 }  // namespace gww
 

@@ -66,7 +66,7 @@ TrainWs train_ws(const gww_enc_cfg& c, int B) {
 // d = 384: the training forward runs on the fused inference kernels (GWW_TRAIN_FUSED=0: the per-op forward of round 1)
 static bool train_fused(const gww_enc_cfg& c) {
   static const bool off = lab_int("GWW_TRAIN_FUSED", 1) == 0;
-  return !off && c.d_model == 384 && c.ffn % 128 == 0 && c.ffn <= 1536;
+  return !off && mlp_fused_supported(c.d_model, c.ffn);
 }
 
 // full fine-tuning: behind the backward's workspace, the partial slabs of the weight-gradient GEMMs and of the LayerNorm
@@ -189,7 +189,10 @@ extern "C" int gww_encoder_train_forward(gww_encoder* e, const float* mel, int b
       if (l == 0) {
         // layer 0: LN1 + q / k / v on the fused block's panel prologue + tail (k_mlp_fused<2, false>), as the inference
         // forward does (round 3 ran the LayerNorm kernel + the plain A-stationary GEMM here: 41 + 112 us at 64 segments)
-        GWW_TRY(launch_lnqkv_fused(sl.x_in_at(sv, 0), W.uqkv, W.cbqkv, W.wqkv_st, qkv, M, d, 3 * d, s));
+        MlpFusedArgs a;
+        a.who = "gww_encoder_train_forward"; a.x = sl.x_in_at(sv, 0); a.Wt = W.wqkv_st; a.M = M; a.d = d;
+        a.qkv_u = W.uqkv; a.qkv_cb = W.cbqkv; a.qkv_out = qkv; a.NQ = 3 * d;
+        GWW_TRY(launch_mlp_fused(a, s));
       }
       if (pooled && l == L - 1) {
         // only the query tile that holds token T - 1 is needed (forward and backward): the other rows of ctx / lse stay
@@ -202,21 +205,24 @@ extern "C" int gww_encoder_train_forward(gww_encoder* e, const float* mel, int b
       }
       GWW_TRY(launch_attention_bf16(qkv, ctx, B, T, H, s, lse, false, q_log2));
       // out_proj fused in front of the block as on the inference path: x_mid = x_in + bf16(ctx W_o^T + bo) comes out of
-      // the kernel's seam (the backward needs ctx and x_mid, never the delta)
-      static const bool op = !(lab_int("GWW_GENERIC_PATH", 0) & 128);
-      if (!op)
+      // the kernel's seam and is kept (the backward needs ctx and x_mid, never the delta)
+      MlpFusedArgs a;
+      a.who = "gww_encoder_train_forward"; a.x = sl.x_in_at(sv, l); a.x_new = x_mid; a.keep_x_new = true;
+      a.ln_u = W.u1; a.ln_cb = W.cb1; a.b2 = W.b2; a.M = M; a.d = d; a.F = F;
+      if (generic_path_mask() & GP_OUT_PROJ) {
         GWW_TRY(launch_gemm_astat(ctx, d, nullptr, nullptr, nullptr, nullptr, W.wo, W.bo, d1, M, d, d, EPI_BIAS, 0, s));
-      const void* a2 = op ? (const void*)ctx : (const void*)d1;
-      const void* st2 = op ? W.wmlp_op : W.wmlp;
-      const float* bo2 = op ? W.bo : nullptr;
-      if (l + 1 < L) {
-        const LayerW& Wn = e->layers[l + 1];
-        void* qkv_n = sv + (size_t)(l + 1) * sl.layer_stride + sl.qkv;
-        GWW_TRY(launch_mlp_fused(sl.x_in_at(sv, l), a2, x_mid, W.u1, W.cb1, st2, W.b2, nullptr, M, d, F, s, Wn.uqkv, Wn.cbqkv, qkv_n,
-                                 3 * d, sl.x_in_at(sv, l + 1), bo2));
+        a.delta = d1; a.Wt = W.wmlp;
       } else {
-        GWW_TRY(launch_mlp_fused(sl.x_in_at(sv, l), a2, x_mid, W.u1, W.cb1, st2, W.b2, d2, M, d, F, s, nullptr, nullptr, nullptr, 0,
-                                 nullptr, bo2));
+        a.ctx = ctx; a.bo = W.bo; a.Wt = W.wmlp_op;
+      }
+      if (l + 1 < L) {   // the next layer's LN1 + q / k / v behind the block, x_next straight into the arena
+        const LayerW& Wn = e->layers[l + 1];
+        a.qkv_u = Wn.uqkv; a.qkv_cb = Wn.cbqkv; a.qkv_out = sv + (size_t)(l + 1) * sl.layer_stride + sl.qkv; a.NQ = 3 * d;
+        a.x_next = sl.x_in_at(sv, l + 1);
+        GWW_TRY(launch_mlp_fused(a, s));
+      } else {
+        a.C = d2;
+        GWW_TRY(launch_mlp_fused(a, s));
         GWW_TRY(launch_add_delta_f32(x_mid, d2, sl.x_in_at(sv, L), M * d, s));
       }
     }

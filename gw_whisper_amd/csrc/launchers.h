@@ -54,22 +54,45 @@ int launch_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx
 // ---- mlp_fused.hip
 int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_folded, void* out, int d, int F, int NQ,
                     hipStream_t s, const void* wo = nullptr);
-int launch_mlp_fused(const float* x, const void* delta, float* x_out, const float* ln_u, const float* ln_cb,
-                     const void* Wt, const float* b2, void* C, long M, int d, int F, hipStream_t s,
-                     const float* q_u = nullptr, const float* q_cb = nullptr, void* q_out = nullptr, int NQ = 0,
-                     float* x_next_out = nullptr, const float* bo = nullptr, bool keep_x_new = true);
-int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const float* ln_u, const float* ln_cb,
-                           const void* Wt, const float* b2, const float* bo, const float* lnf_w, const float* lnf_b, float* y,
-                           long M, int d, int F, hipStream_t s, bool keep_x_new = true);
-int launch_lnqkv_fused(const float* x, const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d,
-                       int NQ, hipStream_t s);
-// layer 0 behind the compact stem: the panel formed from xs / tr / pos where *flag == 1, read from x where it is 0
-int launch_lnqkv_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T, int Tt,
-                          const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d, int NQ,
-                          hipStream_t s);
-int launch_mlp_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T, int Tt,
-                        const void* ctx, const float* bo, const float* ln_u, const float* ln_cb, const void* Wt, const float* b2,
-                        long M, int d, int F, const float* q_u, const float* q_cb, void* q_out, int NQ, hipStream_t s);
+bool mlp_fused_supported(int d, int F);   // the fused block exists for this width / ffn (MF_D, MF_FMAX)
+// The operands of the compact stem (stem_tail.hip) from which layer 0 forms its rows of the residual stream: xs [B, Tt, 384],
+// tr [B, 384], pos [T, 384] where *flag == 1; x is read where it is 0 (decided in the kernel).  M = B T.
+struct MfX0 {
+  const float *xs, *tr, *pos;
+  const int* flag;
+  int T, Tt;
+};
+// One launch of k_mlp_fused.  Unset fields stay null / 0; which are set selects the instantiation <MODE, OP, X0>:
+//   neither delta nor ctx : LayerNorm 1 + q / k / v of x alone (qkv_* set, no block operand)           <2, false>
+//   delta                 : x_new = x + delta, then LN2 + fc1 + GELU + fc2                               <., false>
+//   ctx + bo              : x_new = x + bf16(ctx W_o^T + bo) first; Wt starts with the W_o tiles           <., true>
+//   ... then C            : the block's bf16 delta, to be added to x_new by the next reader                <0, .>
+//   ... or qkv_out        : x_next = x_new + block, LN1 + q / k / v of it behind (the next layer's)        <1, .>
+//   ... or y (ctx only)   : y = LayerNorm_final(x_new + block), the encoder's last block                   <3, true>
+//   x0                    : x is formed in registers from the compact stem; modes <2, false> and <1, true> only
+struct MlpFusedArgs {
+  const char* who = "mlp_fused";   // the calling entry point, for error messages
+  const float* x = nullptr;        // fp32 [M, 384] residual stream entering the launch
+  const void* delta = nullptr;     // bf16 [M, 384] delta pending on x
+  const void* ctx = nullptr;       // bf16 [M, 384] attention context ...
+  const float* bo = nullptr;       // ... and the out_proj bias
+  float* x_new = nullptr;          // fp32 [M, 384], != x: the block's intermediate residual stream ...
+  bool keep_x_new = false;         // ... which a caller that reads it afterwards must ask for
+  const float *ln_u = nullptr, *ln_cb = nullptr;   // LN2 folded into fc1 (gww_ln_fold_weights)
+  const void* Wt = nullptr;        // launch_mlp_pack's stream for this mode
+  const float* b2 = nullptr;
+  void* C = nullptr;               // bf16 [>= roundup(M, 128), 384] (whole 128-row panels are stored)
+  const float *qkv_u = nullptr, *qkv_cb = nullptr;   // LN1 folded into the q / k / v panel
+  void* qkv_out = nullptr;         // bf16 [>= roundup(M, 128), NQ]
+  int NQ = 0;
+  float* x_next = nullptr;         // fp32 [M, 384], != x_new; unset: x_next is written over x
+  const float *lnf_w = nullptr, *lnf_b = nullptr;   // the final LayerNorm
+  float* y = nullptr;              // fp32 [M, 384], != x_new
+  const MfX0* x0 = nullptr;         // (k_mlp_fused takes it by value)
+  long M = 0;
+  int d = 0, F = 0;
+};
+int launch_mlp_fused(const MlpFusedArgs& a, hipStream_t s);
 
 // ---- the bf16 training step: train_ops.hip, dora_grads.hip, wgrad.hip
 int launch_ln_bwd(const float* x, const float* gamma, const void* dy, int dy_f32, float* dx, int accumulate,

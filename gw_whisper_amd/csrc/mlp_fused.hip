@@ -233,14 +233,7 @@ __device__ unsigned long long g_stamp_mlp[24];
 // The loads of a row take a per-lane source (a 128-row panel straddles segments); the shared row's x and r of the at most two
 // segments of a panel are staged in the u table of the LDS (unused otherwise: GWW_MF_NORM).  *flag == 0 (the forward took the
 // full stem): the same loads read X, nothing is staged or fixed up.
-struct MfX0 {
-  const float* xs;
-  const float* tr;
-  const float* pos;
-  const int* flag;
-  int T, Tt;
-};
-
+// (struct MfX0, the operands: launchers.h)
 // source of row g of the residual stream (x0: the device flag); tail: the row is the shared row under pos[j]; seg: its segment
 __device__ __forceinline__ const float* mf_x0_row(const MfX0& z, const float* X, long g, bool x0, bool& tail, int& seg) {
   tail = false; seg = 0;
@@ -1859,7 +1852,7 @@ __global__ __launch_bounds__(256) void k_mlp_pack(const unsigned short* __restri
 int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_folded, void* out, int d, int F, int NQ,
                     hipStream_t s, const void* wo) {
   GWW_REQUIRE(d == MF_D && F % 128 == 0 && F >= 0 && (F > 0 || wqkv_folded),
-              "mlp_pack: d must be 384 and ffn a multiple of 128 (0: only the q / k / v panel, for launch_lnqkv_fused)");
+              "mlp_pack: d must be 384 and ffn a multiple of 128 (0: only the q / k / v panel, for LayerNorm 1 + q / k / v alone)");
   GWW_REQUIRE(!wqkv_folded || (NQ > 0 && NQ % 128 == 0), "mlp_pack: the q / k / v panel needs NQ %% 128 == 0");
   GWW_REQUIRE(!wo || F > 0, "mlp_pack: an out_proj panel goes in front of an MLP stream");
   const long n16 = ((wo ? (long)MF_D * MF_D : 0) + 2L * MF_D * F + (wqkv_folded ? (long)NQ * MF_D : 0)) / 8;
@@ -1870,139 +1863,67 @@ int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_fold
   return GWW_OK;
 }
 
-// x fp32 [M, 384], delta bf16 [M, 384], x_out fp32 [M, 384] (!= x); Wt = launch_mlp_pack of the gain-folded fc1
-// panel and the fc2 panel, ln_u / ln_cb from gww_ln_fold_weights; C bf16 [>= roundup(M, 128), 384] (whole
-// 128-row panels are stored).
-// bo != NULL (OP): `delta` is the attention context ctx (bf16 [M, 384]) and Wt starts with the W_o tiles
-// (launch_mlp_pack(..., wo)): x_out = x + bf16(ctx W_o^T + bo), then the block as above.
-int launch_mlp_fused(const float* x, const void* delta, float* x_out, const float* ln_u, const float* ln_cb,
-                     const void* Wt, const float* b2, void* C, long M, int d, int F, hipStream_t s,
-                     const float* q_u, const float* q_cb, void* q_out, int NQ, float* x_next_out, const float* bo,
-                     bool keep_x_new) {
-  GWW_REQUIRE(x && delta && x_out && ln_u && ln_cb && Wt && b2, "mlp_fused: NULL operand");
-  GWW_REQUIRE(d == MF_D, "mlp_fused: built for d_model = 384 (got %d)", d);
-  GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused: ffn = %d must be a multiple of 128, <= 1536", F);
-  GWW_REQUIRE((const void*)x_out != (const void*)x, "mlp_fused: x_out must not alias x");
-  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "mlp_fused: M = %ld rows exceed the 32-bit row offsets of the seams", M);
-  const bool qkv = q_out != nullptr;
-  GWW_REQUIRE(qkv || C, "mlp_fused: no output");
-  GWW_REQUIRE(!qkv || (q_u && q_cb && NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX),
-              "mlp_fused: the fused q / k / v projection needs u, cb and NQ %% 128 == 0, NQ <= 1536");
-  GWW_REQUIRE(((((uintptr_t)x) | ((uintptr_t)delta) | ((uintptr_t)x_out) | ((uintptr_t)Wt) | ((uintptr_t)C) |
-                ((uintptr_t)q_out)) & 15) == 0, "mlp_fused: operands must be 16-byte aligned");
-  if (M == 0) return GWW_OK;
-  const long panels = cdiv(M, MF_BM);
-  // stagger only when there is more than one round of workgroups to keep de-phased; 100 MHz ticks
-  static const int stagger_env = (int)lab_int("GWW_MLP_STAGGER", 0);   // (lab build; measured: no effect)
-  const int stagger = panels >= 512 ? stagger_env : 0;
-#define GWW_MF_LAUNCH(QQ, OO, ...)                                                                                        \
-  hipLaunchKernelGGL((k_mlp_fused<QQ, OO>), dim3((unsigned)panels), dim3(MF_THREADS), 0, s, x, (const unsigned short*)delta, \
-                     x_out, ln_u, ln_cb, (const unsigned short*)Wt, b2, (unsigned short*)C, M, F, stagger, __VA_ARGS__, bo, keep_x_new ? 1 : 0, MfNoX0{})
-  if (qkv) {
-    // x_next goes to its own buffer (training: the saved activations) or back over x, whose rows each workgroup has
-    // finished reading long before it writes them; never over x_out: the seam's unmasked stores of the clamped rows past M
-    // are only harmless while it does not run in place (k_mlp_fused, seam)
-    float* xnx = x_next_out ? x_next_out : const_cast<float*>(x);
-    GWW_REQUIRE((((uintptr_t)xnx) & 15) == 0 && (const void*)xnx != (const void*)x_out, "mlp_fused: x_next must not alias x_out");
-    if (bo) GWW_MF_LAUNCH(1, true, q_u, q_cb, (unsigned short*)q_out, NQ, xnx);
-    else GWW_MF_LAUNCH(1, false, q_u, q_cb, (unsigned short*)q_out, NQ, xnx);
-  } else {
-    if (bo) GWW_MF_LAUNCH(0, true, nullptr, nullptr, nullptr, 0, nullptr);
-    else GWW_MF_LAUNCH(0, false, nullptr, nullptr, nullptr, 0, nullptr);
+bool mlp_fused_supported(int d, int F) { return d == MF_D && F > 0 && F % 128 == 0 && F <= MF_FMAX; }
+
+// THE launcher of k_mlp_fused (MlpFusedArgs, launchers.h: which fields are set selects <MODE, OP, X0>).  Wt per mode:
+// launch_mlp_pack(w1_folded, w2, next q / k / v panel or NULL, ., wo with ctx); the q / k / v panel alone for <2, false>.
+int launch_mlp_fused(const MlpFusedArgs& a, hipStream_t s) {
+  const char* who = a.who;
+  const void* const A = a.ctx ? a.ctx : a.delta;   // the kernel's `delta` operand
+  const bool op = a.ctx != nullptr, lnq = !A, fin = a.y != nullptr, qkv = a.qkv_out != nullptr, x0 = a.x0 != nullptr;
+  GWW_REQUIRE(!(a.ctx && a.delta) && op == (a.bo != nullptr), "%s: a pending delta, or ctx with the out_proj bias", who);
+  GWW_REQUIRE(!fin || (op && !qkv && !a.C && a.lnf_w && a.lnf_b), "%s: the final LayerNorm takes ctx, bo, lnf_w, lnf_b and no other output", who);
+  GWW_REQUIRE(!lnq || (!a.x_new && !a.ln_u && !a.ln_cb && !a.b2 && !a.C && a.F == 0), "%s: LayerNorm 1 + q / k / v alone takes no block operand", who);
+  GWW_REQUIRE(fin || qkv || (!lnq && a.C), "%s: no output", who);
+  // x0 forms x in registers while xs / tr may live in what is x_new elsewhere: it exists for <2, false> and <1, true>, and never keeps x_new
+  GWW_REQUIRE(!x0 || (!a.x_new && !a.keep_x_new && (lnq || (op && qkv))), "%s: x0 runs LN1 + q / k / v alone or ctx + block + q / k / v, without x_new", who);
+  GWW_REQUIRE(a.Wt && (x0 || a.x) && (lnq || (a.ln_u && a.ln_cb && a.b2 && (x0 || a.x_new))) && (!a.keep_x_new || a.x_new), "%s: NULL operand", who);
+  GWW_REQUIRE(a.d == MF_D && (lnq || mlp_fused_supported(a.d, a.F)),
+              "%s: built for d_model = 384 and ffn a multiple of 128, <= 1536 (got %d, %d)", who, a.d, a.F);
+  GWW_REQUIRE(!qkv || (a.qkv_u && a.qkv_cb && a.NQ > 0 && a.NQ % 128 == 0 && a.NQ <= MF_FMAX),
+              "%s: the q / k / v projection needs u, cb and NQ %% 128 == 0, NQ <= 1536", who);
+  GWW_REQUIRE(x0 || lnq || ((const void*)a.x_new != (const void*)a.x && (const void*)a.y != (const void*)a.x_new),
+              "%s: x_new must alias neither x nor y", who);
+  // (LN1 + q / k / v of a stream in HBM indexes its rows by 64-bit pointers: no limit there)
+  GWW_REQUIRE((lnq && !x0) || a.M * (long)(MF_D * 4) < (1L << 32), "%s: M = %ld rows exceed the 32-bit row offsets of the seams", who, a.M);
+  GWW_REQUIRE((((x0 ? 0 : (uintptr_t)a.x) | ((uintptr_t)A) | ((uintptr_t)a.x_new) | ((uintptr_t)a.Wt) | ((uintptr_t)a.C) |
+                ((uintptr_t)a.qkv_out) | ((uintptr_t)a.y)) & 15) == 0, "%s: operands must be 16-byte aligned", who);
+  if (a.M == 0) return GWW_OK;
+  if (x0) {
+    const MfX0& z = *a.x0;
+    GWW_REQUIRE(z.xs && z.tr && z.pos && z.flag && a.x, "%s: NULL operand", who);
+    // (T >= 128: a 128-row panel then holds rows of at most two segments, which is what the kernel stages)
+    GWW_REQUIRE(z.T >= MF_BM && z.Tt >= 3 && z.Tt < z.T && a.M % z.T == 0, "%s: bad shape M=%ld T=%d Tt=%d", who, a.M, z.T, z.Tt);
+    GWW_REQUIRE(((((uintptr_t)z.xs) | ((uintptr_t)z.tr) | ((uintptr_t)z.pos) | ((uintptr_t)a.x)) & 15) == 0 && (((uintptr_t)z.flag) & 3) == 0,
+                "%s: operands must be 16-byte aligned", who);
   }
-#undef GWW_MF_LAUNCH
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
-}
-
-// The LAST block of the encoder with the final LayerNorm as its epilogue (k_mlp_fused<3, true>): ctx bf16 [M, 384] and x fp32
-// [M, 384] in, y fp32 [M, 384] = LayerNorm_final(x + bf16(ctx W_o^T + bo) + bf16(mlp(...) + b2)) out; x_mid (fp32 [M, 384],
-// != x, != y) receives the block's intermediate residual stream.  Wt = launch_mlp_pack(w1_folded, w2, NULL, ., wo).
-int launch_mlp_fused_final(const float* x, const void* ctx, float* x_mid, const float* ln_u, const float* ln_cb,
-                           const void* Wt, const float* b2, const float* bo, const float* lnf_w, const float* lnf_b, float* y,
-                           long M, int d, int F, hipStream_t s, bool keep_x_new) {
-  GWW_REQUIRE(x && ctx && x_mid && ln_u && ln_cb && Wt && b2 && bo && lnf_w && lnf_b && y, "mlp_fused_final: NULL operand");
-  GWW_REQUIRE(d == MF_D, "mlp_fused_final: built for d_model = 384 (got %d)", d);
-  GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused_final: ffn = %d must be a multiple of 128, <= 1536", F);
-  GWW_REQUIRE((const void*)x_mid != (const void*)x && (const void*)y != (const void*)x_mid, "mlp_fused_final: x_mid must alias neither x nor y");
-  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "mlp_fused_final: M = %ld rows exceed the 32-bit row offsets of the seams", M);
-  GWW_REQUIRE(((((uintptr_t)x) | ((uintptr_t)ctx) | ((uintptr_t)x_mid) | ((uintptr_t)Wt) | ((uintptr_t)y)) & 15) == 0,
-              "mlp_fused_final: operands must be 16-byte aligned");
-  if (M == 0) return GWW_OK;
-  hipLaunchKernelGGL((k_mlp_fused<3, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, x, (const unsigned short*)ctx,
-                     x_mid, ln_u, ln_cb, (const unsigned short*)Wt, b2, reinterpret_cast<unsigned short*>(y), M, F, 0, lnf_w,
-                     lnf_b, (unsigned short*)nullptr, 0, (float*)nullptr, bo, keep_x_new ? 1 : 0, MfNoX0{});
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
-}
-
-// LayerNorm + q / k / v projection of a residual stream WITHOUT a pending delta (layer 0): q_out bf16 [>= roundup(M, 128),
-// NQ] = LN(x) Wqkv'^T + cb with the LayerNorm folded into Wt = launch_mlp_pack(NULL, NULL, wqkv_folded, ., 384, 0, NQ)
-// and q_u / q_cb (gww_ln_fold_weights).  x is only read.
-int launch_lnqkv_fused(const float* x, const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d,
-                       int NQ, hipStream_t s) {
-  GWW_REQUIRE(x && q_u && q_cb && Wt && q_out, "lnqkv_fused: NULL operand");
-  GWW_REQUIRE(d == MF_D, "lnqkv_fused: built for d_model = 384 (got %d)", d);
-  GWW_REQUIRE(NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX, "lnqkv_fused: NQ = %d must be a multiple of 128, <= 1536", NQ);
-  GWW_REQUIRE(((((uintptr_t)x) | ((uintptr_t)Wt) | ((uintptr_t)q_out)) & 15) == 0, "lnqkv_fused: operands must be 16-byte aligned");
-  if (M == 0) return GWW_OK;
-  const long panels = cdiv(M, MF_BM);
-  hipLaunchKernelGGL((k_mlp_fused<2, false>), dim3((unsigned)panels), dim3(MF_THREADS), 0, s, x, (const unsigned short*)nullptr,
-                     (float*)nullptr, (const float*)nullptr, (const float*)nullptr, (const unsigned short*)Wt,
-                     (const float*)nullptr, (unsigned short*)nullptr, M, 0, 0, q_u, q_cb, (unsigned short*)q_out, NQ,
-                     (float*)nullptr, (const float*)nullptr, 0, MfNoX0{});
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
-}
-
-// ---- layer 0 behind the compact stem (stem_tail.hip): both launches form their panel from xs [B, Tt, 384], tr [B, 384] and
-// pos [T, 384] when *flag == 1 and read x [M, 384] when it is 0 (decided in the kernel: no host synchronisation).  M = B T.
-static int x0_check(const char* who, const float* xs, const float* tr, const float* pos, const int* flag, const float* x, long M,
-                    int T, int Tt) {
-  GWW_REQUIRE(xs && tr && pos && flag && x, "%s: NULL operand", who);
-  // (T >= 128: a 128-row panel then holds rows of at most two segments, which is what the kernel stages)
-  GWW_REQUIRE(T >= MF_BM && Tt >= 3 && Tt < T && M % T == 0, "%s: bad shape M=%ld T=%d Tt=%d", who, M, T, Tt);
-  GWW_REQUIRE(((((uintptr_t)xs) | ((uintptr_t)tr) | ((uintptr_t)pos) | ((uintptr_t)x)) & 15) == 0 && (((uintptr_t)flag) & 3) == 0,
-              "%s: operands must be 16-byte aligned", who);
-  return GWW_OK;
-}
-
-// launch_lnqkv_fused on the stream the compact stem describes: x is only read, and only when *flag == 0
-int launch_lnqkv_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T, int Tt,
-                          const float* q_u, const float* q_cb, const void* Wt, void* q_out, long M, int d, int NQ,
-                          hipStream_t s) {
-  GWW_REQUIRE(q_u && q_cb && Wt && q_out, "lnqkv_fused_x0: NULL operand");
-  GWW_REQUIRE(d == MF_D, "lnqkv_fused_x0: built for d_model = 384 (got %d)", d);
-  GWW_REQUIRE(NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX, "lnqkv_fused_x0: NQ = %d must be a multiple of 128, <= 1536", NQ);
-  GWW_REQUIRE(((((uintptr_t)Wt) | ((uintptr_t)q_out)) & 15) == 0, "lnqkv_fused_x0: operands must be 16-byte aligned");
-  if (M == 0) return GWW_OK;
-  GWW_TRY(x0_check("lnqkv_fused_x0", xs, tr, pos, flag, x, M, T, Tt));
-  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "lnqkv_fused_x0: M = %ld rows exceed 32-bit row indices", M);
-  hipLaunchKernelGGL((k_mlp_fused<2, false, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, x,
-                     (const unsigned short*)nullptr, (float*)nullptr, (const float*)nullptr, (const float*)nullptr,
-                     (const unsigned short*)Wt, (const float*)nullptr, (unsigned short*)nullptr, M, 0, 0, q_u, q_cb,
-                     (unsigned short*)q_out, NQ, (float*)nullptr, (const float*)nullptr, 0, MfX0{xs, tr, pos, flag, T, Tt});
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
-}
-
-// launch_mlp_fused with the out_proj in front and the next layer's q / k / v behind (k_mlp_fused<1, true>), the block's x formed
-// in its accumulators; x_next is written to x (flag 1: x is not read at all), x_new is not kept
-int launch_mlp_fused_x0(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T, int Tt,
-                        const void* ctx, const float* bo, const float* ln_u, const float* ln_cb, const void* Wt, const float* b2,
-                        long M, int d, int F, const float* q_u, const float* q_cb, void* q_out, int NQ, hipStream_t s) {
-  GWW_REQUIRE(ctx && bo && ln_u && ln_cb && Wt && b2 && q_u && q_cb && q_out, "mlp_fused_x0: NULL operand");
-  GWW_REQUIRE(d == MF_D, "mlp_fused_x0: built for d_model = 384 (got %d)", d);
-  GWW_REQUIRE(F % 128 == 0 && F > 0 && F <= MF_FMAX, "mlp_fused_x0: ffn = %d must be a multiple of 128, <= 1536", F);
-  GWW_REQUIRE(NQ > 0 && NQ % 128 == 0 && NQ <= MF_FMAX, "mlp_fused_x0: NQ = %d must be a multiple of 128, <= 1536", NQ);
-  GWW_REQUIRE(M * (long)(MF_D * 4) < (1L << 32), "mlp_fused_x0: M = %ld rows exceed the 32-bit row offsets of the seams", M);
-  GWW_REQUIRE(((((uintptr_t)ctx) | ((uintptr_t)Wt) | ((uintptr_t)q_out)) & 15) == 0, "mlp_fused_x0: operands must be 16-byte aligned");
-  if (M == 0) return GWW_OK;
-  GWW_TRY(x0_check("mlp_fused_x0", xs, tr, pos, flag, x, M, T, Tt));
-  hipLaunchKernelGGL((k_mlp_fused<1, true, true>), dim3((unsigned)cdiv(M, MF_BM)), dim3(MF_THREADS), 0, s, (const float*)x,
-                     (const unsigned short*)ctx, (float*)nullptr, ln_u, ln_cb, (const unsigned short*)Wt, b2,
-                     (unsigned short*)nullptr, M, F, 0, q_u, q_cb, (unsigned short*)q_out, NQ, x, bo, 0,
-                     MfX0{xs, tr, pos, flag, T, Tt});
+  // x_next goes to its own buffer (training: the saved activations) or back over x, whose rows each workgroup has finished
+  // reading long before it writes them (x0 with flag 1: never reads them); never over x_new: the seam's unmasked stores of the
+  // clamped rows past M are only harmless while it does not run in place (k_mlp_fused, seam)
+  float* const x_next = !qkv || lnq ? nullptr : a.x_next ? a.x_next : const_cast<float*>(a.x);
+  GWW_REQUIRE(!x_next || ((((uintptr_t)x_next) & 15) == 0 && x_next != a.x_new), "%s: x_next must not alias x_new", who);
+  const long panels = cdiv(a.M, MF_BM);
+  // stagger (lab build; measured: no effect) only when there is more than one round of workgroups to keep de-phased; 100 MHz ticks
+  static const int stagger_env = (int)lab_int("GWW_MLP_STAGGER", 0);
+  const int stagger = !lnq && !fin && !x0 && panels >= 512 ? stagger_env : 0;
+  // the kernel's parameters that change meaning with the mode: C is y as fp32, q_u / q_cb are the final LayerNorm's gain and bias
+  auto launch = [&](auto kernel, auto z) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)panels), dim3(MF_THREADS), 0, s, a.x, (const unsigned short*)A, a.x_new, a.ln_u, a.ln_cb,
+                       (const unsigned short*)a.Wt, a.b2, fin ? reinterpret_cast<unsigned short*>(a.y) : (unsigned short*)a.C, a.M, a.F,
+                       stagger, fin ? a.lnf_w : qkv ? a.qkv_u : nullptr, fin ? a.lnf_b : qkv ? a.qkv_cb : nullptr,
+                       (unsigned short*)a.qkv_out, qkv ? a.NQ : 0, x_next, a.bo, a.keep_x_new ? 1 : 0, z);
+  };
+  switch ((lnq ? 2 : fin ? 3 : qkv ? 1 : 0) | (op ? 4 : 0) | (x0 ? 8 : 0)) {   // every instantiation there is (in the order the code object has always held them)
+    case 5: launch(k_mlp_fused<1, true>, MfNoX0{}); break;
+    case 1: launch(k_mlp_fused<1, false>, MfNoX0{}); break;
+    case 4: launch(k_mlp_fused<0, true>, MfNoX0{}); break;
+    case 0: launch(k_mlp_fused<0, false>, MfNoX0{}); break;
+    case 7: launch(k_mlp_fused<3, true>, MfNoX0{}); break;
+    case 2: launch(k_mlp_fused<2, false>, MfNoX0{}); break;
+    case 10: launch(k_mlp_fused<2, false, true>, *a.x0); break;
+    case 13: launch(k_mlp_fused<1, true, true>, *a.x0); break;
+    default: return fail(GWW_ERR_ARG, "%s: no such instantiation of k_mlp_fused", who);
+  }
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
@@ -2034,44 +1955,75 @@ extern "C" int gww_mlp_pack_op_bf16(const void* wo, const void* w1_folded, const
   return launch_mlp_pack(w1_folded, w2, wqkv_folded_or_null, out, d, F, NQ, (hipStream_t)stream, wo);
 }
 
+// ---- the C ABI of k_mlp_fused: each entry point fills the launcher's descriptor with what it is given
+static MlpFusedArgs mf_block_args(const char* who, const float* x, float* x_new, const float* ln_u, const float* ln_cb, const void* Wt,
+                                  const float* b2, long M, int d, int F) {
+  MlpFusedArgs a;
+  a.who = who; a.x = x; a.x_new = x_new; a.keep_x_new = x_new != nullptr; a.ln_u = ln_u; a.ln_cb = ln_cb; a.Wt = Wt; a.b2 = b2;
+  a.M = M; a.d = d; a.F = F;
+  return a;
+}
+static void mf_qkv_args(MlpFusedArgs& a, const float* qkv_u, const float* qkv_cb, void* qkv_out, int NQ) {
+  a.qkv_u = qkv_u; a.qkv_cb = qkv_cb; a.qkv_out = qkv_out; a.NQ = NQ;
+}
+
 extern "C" int gww_attn_out_mlp_fused_bf16(float* x, const void* ctx, const float* bo, float* x_out, const float* ln_u,
                                            const float* ln_cb, const void* Wt, const float* b2, void* C, long M, int d,
                                            int F, const float* qkv_u, const float* qkv_cb, void* qkv_out, int NQ,
                                            void* stream) {
-  GWW_REQUIRE(bo, "gww_attn_out_mlp_fused_bf16: NULL out_proj bias");
-  return launch_mlp_fused(x, ctx, x_out, ln_u, ln_cb, Wt, b2, C, M, d, F, (hipStream_t)stream, qkv_u, qkv_cb, qkv_out, NQ,
-                          nullptr, bo);
+  GWW_REQUIRE(ctx && bo, "gww_attn_out_mlp_fused_bf16: NULL ctx or out_proj bias");
+  MlpFusedArgs a = mf_block_args("gww_attn_out_mlp_fused_bf16", x, x_out, ln_u, ln_cb, Wt, b2, M, d, F);
+  a.ctx = ctx; a.bo = bo; a.C = C;
+  mf_qkv_args(a, qkv_u, qkv_cb, qkv_out, NQ);
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }
 
 extern "C" int gww_attn_out_mlp_final_bf16(const float* x, const void* ctx, const float* bo, float* x_mid, const float* ln_u,
                                           const float* ln_cb, const void* Wt, const float* b2, const float* lnf_w,
                                           const float* lnf_b, float* y, long M, int d, int F, void* stream) {
-  return launch_mlp_fused_final(x, ctx, x_mid, ln_u, ln_cb, Wt, b2, bo, lnf_w, lnf_b, y, M, d, F, (hipStream_t)stream);
+  MlpFusedArgs a = mf_block_args("gww_attn_out_mlp_final_bf16", x, x_mid, ln_u, ln_cb, Wt, b2, M, d, F);
+  a.ctx = ctx; a.bo = bo; a.lnf_w = lnf_w; a.lnf_b = lnf_b; a.y = y;
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }
 
 extern "C" int gww_lnqkv_fused_bf16(const float* x, const float* qkv_u, const float* qkv_cb, const void* Wt, void* qkv_out,
                                     long M, int d, int NQ, void* stream) {
-  return launch_lnqkv_fused(x, qkv_u, qkv_cb, Wt, qkv_out, M, d, NQ, (hipStream_t)stream);
+  MlpFusedArgs a;
+  a.who = "gww_lnqkv_fused_bf16"; a.x = x; a.Wt = Wt; a.M = M; a.d = d;
+  mf_qkv_args(a, qkv_u, qkv_cb, qkv_out, NQ);
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }
 
 extern "C" int gww_mlp_fused_bf16(float* x, const void* delta, float* x_out, const float* ln_u,
                                   const float* ln_cb, const void* Wt, const float* b2, void* C, long M, int d,
                                   int F, const float* qkv_u, const float* qkv_cb, void* qkv_out, int NQ,
                                   void* stream) {
-  return launch_mlp_fused(x, delta, x_out, ln_u, ln_cb, Wt, b2, C, M, d, F, (hipStream_t)stream, qkv_u, qkv_cb, qkv_out,
-                          NQ, nullptr, nullptr);
+  GWW_REQUIRE(delta, "gww_mlp_fused_bf16: NULL operand");
+  MlpFusedArgs a = mf_block_args("gww_mlp_fused_bf16", x, x_out, ln_u, ln_cb, Wt, b2, M, d, F);
+  a.delta = delta; a.C = C;
+  mf_qkv_args(a, qkv_u, qkv_cb, qkv_out, NQ);
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }
 
 extern "C" int gww_lnqkv_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, const float* x, int T,
                                        int Tt, const float* qkv_u, const float* qkv_cb, const void* Wt, void* qkv_out, long M,
                                        int d, int NQ, void* stream) {
-  return launch_lnqkv_fused_x0(xs, tr, pos, flag, x, T, Tt, qkv_u, qkv_cb, Wt, qkv_out, M, d, NQ, (hipStream_t)stream);
+  const MfX0 z{xs, tr, pos, flag, T, Tt};
+  MlpFusedArgs a;
+  a.who = "gww_lnqkv_fused_x0_bf16"; a.x = x; a.x0 = &z; a.Wt = Wt; a.M = M; a.d = d;
+  mf_qkv_args(a, qkv_u, qkv_cb, qkv_out, NQ);
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }
 
+// (x_next is written to x -- flag 1: x is not read at all --, x_new is not kept)
 extern "C" int gww_attn_out_mlp_fused_x0_bf16(const float* xs, const float* tr, const float* pos, const int* flag, float* x, int T,
                                               int Tt, const void* ctx, const float* bo, const float* ln_u, const float* ln_cb,
                                               const void* Wt, const float* b2, long M, int d, int F, const float* qkv_u,
                                               const float* qkv_cb, void* qkv_out, int NQ, void* stream) {
-  return launch_mlp_fused_x0(xs, tr, pos, flag, x, T, Tt, ctx, bo, ln_u, ln_cb, Wt, b2, M, d, F, qkv_u, qkv_cb, qkv_out, NQ,
-                             (hipStream_t)stream);
+  GWW_REQUIRE(ctx, "gww_attn_out_mlp_fused_x0_bf16: NULL operand");
+  const MfX0 z{xs, tr, pos, flag, T, Tt};
+  MlpFusedArgs a = mf_block_args("gww_attn_out_mlp_fused_x0_bf16", x, nullptr, ln_u, ln_cb, Wt, b2, M, d, F);
+  a.ctx = ctx; a.bo = bo; a.x0 = &z;
+  mf_qkv_args(a, qkv_u, qkv_cb, qkv_out, NQ);
+  return launch_mlp_fused(a, (hipStream_t)stream);
 }

@@ -60,22 +60,33 @@ def mels(torch, batch, n_mels=80):
     return padded, dense
 
 
-def inference(torch, rec):
-    tiny = (384, 4, 6, 1536)
-    enc = encoder(tiny)[0].cuda()
+def inference(torch, rec, trace=False):
+    """trace: also record the encoder's own span count per kernel class (trace_read) of every forward, under <key>/trace."""
+    def enc_for(dims, **kw):
+        enc = encoder(dims, **kw)[0].cuda()
+        enc.trace_enable(trace)
+        return enc
+
+    def run(enc, key, fn):
+        out = fn()
+        if trace:
+            rec.put(key + "/trace", np.asarray([n for _, n in enc.trace_read().values()], dtype=np.int64))
+        return out
+
+    enc = enc_for((384, 4, 6, 1536))
     padded, dense = mels(torch, 2)
     with torch.no_grad():
         for tag, mel in (("padded", padded), ("dense", dense)):
             for want_h, want_l in ((True, False), (False, True), (True, True)):
-                h, l = enc.forward_raw(mel, want_hidden=want_h, want_last=want_l)
-                torch.cuda.synchronize()
                 key = f"inf/tiny/{tag}/{'h' if want_h else ''}{'l' if want_l else ''}"
+                h, l = run(enc, key, lambda: enc.forward_raw(mel, want_hidden=want_h, want_last=want_l))
+                torch.cuda.synchronize()
                 rec.put(key + "/shortcut", np.asarray(enc.stem_shortcut_flags(2)))
                 if want_h:
                     rec.put(key + "/hidden", h)
                 if want_l:
                     rec.put(key + "/last", l)
-        o = enc(padded[:1], output_hidden_states=True, output_attentions=True)
+        o = run(enc, "inf/tiny/outputs", lambda: enc(padded[:1], output_hidden_states=True, output_attentions=True))
         rec.put("inf/tiny/outputs/last", o.last_hidden_state)
         for i, t in enumerate(o.hidden_states):
             rec.put(f"inf/tiny/outputs/hidden{i}", t)
@@ -85,26 +96,30 @@ def inference(torch, rec):
         # the dual-stream split: 64 segments, half of them dense
         big = torch.cat([mels(torch, 32)[0], dense.repeat(16, 1, 1)])
         enc.set_split(True)
-        h, l = enc.forward_raw(big, want_hidden=True, want_last=True)
+        h, l = run(enc, "inf/tiny/split64", lambda: enc.forward_raw(big, want_hidden=True, want_last=True))
         rec.put("inf/tiny/split64/hidden", h)
         rec.put("inf/tiny/split64/last", l)
-        rec.put("inf/tiny/split64/last_only", enc.forward_raw(big, want_hidden=False, want_last=True)[1])
+        rec.put("inf/tiny/split64/last_only", run(enc, "inf/tiny/split64/last_only",
+                                                  lambda: enc.forward_raw(big, want_hidden=False, want_last=True))[1])
         enc.set_split(False)
         del enc, big, h, l
         for dims in ((512, 2, 8, 2048), (768, 2, 12, 3072)):
-            enc = encoder(dims)[0].cuda()
-            rec.put(f"inf/d{dims[0]}/last_only", enc.forward_raw(padded, want_hidden=False, want_last=True)[1])
-            rec.put(f"inf/d{dims[0]}/hidden", enc.forward_raw(dense, want_hidden=True, want_last=True)[0])
-        enc = encoder((384, 2, 6, 1536), n_mels=128)[0].cuda()
+            enc = enc_for(dims)
+            key = f"inf/d{dims[0]}"
+            rec.put(key + "/last_only", run(enc, key + "/last_only", lambda: enc.forward_raw(padded, want_hidden=False, want_last=True))[1])
+            rec.put(key + "/hidden", run(enc, key + "/hidden", lambda: enc.forward_raw(dense, want_hidden=True, want_last=True))[0])
+        enc = enc_for((384, 2, 6, 1536), n_mels=128)
         m128 = mels(torch, 2, 128)[1]
-        rec.put("inf/mels128/hidden", enc.forward_raw(m128, want_hidden=True, want_last=False)[0])
-        rec.put("inf/mels128/last_only", enc.forward_raw(m128, want_hidden=False, want_last=True)[1])
-        enc = encoder((384, 2, 6, 1536), precision="fp32")[0].cuda()
+        rec.put("inf/mels128/hidden", run(enc, "inf/mels128/hidden", lambda: enc.forward_raw(m128, want_hidden=True, want_last=False))[0])
+        rec.put("inf/mels128/last_only", run(enc, "inf/mels128/last_only",
+                                             lambda: enc.forward_raw(m128, want_hidden=False, want_last=True))[1])
+        enc = enc_for((384, 2, 6, 1536), precision="fp32")
         for tag, mel in (("padded", padded), ("dense", dense)):
-            h, l = enc.forward_raw(mel, want_hidden=True, want_last=True)
-            rec.put(f"inf/fp32/{tag}/hidden", h)
-            rec.put(f"inf/fp32/{tag}/last", l)
-            rec.put(f"inf/fp32/{tag}/last_only", enc.forward_raw(mel, want_hidden=False, want_last=True)[1])
+            key = f"inf/fp32/{tag}"
+            h, l = run(enc, key, lambda: enc.forward_raw(mel, want_hidden=True, want_last=True))
+            rec.put(key + "/hidden", h)
+            rec.put(key + "/last", l)
+            rec.put(key + "/last_only", run(enc, key + "/last_only", lambda: enc.forward_raw(mel, want_hidden=False, want_last=True))[1])
 
 
 def train_model(torch, dims, precision, projs, r, dora):
@@ -219,15 +234,20 @@ def main():
     ap.add_argument("--out", default="encoder_paths.npz")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two results instead of running")
     ap.add_argument("--only", choices=["inference", "training", "sizes"], default=None)
+    ap.add_argument("--inference-trace", action="store_true",
+                    help="only the inference section, with the encoder's span count per kernel class of every forward "
+                         "(for the laboratory library under each GWW_GENERIC_PATH mask, one process per mask)")
     args = ap.parse_args()
     if args.compare:
         sys.exit(compare(*args.compare))
     import torch
     rec = Recorder()
+    if args.inference_trace:
+        args.only = "inference"
     if args.only in (None, "sizes"):
         sizes(rec)
     if args.only in (None, "inference"):
-        inference(torch, rec)
+        inference(torch, rec, trace=args.inference_trace)
     if args.only in (None, "training"):
         training(torch, rec)
     torch.cuda.synchronize()
