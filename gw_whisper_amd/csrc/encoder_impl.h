@@ -1,6 +1,6 @@
 // What the three host drivers of the encoder share: the handle and its packed weights (encoder.hip: create / pack /
-// inference forward, encoder_train.hip: the bf16 training step, encoder_train_f32.hip: the exact-fp32 one).
-// Internal: not installed, nothing of it is part of the C ABI.
+// inference forward, encoder_train.hip: the bf16 training step, encoder_train_f32.hip: the exact-fp32 one), the checks and the
+// table of the adapter targets of both training backwards.  Internal: not installed, nothing of it is part of the C ABI.
 #pragma once
 
 #include "common.h"
@@ -69,6 +69,35 @@ inline int generic_path_mask() {
   static const int mask = (int)lab_int("GWW_GENERIC_PATH", 0);
   return mask;
 }
+
+// The adapter targets of a training backward (gww_dora_target), checked and indexed once for both drivers.  check_targets
+// reads nothing of the handle: the targets' own fields (rank, the seven pointers), then that no (layer, proj) comes twice.
+inline int check_targets(const char* who, const gww_dora_target* t, int n) {
+  for (int i = 0; i < n; ++i) {
+    GWW_REQUIRE(t[i].r >= 1 && t[i].r <= 64, "%s: target %d has rank %d: adapter gradients support ranks 1..64", who, i, t[i].r);
+    GWW_REQUIRE(t[i].A && t[i].B && t[i].mag && t[i].nrm && t[i].dA && t[i].dB && t[i].dm, "%s: NULL pointer in target %d", who, i);
+  }
+  for (int i = 1; i < n; ++i)
+    for (int j = 0; j < i; ++j)
+      GWW_REQUIRE(t[i].layer != t[j].layer || t[i].proj != t[j].proj, "%s: duplicate target: %d and %d both name layer %d proj %d",
+                  who, j, i, t[i].layer, t[i].proj);
+  return GWW_OK;
+}
+// ... and, once the handle has given L, their layer / proj range
+inline int check_target_range(const char* who, const gww_dora_target* t, int n, int L) {
+  for (int i = 0; i < n; ++i)
+    GWW_REQUIRE(t[i].layer >= 0 && t[i].layer < L && t[i].proj >= 0 && t[i].proj <= 5, "%s: bad target %d", who, i);
+  return GWW_OK;
+}
+// at(layer, proj): the target of that projection or nullptr, of targets that passed both checks
+struct TargetTable {
+  std::vector<const gww_dora_target*> slot;   // [L][6]; empty without targets
+  TargetTable() = default;
+  TargetTable(const gww_dora_target* t, int n, int L) : slot(n > 0 ? (size_t)L * 6 : 0, nullptr) {
+    for (int i = 0; i < n; ++i) slot[(size_t)t[i].layer * 6 + t[i].proj] = &t[i];
+  }
+  const gww_dora_target* at(int layer, int proj) const { return slot.empty() ? nullptr : slot[(size_t)layer * 6 + proj]; }
+};
 
 }  // namespace gww
 

@@ -1,8 +1,8 @@
 // DoRA / LoRA training step in exact fp32 (precision="fp32", the parity twin of the bf16 step of encoder_train.hip): every saved
 // activation is fp32 and every contraction runs on the fp32 MFMA (gemm_f32.hip, train_f32.hip, attention_bwd_f32.hip).
 // It mirrors the per-op branch of the bf16 step at every width (the fused d = 384 kernels are bf16-only), including the
-// pooled last layer and the stem backward.  The dX GEMMs read the stored fp32 [out][in] panels un-transposed
-// (k_gemm_f32_dx): no second set of fp32 panels for the optimizer step's re-pack to maintain.
+// pooled last layer and the stem backward, and shares the target checks and the TargetTable of encoder_impl.h with it.  The dX
+// GEMMs read the stored fp32 [out][in] panels un-transposed (k_gemm_f32_dx): no second set for the optimizer step's re-pack.
 //
 // saved arena, per layer l:  x_in[l] [Mp,d] | qkv [Mp,3d] | lse [B,H,T] | ctx [Mp,d] | x_mid [Mp,d]   (+ x_in[L])
 // LN1(x_in), LN2(x_mid) and the fc1 pre-activation z are recomputed in the backward (one LayerNorm + one fc1 GEMM per
@@ -59,6 +59,24 @@ TrainWs32 train_ws32(const gww_enc_cfg& c, int B) {
   w.ascr = a.take(w.ascr_bytes);
   w.total = a.total();
   return w;
+}
+
+// ---- conv stem backward: x0 = gelu(conv2(gelu(conv1(mel)))) + pos, dx = d(x0) in; melT and c1 of the forward are still in
+// the workspace, the pre-activations are recomputed by the same GEMMs with a plain bias epilogue
+int stem_backward(const gww_encoder* e, char* base, const TrainWs32& w, const float* dx, float* d_mel, int B, hipStream_t s) {
+  const int d = e->cfg.d_model, Tin = e->cfg.t_in, T = Tin / 2, C = e->cfg.n_mels, Kc1 = conv1_kpad(C);
+  const float* melT = (const float*)(base + w.melT);
+  const float* c1 = (const float*)(base + w.c1);
+  float* zb = (float*)(base + w.zb);
+  float* fb = (float*)(base + w.fb);
+  const long M2 = (long)B * (T + 1), M1 = (long)B * (Tin + 2);
+  GWW_TRY(launch_gemm_f32(c1, 2L * d, e->c2w32, e->c2b, nullptr, nullptr, zb, M2, d, 3 * d, EPI_BIAS, 0, s));   // z2
+  GWW_TRY(launch_stem_dz2_f32(dx, zb, fb, B, T, d, s));                                                       // dz2
+  GWW_TRY(launch_gemm_f32_dx(fb, d, e->c2w32, zb, 3L * d, M2, 3 * d, d, s));                                  // col
+  GWW_TRY(launch_gemm_f32(melT, C, e->c1w32, e->c1b, nullptr, nullptr, fb, M1, d, Kc1, EPI_BIAS, 0, s));      // z1
+  GWW_TRY(launch_stem_dz1_f32(zb, fb, fb, B, T, Tin, d, s));                                                 // dz1
+  GWW_TRY(launch_gemm_f32_dx(fb, d, e->c1w32, zb, Kc1, M1, Kc1, d, s));                                       // col1
+  return launch_stem_dmel_f32(zb, d_mel, B, Tin, C, Kc1, s);
 }
 }  // namespace
 
@@ -143,25 +161,16 @@ extern "C" int gww_encoder_train_backward_f32(gww_encoder* e, int batch, void* w
                                               const void* saved, size_t saved_bytes, const float* d_last_hidden,
                                               const gww_dora_target* targets, int n_targets, float* d_x0, float* d_mel,
                                               int pooled, void* stream) {
-  GWW_REQUIRE(e && workspace && saved && d_last_hidden, "gww_encoder_train_backward_f32: NULL argument");
-  GWW_REQUIRE(batch > 0 && n_targets >= 0 && (n_targets == 0 || targets), "gww_encoder_train_backward_f32: bad argument");
-  // the targets' own fields first (nothing of the handle is read for them), then what needs the handle
-  for (int i = 0; i < n_targets; ++i) {
-    const gww_dora_target& t = targets[i];
-    GWW_REQUIRE(t.r >= 1 && t.r <= 64, "gww_encoder_train_backward_f32: target %d has rank %d: adapter gradients support "
-                "ranks 1..64", i, t.r);
-    GWW_REQUIRE(t.A && t.B && t.mag && t.nrm && t.dA && t.dB && t.dm,
-                "gww_encoder_train_backward_f32: NULL pointer in target %d", i);
-  }
+  const char* who = "gww_encoder_train_backward_f32";
+  GWW_REQUIRE(e && workspace && saved && d_last_hidden, "%s: NULL argument", who);
+  GWW_REQUIRE(batch > 0 && n_targets >= 0 && (n_targets == 0 || targets), "%s: bad argument", who);
+  GWW_TRY(check_targets(who, targets, n_targets));   // the targets' own fields first (nothing of the handle is read for them)
   GWW_REQUIRE((((uintptr_t)workspace) & 255) == 0 && (((uintptr_t)saved) & 255) == 0 && (((uintptr_t)d_last_hidden) & 15) == 0,
-              "gww_encoder_train_backward_f32: workspace and saved must be 256-byte, d_last_hidden 16-byte aligned");
-  if (!e->ready) return fail(GWW_ERR_STATE, "gww_encoder_train_backward_f32: weights not set");
+              "%s: workspace and saved must be 256-byte, d_last_hidden 16-byte aligned", who);
+  if (!e->ready) return fail(GWW_ERR_STATE, "%s: weights not set", who);
   const int L = e->cfg.n_layers;
-  for (int i = 0; i < n_targets; ++i) {
-    const gww_dora_target& t = targets[i];
-    GWW_REQUIRE(t.layer >= 0 && t.layer < L && t.proj >= 0 && t.proj <= 5, "gww_encoder_train_backward_f32: bad target %d",
-                i);
-  }
+  GWW_TRY(check_target_range(who, targets, n_targets, L));
+  const TargetTable tt(targets, n_targets, L);
   const SavedLayout32 sl = saved_layout32(e->cfg, batch);
   const TrainWs32 w = train_ws32(e->cfg, batch);
   if (workspace_bytes < w.total || saved_bytes < sl.total)
@@ -186,11 +195,6 @@ extern "C" int gww_encoder_train_backward_f32(gww_encoder* e, int batch, void* w
     return launch_adapter_grads_f32(X, ldx, dY, Y, ldy, bias, ysc, t.scaling, t.A, t.B, t.mag, t.nrm, t.dA, t.dB, t.dm,
                                     rows, d_in, d_out, t.r, s, ascr, w.ascr_bytes);
   };
-  auto find_target = [&](int l, int proj) -> const gww_dora_target* {
-    for (int i = 0; i < n_targets; ++i)
-      if (targets[i].layer == l && targets[i].proj == proj) return &targets[i];
-    return nullptr;
-  };
   const float q_ysc = 0.125f;   // the stored q is (W' x + b) / 8: the fp32 panels keep natural units
   // final LayerNorm backward -> dx (grad w.r.t. x_in[L]); pooled: on the B last-token rows only
   GWW_TRY(launch_ln_bwd(sl.x_in_at(sv, L), e->lnw, d_last_hidden, 1, dx, 0, nullptr, pooled ? B : M, d, s));
@@ -206,21 +210,21 @@ extern "C" int gww_encoder_train_backward_f32(gww_encoder* e, int batch, void* w
     // fc2 / GELU / fc1 / LN2   (x_out = x_mid + fc2(gelu(fc1(LN2(x_mid))))); dx = d(x_out)
     GWW_TRY(launch_layernorm(x_mid, W.ln2w, W.ln2b, h, 0, rows, d, s));
     GWW_TRY(launch_gemm_f32(h, d, W.w132, W.b1, nullptr, nullptr, zb, rows, F, d, EPI_BIAS, 0, s));   // z
-    if (const gww_dora_target* t = find_target(l, 5)) {   // fc2: x = gelu(z), dy = d(x_out), y = x_out - x_mid
+    if (const gww_dora_target* t = tt.at(l, 5)) {   // fc2: x = gelu(z), dy = d(x_out), y = x_out - x_mid
       GWW_TRY(launch_gelu_f32(zb, nullptr, fb, rows * F, s));
       GWW_TRY(launch_sub_f32(sl.x_in_at(sv, l + 1), x_mid, dh, rows * d, s));
       GWW_TRY(agrad(*t, fb, F, dx, dh, d, W.b2, 1.0f, rows, F, d));
     }
     GWW_TRY(launch_gemm_f32_dx(dx, d, W.w232, fb, F, rows, F, d, s));
     GWW_TRY(launch_gelu_f32(zb, fb, fb, rows * F, s));   // d(pre-activation)
-    if (const gww_dora_target* t = find_target(l, 4))   // fc1: x = LN2(x_mid), dy = d(pre-activation), y = z
+    if (const gww_dora_target* t = tt.at(l, 4))   // fc1: x = LN2(x_mid), dy = d(pre-activation), y = z
       GWW_TRY(agrad(*t, h, d, fb, zb, F, W.b1, 1.0f, rows, d, F));
     GWW_TRY(launch_gemm_f32_dx(fb, F, W.w132, dh, d, rows, d, F, s));
     GWW_TRY(launch_ln_bwd(x_mid, W.ln2w, dh, 1, dx, 1, nullptr, rows, d, s));
     // out_proj: x = ctx, dy = d(x_mid) (= dx), y = x_mid - x_in
     const float* ctx_x = last_pooled ? ctx + (size_t)(T - 1) * d : ctx;
     const long ldc = last_pooled ? (long)T * d : d;
-    if (const gww_dora_target* t = find_target(l, 3)) {
+    if (const gww_dora_target* t = tt.at(l, 3)) {
       if (last_pooled) {
         GWW_HIP(hipMemcpy2DAsync(dctx, (size_t)d * 4, sl.x_in_at(sv, l) + (size_t)(T - 1) * d, (size_t)T * d * 4, (size_t)d * 4, B,
                                  hipMemcpyDeviceToDevice, s));
@@ -246,15 +250,15 @@ extern "C" int gww_encoder_train_backward_f32(gww_encoder* e, int batch, void* w
     GWW_TRY(launch_attention_bwd_f32(qkv, ctx, dctx, lse, Dv, dqkv, B, T, H, s));
     // q / k / v adapters: x = LN1(x_in) (recomputed), dy / y = the q | k | v sections of dqkv / qkv
     bool have_h1 = false;
-    for (int i = 0; i < n_targets; ++i) {
-      const gww_dora_target& t = targets[i];
-      if (t.layer != l || t.proj > 2) continue;
+    for (int pr = 0; pr < 3; ++pr) {
+      const gww_dora_target* t = tt.at(l, pr);
+      if (!t) continue;
       if (!have_h1) {
         GWW_TRY(launch_layernorm(sl.x_in_at(sv, l), W.ln1w, W.ln1b, h, 0, M, d, s));
         have_h1 = true;
       }
-      const long off = (long)t.proj * d;
-      GWW_TRY(agrad(t, h, d, dqkv + off, qkv + off, 3L * d, W.bqkv + off, t.proj == 0 ? q_ysc : 1.0f, M, d, d));
+      const long off = (long)pr * d;
+      GWW_TRY(agrad(*t, h, d, dqkv + off, qkv + off, 3L * d, W.bqkv + off, pr == 0 ? q_ysc : 1.0f, M, d, d));
     }
     // below layer 0 the gradient only continues into LN1 of layer 0 and the conv stem
     if (l == 0 && !d_x0 && !d_mel) break;
@@ -262,20 +266,5 @@ extern "C" int gww_encoder_train_backward_f32(gww_encoder* e, int batch, void* w
     GWW_TRY(launch_ln_bwd(sl.x_in_at(sv, l), W.ln1w, dh, 1, dx, 1, nullptr, M, d, s));
   }
   if (d_x0) GWW_HIP(hipMemcpyAsync(d_x0, dx, (size_t)M * d * 4, hipMemcpyDeviceToDevice, s));
-  if (d_mel) {
-    // ---- conv stem backward: x0 = gelu(conv2(gelu(conv1(mel)))) + pos; melT and c1 of the forward are still in the
-    // workspace, the pre-activations are recomputed by the same GEMMs with a plain bias epilogue
-    const int Tin = e->cfg.t_in, C = e->cfg.n_mels, Kc1 = conv1_kpad(C);
-    const float* melT = (const float*)(base + w.melT);
-    const float* c1 = (const float*)(base + w.c1);
-    const long M2 = (long)B * (T + 1), M1 = (long)B * (Tin + 2);
-    GWW_TRY(launch_gemm_f32(c1, 2L * d, e->c2w32, e->c2b, nullptr, nullptr, zb, M2, d, 3 * d, EPI_BIAS, 0, s));   // z2
-    GWW_TRY(launch_stem_dz2_f32(dx, zb, fb, B, T, d, s));                                                       // dz2
-    GWW_TRY(launch_gemm_f32_dx(fb, d, e->c2w32, zb, 3L * d, M2, 3 * d, d, s));                                  // col
-    GWW_TRY(launch_gemm_f32(melT, C, e->c1w32, e->c1b, nullptr, nullptr, fb, M1, d, Kc1, EPI_BIAS, 0, s));      // z1
-    GWW_TRY(launch_stem_dz1_f32(zb, fb, fb, B, T, Tin, d, s));                                                 // dz1
-    GWW_TRY(launch_gemm_f32_dx(fb, d, e->c1w32, zb, Kc1, M1, Kc1, d, s));                                       // col1
-    GWW_TRY(launch_stem_dmel_f32(zb, d_mel, B, Tin, C, Kc1, s));
-  }
-  return GWW_OK;
+  return d_mel ? stem_backward(e, base, w, dx, d_mel, B, s) : GWW_OK;
 }

@@ -229,6 +229,11 @@ typedef struct {
   float* dB;
   float* dm;
 } gww_dora_target;
+/* The three backward entry points below check a target array the same way and in the same order: first the targets' own
+ * fields (rank 1..64, none of the seven pointers NULL) and that no (layer, proj) is named twice -- nothing of the
+ * handle is read for these --, then the layer / proj range against the handle, then the workspace and arena sizes.
+ * Two targets with the same (layer, proj) are refused with GWW_ERR_ARG (the message names both indices); with several
+ * faults in one call the first in that order is the one reported. */
 
 size_t gww_train_saved_bytes(const gww_encoder* enc, int batch);
 size_t gww_train_workspace_bytes(const gww_encoder* enc, int batch);

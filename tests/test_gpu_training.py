@@ -576,6 +576,65 @@ def test_input_gradient_through_the_conv_stem(T, gww):
         assert abs(an - fd) < 0.06 * abs(fd) + 2e-3, (an, fd)
 
 
+def _c_step(T, enc, mel, pooled, d_hidden, want_x0, want_mel):
+    """gww_encoder_train_forward + _backward (their _f32 twins for an fp32 encoder) straight through ctypes, no targets:
+    (d_x0 | None, d_mel | None).  The outputs start as NaN, so an element the backward leaves unwritten shows."""
+    from gw_whisper_amd import _lib
+    lib = _lib.lib()
+    sfx = "_f32" if enc.precision == "fp32" else ""
+    B, d, Tn = mel.shape[0], enc.config.d_model, enc.config.max_source_positions
+    with T.cuda.device(mel.device):
+        enc._sync_weights()
+        h = enc._ensure_handle()
+        ws = T.empty((getattr(lib, "gww_train_workspace_bytes" + sfx)(h, B),), dtype=T.uint8, device=mel.device)
+        saved = T.empty((getattr(lib, "gww_train_saved_bytes" + sfx)(h, B),), dtype=T.uint8, device=mel.device)
+        hidden = T.empty((B, d) if pooled else (B, Tn, d), dtype=T.float32, device=mel.device)
+        stream = T.cuda.current_stream().cuda_stream
+        _lib.check(getattr(lib, "gww_encoder_train_forward" + sfx)(
+            h, mel.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(), int(pooled),
+            stream), "train_forward" + sfx)
+        d_x0 = T.full((B, Tn, d), float("nan"), dtype=T.float32, device=mel.device) if want_x0 else None
+        d_mel = T.full(mel.shape, float("nan"), dtype=T.float32, device=mel.device) if want_mel else None
+        _lib.check(getattr(lib, "gww_encoder_train_backward" + sfx)(
+            h, B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), d_hidden.data_ptr(), None, 0,
+            d_x0.data_ptr() if want_x0 else None, d_mel.data_ptr() if want_mel else None, int(pooled), stream),
+            "train_backward" + sfx)
+        T.cuda.synchronize()
+    return d_x0, d_mel
+
+
+@pytest.mark.parametrize("pooled", [False, True], ids=["dense", "pooled"])
+def test_d_x0_of_the_c_entries(T, gww, pooled):
+    """d_x0, the gradient w.r.t. the residual stream entering layer 0, is in the ABI of all three backward entry points
+    and no Python caller asks for it: asked for alone (no targets, no d_mel) the walk must still continue below layer 0's
+    q / k / v.  Per precision: (a) d_x0 alone is finite and not all zero; (b) with d_mel also requested d_x0 is
+    bit-identical to (a) and d_mel bit-identical to a d_mel-only call (no kernel on this path accumulates with atomics:
+    csrc/attention_bwd.hip).  (c) Pooled: nothing is asserted about which rows are zero -- attention carries the gradient
+    of token T-1 to every row.  (d) Across precisions: the relative Frobenius error of the bf16 d_x0 against the exact-fp32
+    step's is at most 0.03, the bound tests/test_gpu_backward_widths.py holds the bf16 d_mel to (d_x0 is the same
+    gradient with the stem backward left off)."""
+    from gw_whisper_amd import ops
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    dims = (128, 2, 2, 512)
+    sd = synth.encoder_state_dict(*dims, seed=3)
+    mel = ops.logmel(T.from_numpy(synth.strain_segments(1, seed=41)).cuda()).float().contiguous()
+    g = T.Generator().manual_seed(11)
+    d_hidden = T.randn((1, dims[0]) if pooled else (1, 1500, dims[0]), generator=g).cuda()
+    x0 = {}
+    for precision in ("bf16", "fp32"):
+        enc = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(*dims), precision=precision).cuda()
+        a, _ = _c_step(T, enc, mel, pooled, d_hidden, True, False)
+        assert bool(T.isfinite(a).all()) and float(a.abs().max()) > 0, precision
+        b, b_mel = _c_step(T, enc, mel, pooled, d_hidden, True, True)
+        _, c_mel = _c_step(T, enc, mel, pooled, d_hidden, False, True)
+        assert T.equal(a, b), precision
+        assert bool(T.isfinite(c_mel).all()) and float(c_mel.abs().max()) > 0 and T.equal(b_mel, c_mel), precision
+        x0[precision] = a.double()
+    rel = float((x0["bf16"] - x0["fp32"]).norm() / x0["fp32"].norm())
+    print(f"d_x0 {'pooled' if pooled else 'dense'}: relative Frobenius error bf16 against fp32 {rel:.5f} (bound 0.03)")
+    assert rel <= 0.03, rel
+
+
 def test_run_train_harness_end_to_end(T, gww, tmp_path):
     """harness/run_train.py (counterpart of Signal_vs_Noise/run_train.py): two epochs on synthetic chirps with the
     reduced encoder: the loss goes down, the artefacts have the reference's names and load back."""

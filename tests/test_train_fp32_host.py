@@ -1,5 +1,6 @@
 """CPU-side checks of the exact-fp32 training step's C entries: exported and bound, and bad arguments (NULL handles and
-pointers, ranks outside 1..64) rejected before any HIP call; the harness flag."""
+pointers, ranks outside 1..64) rejected before any HIP call; the target checks it shares with the bf16 backward entries
+(ranks, NULL pointers, duplicates); the harness flag."""
 
 import ctypes as C
 import os
@@ -84,17 +85,39 @@ def test_fp32_entries_reject_each_null_pointer():
         assert b"NULL" in lib.gww_last_error(), i
 
 
+def _backward_entries(lib):
+    """(name, call(targets, n)) of the three backward entry points on fake, never dereferenced arguments."""
+    head = [_fake(0), 2, _fake(1), 1 << 20, _fake(2), 1 << 20, _fake(3)]
+    return [("gww_encoder_train_backward", lambda t, n: lib.gww_encoder_train_backward(*head, t, n, None, None, 0, None)),
+            ("gww_encoder_train_backward_full",
+             lambda t, n: lib.gww_encoder_train_backward_full(*head, t, n, None, None, 0, None, None)),
+            ("gww_encoder_train_backward_f32", lambda t, n: lib.gww_encoder_train_backward_f32(*head, t, n, None, None, 0, None))]
+
+
 def test_fp32_backward_rejects_target_ranks_before_any_hip_call():
-    """The per-target checks of gww_encoder_train_backward_f32: rank 0 or 65 and a NULL gradient pointer are refused
-    before the handle is read or anything is launched."""
+    """The per-target checks shared by gww_encoder_train_backward_f32 and the two bf16 entries (check_targets,
+    csrc/encoder_impl.h): rank 0 or 65 and a NULL gradient pointer are refused before the handle is read or anything is
+    launched."""
     lib = gw_whisper_amd.lib()
-    for r, null_dm in ((0, False), (65, False), (8, True)):
-        t = (_lib.DoraTarget * 1)()
-        t[0] = _lib.DoraTarget(0, 4, r, 4.0, *(_fake(10 + j).value for j in range(6)), None if null_dm else _fake(20).value)
-        rc = lib.gww_encoder_train_backward_f32(_fake(0), 2, _fake(1), 1 << 20, _fake(2), 1 << 20, _fake(3), t, 1, None,
-                                                None, 0, None)
-        assert rc == -1, r
-        assert (b"NULL pointer in target" if null_dm else b"rank") in lib.gww_last_error(), r
+    for name, call in _backward_entries(lib):
+        for r, null_dm in ((0, False), (65, False), (8, True)):
+            t = (_lib.DoraTarget * 1)()
+            t[0] = _lib.DoraTarget(0, 4, r, 4.0, *(_fake(10 + j).value for j in range(6)), None if null_dm else _fake(20).value)
+            assert call(t, 1) == -1, (name, r)
+            assert (b"NULL pointer in target" if null_dm else b"rank") in lib.gww_last_error(), (name, r)
+
+
+def test_backward_entries_refuse_duplicate_targets_before_any_hip_call():
+    """Two targets with the same (layer, proj) are refused by all three backward entry points with the argument-error
+    status, before the handle is read or anything is launched, and the message names the duplicate."""
+    lib = gw_whisper_amd.lib()
+    for name, call in _backward_entries(lib):
+        t = (_lib.DoraTarget * 3)()
+        for i, (layer, proj) in enumerate(((1, 3), (0, 0), (1, 3))):
+            t[i] = _lib.DoraTarget(layer, proj, 8, 4.0, *(_fake(10 + 7 * i + j).value for j in range(7)))
+        assert call(t, 3) == -1, name
+        err = lib.gww_last_error()
+        assert b"duplicate" in err and b"layer 1 proj 3" in err and b"0 and 2" in err, (name, err)
 
 
 def test_fp32_adapter_grads_rejects_misaligned_scratch():

@@ -7,7 +7,8 @@ Cases: bf16 inference on whisper-tiny (hidden, last token, both; per-layer outpu
 log-mel that takes the stem shortcut and a dense one that does not), at d = 512 / 768 (the generic pooled last layer),
 with 128 mels, in fp32; the bf16 training step on tiny dims pooled and unpooled (rank-8 q/k/v DoRA, rank-8 out_proj,
 all-linear rank 4, plain LoRA, full fine-tuning with d_mel), at d = 512 / 768 / 128; the fp32 step pooled and unpooled
-(all-linear, d_mel); and every gww_*_bytes query of the named sizes at 1 / 32 / 64 / 256 segments.
+(all-linear, d_mel); what only the C entries can ask for, through ctypes (d_x0 alone and with d_mel, base gradients together
+with all-linear rank-4 targets through gww_encoder_train_backward_full, d_x0 of the fp32 entry); and every gww_*_bytes query of the named sizes at 1 / 32 / 64 / 256 segments.
 
 Arrays above 4 M elements are stored as their SHA-256 and their first 4096 values.  The gradients that are
 summed with float atomics are listed under ``atomic``: every adapter gradient of the d = 128 step (k_dora_grads adds dA,
@@ -185,6 +186,88 @@ def training(torch, rec):
         del model, params
 
 
+def c_entries(torch, rec):
+    """What only the C ABI can ask of the training step, through ctypes on the encoder's handle and the *_bytes queries:
+    tiny-width two-layer dims, 2 segments, pooled and dense.  d_x0 with no targets; d_x0 with d_mel; base gradients
+    (every field) together with an all-linear rank-4 DoRA target set through gww_encoder_train_backward_full, run twice
+    (run0 / run1: the same step again on re-zeroed buffers, which shows whether anything on that path sums with float
+    atomics); d_x0 through the fp32 entry.  The adapters are merged into the weights the encoder packs, as peft would."""
+    from gw_whisper_amd import _lib, synth
+    from gw_whisper_amd import encoder as _enc
+    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    lib = _lib.lib()
+    dims, B, r, scaling = (384, 2, 6, 1536), 2, 4, 8.0
+    mel = mels(torch, B)[0].float().contiguous()
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
+    sd = synth.encoder_state_dict(*dims, seed=3)
+    base_shapes = {None: {f: sd[f"{path}.{attr}"].shape for f, path, attr in _enc._fields(_enc._GLOBALS)}}
+    for li in range(dims[1]):
+        base_shapes[li] = {f: sd[f"layers.{li}.{path}.{attr}"].shape for f, path, attr in _enc._fields(_enc._LAYER)}
+    adapters, sd_merged = [], dict(sd)
+    for li in range(dims[1]):
+        for row in _enc._LAYER:
+            if row[4] is not None:
+                name = f"layers.{li}.{row[0]}.weight"
+                A, Bm, mag = synth.dora_adapter(*sd[name].shape, r, sd[name], seed=90 + len(adapters))
+                Wd = sd[name] + scaling * (Bm @ A)
+                nrm = np.linalg.norm(Wd, axis=1).astype(np.float32)
+                sd_merged[name] = ((mag / nrm)[:, None] * Wd).astype(np.float32)
+                adapters.append((li, row[4], row[0], [dev(x) for x in (A, Bm, mag, nrm)]))
+
+    def step(enc, key, pooled, want_x0, want_mel, with_targets=False, bwd="gww_encoder_train_backward"):
+        sfx = "_f32" if bwd.endswith("_f32") else ""
+        g = torch.Generator().manual_seed(7)
+        d_hidden = torch.randn((B, dims[0]) if pooled else (B, 1500, dims[0]), generator=g).cuda()
+        enc._sync_weights()
+        h = enc._ensure_handle()
+        ws_query = "gww_train_workspace_bytes" + ("_full" if bwd.endswith("_full") else sfx)
+        ws = torch.empty((getattr(lib, ws_query)(h, B),), dtype=torch.uint8, device="cuda")
+        saved = torch.empty((getattr(lib, "gww_train_saved_bytes" + sfx)(h, B),), dtype=torch.uint8, device="cuda")
+        hidden = torch.empty_like(d_hidden)
+        stream = torch.cuda.current_stream().cuda_stream
+        _lib.check(getattr(lib, "gww_encoder_train_forward" + sfx)(
+            h, mel.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(), int(pooled),
+            stream), "train_forward" + sfx)
+        rec.put(key + "/out", hidden)
+        d_x0 = torch.zeros((B, 1500, dims[0]), device="cuda") if want_x0 else None
+        d_mel = torch.zeros_like(mel) if want_mel else None
+        arr, named, extra = (_lib.DoraTarget * max(len(adapters), 1))(), [], ()
+        if with_targets:
+            for i, (li, pid, mod, (A, Bm, mag, nrm)) in enumerate(adapters):
+                dA, dB, dm = torch.zeros_like(A), torch.zeros_like(Bm), torch.zeros_like(mag)
+                arr[i] = _lib.DoraTarget(li, pid, r, scaling, A.data_ptr(), Bm.data_ptr(), mag.data_ptr(), nrm.data_ptr(),
+                                         dA.data_ptr(), dB.data_ptr(), dm.data_ptr())
+                named += [(f"layers.{li}.{mod}.{n}", t) for n, t in (("dA", dA), ("dB", dB), ("dm", dm))]
+        if bwd.endswith("_full"):
+            gl, layers = _lib.EncGrads(), (_lib.EncLayerGrads * dims[1])()
+            gl.layers = layers
+            for li, fields in base_shapes.items():
+                for f, shape in fields.items():
+                    buf = torch.zeros(tuple(shape), device="cuda")
+                    setattr(gl if li is None else layers[li], f, buf.data_ptr())
+                    named.append((f"base.{f}" if li is None else f"base.layers.{li}.{f}", buf))
+            extra = (C.byref(gl),)
+        _lib.check(getattr(lib, bwd)(
+            h, B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), d_hidden.data_ptr(), arr,
+            len(adapters) if with_targets else 0, d_x0.data_ptr() if want_x0 else None,
+            d_mel.data_ptr() if want_mel else None, int(pooled), *extra, stream), bwd)
+        torch.cuda.synchronize()
+        for n, t in named + [("d_x0", d_x0), ("d_mel", d_mel)]:
+            if t is not None:
+                rec.put(f"{key}/{n}", t)
+
+    plain = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(*dims), precision="bf16").cuda()
+    merged = WhisperEncoder.from_numpy_state_dict(sd_merged, WhisperConfig(*dims), precision="bf16").cuda()
+    plain32 = WhisperEncoder.from_numpy_state_dict(sd, WhisperConfig(*dims), precision="fp32").cuda()
+    for pooled in (True, False):
+        mode = "pooled" if pooled else "dense"
+        step(plain, f"c/x0/{mode}", pooled, True, False)
+        step(plain, f"c/x0_mel/{mode}", pooled, True, True)
+        for run in (0, 1):
+            step(merged, f"c/full_all_r4/{mode}/run{run}", pooled, False, False, True, "gww_encoder_train_backward_full")
+        step(plain32, f"c/fp32_x0/{mode}", pooled, True, False, bwd="gww_encoder_train_backward_f32")
+
+
 def sizes(rec):
     from gw_whisper_amd import _lib, synth
     lib = _lib.lib()
@@ -233,7 +316,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
     ap.add_argument("--out", default="encoder_paths.npz")
     ap.add_argument("--compare", nargs=2, metavar=("A", "B"), help="compare two results instead of running")
-    ap.add_argument("--only", choices=["inference", "training", "sizes"], default=None)
+    ap.add_argument("--only", choices=["inference", "training", "c-entries", "sizes"], default=None)
     ap.add_argument("--inference-trace", action="store_true",
                     help="only the inference section, with the encoder's span count per kernel class of every forward "
                          "(for the laboratory library under each GWW_GENERIC_PATH mask, one process per mask)")
@@ -250,6 +333,8 @@ def main():
         inference(torch, rec, trace=args.inference_trace)
     if args.only in (None, "training"):
         training(torch, rec)
+    if args.only in (None, "c-entries"):
+        c_entries(torch, rec)
     torch.cuda.synchronize()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     np.savez(args.out, atomic=np.asarray(rec.atomic, dtype=str), **rec.out)
