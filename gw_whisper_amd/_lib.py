@@ -216,6 +216,17 @@ SIGNATURES = {
                                             C.c_void_p]),
     "gww_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "gww_det_head_forward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 10),
+    "gww_det_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gww_det_head_backward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+                                  + [C.c_void_p] * 12),
+    "gww_det_head_scores_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
+                                          C.c_void_p]),
+    "gww_det_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
+    "gww_score_thresholds_workspace_bytes": (C.c_size_t, []),
+    "gww_score_thresholds_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "gww_detection_counts_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

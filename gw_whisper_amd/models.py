@@ -6,6 +6,7 @@ load unchanged -- SURVEY.md appendix A) and forward semantics as
   * ``Signal_vs_Noise/src/model.py:4-29``   two_channel_ligo_binary_classifier
   * ``Signal_vs_Noise/src/model.py:31-52``  one_channel_ligo_binary_classifier
   * ``Glitch_classification/src/model.py:4-39``  (multi-class head with Dropout(0.3))
+  * ``Signal_vs_Noise/Efficiency_test/src/network.py:69-90``  efficiency_classifier (2-way Softmax head)
 
 The reference's own classes also work unchanged on a ``gw_whisper_amd`` encoder (they only
 call ``encoder(mel).last_hidden_state[:, -1, :]`` and read ``encoder.config.d_model``);
@@ -73,6 +74,25 @@ class glitch_classifier(nn.Module):
             nn.Linear(512, 256), nn.ReLU(), nn.Dropout(0.3),
             nn.Linear(256, 128), nn.ReLU(), nn.Dropout(0.3),
             nn.Linear(128, num_classes))
+
+    def forward(self, mel_tensor_0):
+        return self.classifier(_pooled(self.encoder, mel_tensor_0))
+
+
+class efficiency_classifier(nn.Module):
+    """``Signal_vs_Noise/Efficiency_test/src/network.py:69-90`` (there also named
+    ``one_channel_ligo_binary_classifier``): d -> 512 -> 256 -> 128 -> 64 -> C with a trailing ``Softmax(dim=1)``, slots
+    ``0 2 4 6 8`` as there, so the reference's ``dense_layers_*.pth`` load unchanged."""
+
+    def __init__(self, encoder, num_classes=2):
+        super().__init__()
+        self.encoder = encoder
+        self.classifier = nn.Sequential(
+            nn.Linear(self.encoder.config.d_model, 512), nn.ReLU(),
+            nn.Linear(512, 256), nn.ReLU(),
+            nn.Linear(256, 128), nn.ReLU(),
+            nn.Linear(128, 64), nn.ReLU(),
+            nn.Linear(64, num_classes), nn.Softmax(dim=1))
 
     def forward(self, mel_tensor_0):
         return self.classifier(_pooled(self.encoder, mel_tensor_0))

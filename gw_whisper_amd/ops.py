@@ -913,3 +913,142 @@ def eval_accumulate(logits, labels, row_loss, confusion, loss_sum, n):
         check(lib().gww_eval_accumulate(logits.data_ptr(), labels.data_ptr(), row_loss.data_ptr(), B, C,
                                         confusion.data_ptr(), loss_sum.data_ptr(), n.data_ptr(), _stream()),
               "gww_eval_accumulate")
+
+
+DET_WIDTHS = (512, 256, 128, 64)   # hidden widths of models.efficiency_classifier's head (Efficiency_test/src/network.py:73-85)
+SCORE_PROB0, SCORE_LOGIT_DIFF = 0, 1
+MAX_FAPS = 8
+
+
+def _det_params(params):
+    if len(params) != 10:
+        raise _lib.GwwError("det_head: expected (w1, b1, w2, b2, w3, b3, w4, b4, w5, b5)")
+    ps = [_dev(p, torch.float32, "head parameter") for p in params]
+    d_in, C = ps[0].shape[1], ps[8].shape[0]
+    shapes = [(512, d_in), (512,), (256, 512), (256,), (128, 256), (128,), (64, 128), (64,), (C, 64), (C,)]
+    for p, s in zip(ps, shapes):
+        if tuple(p.shape) != s:
+            raise _lib.GwwError(f"det_head: parameter of shape {tuple(p.shape)} where the detection head d_in -> 512 -> 256 "
+                                f"-> 128 -> 64 -> C has {s}")
+    return ps, d_in, C
+
+
+def det_head_forward(x, params, targets, epsilon: float = 1e-6):
+    """Detection head + Softmax + regularised BCELoss forward (``gww_det_head_forward_f32``, 2 launches): x fp32 [B, d_in],
+    params the ten ``nn.Linear`` tensors of ``efficiency_classifier.classifier`` in order, targets fp32 [B, C] in [0, 1].
+    Returns (loss [1] device scalar, logits [B, C], probs [B, C], row_loss [B], saved) with ``saved`` what
+    ``det_head_backward`` needs."""
+    x = _dev(x, torch.float32, "x")
+    targets = _dev(targets, torch.float32, "targets")
+    ps, d_in, C = _det_params(params)
+    if x.dim() != 2 or x.shape[1] != d_in or tuple(targets.shape) != (x.shape[0], C):
+        raise _lib.GwwError(f"det_head_forward: x {tuple(x.shape)} / targets {tuple(targets.shape)} do not fit d_in = {d_in}, "
+                            f"C = {C}")
+    B, dev = x.shape[0], x.device
+    h = [torch.empty((B, w), dtype=torch.float32, device=dev) for w in DET_WIDTHS]
+    logits, probs, dz = (torch.empty((B, C), dtype=torch.float32, device=dev) for _ in range(3))
+    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    loss = torch.empty((1,), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_det_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], targets.data_ptr(), B, d_in, C,
+                                             float(epsilon), *[t.data_ptr() for t in h], logits.data_ptr(), probs.data_ptr(),
+                                             row_loss.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
+              "gww_det_head_forward_f32")
+    return loss, logits, probs, row_loss, (x, ps, h, dz)
+
+
+def det_head_backward(saved, dloss=None, ws=None):
+    """(dx [B, d_in], [dw1, db1, ..., dw5, db5]) of ``det_head_forward``'s loss times the device scalar ``dloss``
+    (``gww_det_head_backward_f32``, 2 launches; no host sync).  ``ws``: a caller's fp32 workspace of at least
+    ``gww_det_head_workspace_bytes(B, C)`` bytes (allocated here when None)."""
+    x, ps, h, dz = saved
+    B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
+    if dloss is not None:
+        dloss = _dev(dloss.reshape(1), torch.float32, "dloss")
+    if ws is None:
+        ws = torch.empty((lib().gww_det_head_workspace_bytes(B, C) // 4,), dtype=torch.float32, device=dev)
+    ws = _dev(ws, torch.float32, "ws")
+    dx = torch.empty_like(x)
+    grads = [torch.empty_like(t) for t in ps]
+    with torch.cuda.device(dev):
+        check(lib().gww_det_head_backward_f32(x.data_ptr(), *[ps[i].data_ptr() for i in (0, 2, 4, 6, 8)],
+                                              *[t.data_ptr() for t in h], dz.data_ptr(),
+                                              None if dloss is None else dloss.data_ptr(), B, d_in, C, ws.data_ptr(),
+                                              ws.numel() * 4, dx.data_ptr(), *[g.data_ptr() for g in grads], _stream()),
+              "gww_det_head_backward_f32")
+    return dx, grads
+
+
+def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
+    """One score per row of x into ``out`` (``gww_det_head_scores_f32``, one launch, inference only): ``probs[:, 0]``
+    (mode SCORE_PROB0) or ``z0 - z1`` (SCORE_LOGIT_DIFF, C = 2).  ``out``: a 1-d fp32 GPU view of B elements, of any
+    stride -- a slice of the score buffer of a whole pass."""
+    x = _dev(x, torch.float32, "x")
+    ps, d_in, C = _det_params(params)
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != d_in:
+        raise _lib.GwwError(f"det_head_scores: x {tuple(x.shape)} does not fit d_in = {d_in}")
+    if not out.is_cuda or out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != B or (B > 1 and out.stride(0) < 1):
+        raise _lib.GwwError(f"det_head_scores: out must be a 1-d fp32 GPU view of {B} elements with a positive stride")
+    with torch.cuda.device(x.device):
+        check(lib().gww_det_head_scores_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d_in, C, int(mode), out.data_ptr(),
+                                            max(out.stride(0), 1), _stream()), "gww_det_head_scores_f32")
+    return out
+
+
+def _state(t, dt, shape, who, name):
+    if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+        raise _lib.GwwError(f"{who}: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
+
+
+def det_eval_accumulate(probs, targets, row_loss, correct, loss_sum, n, batches):
+    """One batch into the device-resident evaluation state (``gww_det_eval_accumulate``, one launch, no host sync):
+    correct int64 [1], loss_sum fp64 [1] (sum of the batches' mean losses), n int64 [1], batches int64 [1]."""
+    probs = _dev(probs, torch.float32, "probs")
+    targets = _dev(targets, torch.float32, "targets")
+    row_loss = _dev(row_loss, torch.float32, "row_loss")
+    B, C = probs.shape
+    if tuple(targets.shape) != (B, C) or tuple(row_loss.shape) != (B,):
+        raise _lib.GwwError("det_eval_accumulate: targets must be [B, C] and row_loss [B]")
+    for t, dt, name in ((correct, torch.int64, "correct"), (loss_sum, torch.float64, "loss_sum"), (n, torch.int64, "n"),
+                        (batches, torch.int64, "batches")):
+        _state(t, dt, (1,), "det_eval_accumulate", name)
+    with torch.cuda.device(probs.device):
+        check(lib().gww_det_eval_accumulate(probs.data_ptr(), targets.data_ptr(), row_loss.data_ptr(), B, C, correct.data_ptr(),
+                                            loss_sum.data_ptr(), n.data_ptr(), batches.data_ptr(), _stream()),
+              "gww_det_eval_accumulate")
+
+
+def score_thresholds(scores, ranks, ws=None):
+    """thr fp32 [F] with ``thr[f] = sort(scores)[N - ranks[f]]`` (rank 0: the smallest score, the reference's
+    ``noise_outputs[-0]``), selected on the device (``gww_score_thresholds_f32``, no sort, no host sync).  scores fp32 [N],
+    ranks int64 [F] on the GPU, F <= 8, every rank in 0..N (the caller's contract: they are device values)."""
+    scores = _dev(scores, torch.float32, "scores")
+    ranks = _dev(ranks, torch.int64, "ranks")
+    if scores.dim() != 1 or ranks.dim() != 1 or scores.numel() < 1 or not 1 <= ranks.numel() <= MAX_FAPS:
+        raise _lib.GwwError(f"score_thresholds: scores must be [N >= 1] and ranks [1..{MAX_FAPS}]")
+    need = lib().gww_score_thresholds_workspace_bytes()
+    if ws is None:
+        ws = torch.empty(((need + 7) // 8,), dtype=torch.int64, device=scores.device)
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.GwwError("score_thresholds: ws must be a contiguous GPU tensor")
+    thr = torch.empty((ranks.numel(),), dtype=torch.float32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        check(lib().gww_score_thresholds_f32(scores.data_ptr(), scores.numel(), ranks.data_ptr(), ranks.numel(), thr.data_ptr(),
+                                             ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+              "gww_score_thresholds_f32")
+    return thr
+
+
+def detection_counts(scores, thr, counts):
+    """``counts[f] += #{scores > thr[f]}`` in place (``gww_detection_counts_f32``, one launch, no host sync): scores fp32
+    [n], thr fp32 [F], counts a contiguous int64 [F] GPU view, such as one row of an [S, F] table."""
+    scores = _dev(scores, torch.float32, "scores")
+    thr = _dev(thr, torch.float32, "thr")
+    F = thr.numel()
+    if scores.dim() != 1 or scores.numel() < 1 or thr.dim() != 1 or not 1 <= F <= MAX_FAPS:
+        raise _lib.GwwError(f"detection_counts: scores must be [n >= 1] and thr [1..{MAX_FAPS}]")
+    _state(counts, torch.int64, (F,), "detection_counts", "counts")
+    with torch.cuda.device(scores.device):
+        check(lib().gww_detection_counts_f32(scores.data_ptr(), scores.numel(), thr.data_ptr(), F, counts.data_ptr(), _stream()),
+              "gww_detection_counts_f32")

@@ -630,6 +630,54 @@ int gww_head_dropout_mask_f32(unsigned long long seed, unsigned long long offset
  * order, n (int64) += B; all three are device buffers the host reads once per epoch.  C 1..64, B 1..65536. */
 int gww_eval_accumulate(const float* logits, const long long* labels, const float* row_loss, int B, int C,
                         long long* confusion, double* loss_sum, long long* n, void* stream);
+/* Detection head step (detect.hip; the conventions of the glitch head: exact fp32 MFMA chains, no float atomics, identical
+ * calls give identical bits, plain launches, no synchronisation).  The head is models.efficiency_classifier's
+ * nn.Sequential (Signal_vs_Noise/Efficiency_test/src/network.py:69-90; GWWhisperClassifier has the same stack):
+ * x [B, d_in] -> Linear 512 -> ReLU -> Linear 256 -> ReLU -> Linear 128 -> ReLU -> Linear 64 -> ReLU -> Linear C ->
+ * Softmax(dim=1), reg_BCELoss(dim=C, epsilon) (tools.py:181-191) against targets [B, C] (float in [0, 1]).
+ * d_in a multiple of 128 in 128..1280, C 2..64, B 1..65536, 0 <= epsilon < 1 / C; w_i [out, in] and b_i [out] as nn.Linear
+ * stores them; x, w_i, b1..b4, h_i, ws, dx and dw_i 16-byte aligned.
+ * Forward (2 launches): writes h1 [B, 512], h2 [B, 256], h3 [B, 128], h4 [B, 64] (post-ReLU), logits [B, C], probs [B, C],
+ * row_loss [B] = sum over c of -[t log q + (1 - t) log(1 - q)] with q = epsilon + (1 - C epsilon) p and both logs clamped
+ * at -100 as nn.BCELoss clamps them, the device scalar loss = sum(row_loss) / (B C) (fp64 partial sums in a fixed tree),
+ * and dz [B, C] = d loss / d logits through the softmax, with torch's (q - t) / max((1 - q) q, 1e-12) / (B C) as the q
+ * derivative.  1 - p_c and 1 - q_c are formed from the sum of the other classes' exponentials, never by subtraction;
+ * everything behind the fp32 logits is evaluated in fp64 and rounded to fp32 once per output.
+ * Backward (2 launches): reads the upstream gradient of the loss from the device scalar dloss (NULL: 1), writes
+ * dx [B, d_in] and the ten parameter gradients (not accumulated); ws: gww_det_head_workspace_bytes(B, C) bytes, refused
+ * before any launch when ws_bytes is smaller.
+ * Scores (1 launch, inference only): out[r * out_stride] = probs[r, 0] (mode 0) or z0 - z1 (mode 1, C = 2 only: column 0
+ * of the reference's remove_softmax layer [[1, -1], [-1, 1]]), bit for bit what the forward gives. */
+int gww_det_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                             const float* b5, const float* targets, int B, int d_in, int C, float epsilon, float* h1,
+                             float* h2, float* h3, float* h4, float* logits, float* probs, float* row_loss, float* dz,
+                             float* loss, void* stream);
+size_t gww_det_head_workspace_bytes(int B, int C);
+int gww_det_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
+                              const float* w5, const float* h1, const float* h2, const float* h3, const float* h4,
+                              const float* dz, const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes,
+                              float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dw4,
+                              float* db4, float* dw5, float* db5, void* stream);
+int gww_det_head_scores_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                            const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                            const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride, void* stream);
+/* Evaluation accumulate, one one-workgroup launch per batch: correct (int64) += the rows with argmax(targets) ==
+ * argmax(probs) (a NaN is the maximum, ties go to the lowest index), loss_sum (fp64) += the batch's mean loss
+ * (float)(sum(row_loss) / (B C)), one writer, n (int64) += B, batches (int64) += 1: the reference's validation loss is
+ * loss_sum / batches (train.py:150).  C 2..64, B 1..65536. */
+int gww_det_eval_accumulate(const float* probs, const float* targets, const float* row_loss, int B, int C,
+                            long long* correct, double* loss_sum, long long* n, long long* batches, void* stream);
+/* thr[f] = sorted_ascending(scores)[N - ranks[f]] for 1 <= ranks[f] <= N, sorted[0] for ranks[f] == 0 (the reference's
+ * noise_outputs[-0], tools.py:354); a NaN orders as the largest value, as torch.sort orders it.  Radix select over the
+ * order-preserving integer image of fp32: four histogram passes for all F <= 8 ranks together (9 launches, integer
+ * atomics only).  scores [N] fp32, ranks [F] int64 and thr [F] on the device; ws: gww_score_thresholds_workspace_bytes()
+ * bytes, 8-byte aligned, refused before any launch when ws_bytes is smaller.  N 1..2^31-1. */
+size_t gww_score_thresholds_workspace_bytes(void);
+int gww_score_thresholds_f32(const float* scores, long N, const long long* ranks, int F, float* thr, void* ws,
+                             size_t ws_bytes, void* stream);
+/* counts[f] (int64, device) += #{i < n: scores[i] > thr[f]}, the strict comparison of tools.py:365; F 1..8. */
+int gww_detection_counts_f32(const float* scores, long n, const float* thr, int F, long long* counts, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
