@@ -227,6 +227,17 @@ SIGNATURES = {
     "gww_score_thresholds_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                            C.c_void_p]),
     "gww_detection_counts_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gww_roc_tile": (C.c_int, []),
+    "gww_roc_sort_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_roc_sort_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gww_roc_curve_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_roc_curve_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gww_roc_bootstrap_workspace_bytes": (C.c_size_t, [C.c_long, C.c_long]),
+    "gww_roc_bootstrap_tpr_f64": (C.c_int, [C.c_void_p] * 5 + [C.c_long, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "gww_roc_band_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gww_binary_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

@@ -1052,3 +1052,134 @@ def detection_counts(scores, thr, counts):
     with torch.cuda.device(scores.device):
         check(lib().gww_detection_counts_f32(scores.data_ptr(), scores.numel(), thr.data_ptr(), F, counts.data_ptr(), _stream()),
               "gww_detection_counts_f32")
+
+
+# ---- signal-vs-noise evaluation: ROC curve, AUC, bootstrap band (csrc/roc.hip) ----------------------------------------
+ROC_TILE = 16384        # include/gww.h GWW_ROC_TILE: sorted positions of one LDS tile of the bootstrap kernel
+ROC_MAX_N = 1 << 24
+ROC_MAX_Q = 1024
+
+
+def _roc_ws(ws, need, device, who):
+    if ws is None:
+        ws = torch.empty((need,), dtype=torch.uint8, device=device)
+    if not ws.is_cuda or not ws.is_contiguous():
+        raise _lib.GwwError(f"{who}: ws must be a contiguous GPU tensor")
+    return ws
+
+
+def roc_sort(scores, labels, ws=None):
+    """Stable descending sort of the scores on the device (``gww_roc_sort_f32``, no host sync).  scores, labels fp32 [N],
+    2 <= N <= 2^24; a label is positive iff it is > 0.5.  Returns (order int32 [N], rank int32 [N], pos uint8 [N],
+    gend int32 [N] of which the first G entries are written, G int32 [1], n_nan int32 [1])."""
+    scores = _dev(scores, torch.float32, "scores")
+    labels = _dev(labels, torch.float32, "labels")
+    N = scores.numel()
+    if scores.dim() != 1 or tuple(labels.shape) != (N,) or not 2 <= N <= ROC_MAX_N:
+        raise _lib.GwwError("roc_sort: scores and labels must be [N] with 2 <= N <= 2^24")
+    dev = scores.device
+    ws = _roc_ws(ws, lib().gww_roc_sort_workspace_bytes(N), dev, "roc_sort")
+    order = torch.empty((N,), dtype=torch.int32, device=dev)
+    rank = torch.empty((N,), dtype=torch.int32, device=dev)
+    pos = torch.empty((N,), dtype=torch.uint8, device=dev)
+    gend = torch.empty((N,), dtype=torch.int32, device=dev)
+    G = torch.empty((1,), dtype=torch.int32, device=dev)
+    n_nan = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_roc_sort_f32(scores.data_ptr(), labels.data_ptr(), N, order.data_ptr(), rank.data_ptr(), pos.data_ptr(),
+                                     gend.data_ptr(), G.data_ptr(), n_nan.data_ptr(), ws.data_ptr(),
+                                     ws.numel() * ws.element_size(), _stream()), "gww_roc_sort_f32")
+    return order, rank, pos, gend, G, n_nan
+
+
+def roc_curve(pos, gend, G, ws=None):
+    """``sklearn.metrics.roc_curve(drop_intermediate=False)`` and the AUC from the sort's pos / gend / G
+    (``gww_roc_curve_f64``, one launch, no host sync).  Returns (fps int64 [N + 1], tps int64 [N + 1], fpr fp64 [N + 1],
+    tpr fp64 [N + 1] -- G + 1 entries of each are written --, counts int64 [2] = (P, Nneg), auc fp64 [1])."""
+    pos = _dev(pos, torch.uint8, "pos")
+    gend = _dev(gend, torch.int32, "gend")
+    N = pos.numel()
+    if pos.dim() != 1 or tuple(gend.shape) != (N,) or not 2 <= N <= ROC_MAX_N:
+        raise _lib.GwwError("roc_curve: pos and gend must be [N] with 2 <= N <= 2^24")
+    _state(G, torch.int32, (1,), "roc_curve", "G")
+    dev = pos.device
+    ws = _roc_ws(ws, lib().gww_roc_curve_workspace_bytes(N), dev, "roc_curve")
+    fps = torch.empty((N + 1,), dtype=torch.int64, device=dev)
+    tps = torch.empty((N + 1,), dtype=torch.int64, device=dev)
+    fpr = torch.empty((N + 1,), dtype=torch.float64, device=dev)
+    tpr = torch.empty((N + 1,), dtype=torch.float64, device=dev)
+    counts = torch.empty((2,), dtype=torch.int64, device=dev)
+    auc = torch.empty((1,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_roc_curve_f64(pos.data_ptr(), gend.data_ptr(), G.data_ptr(), N, fps.data_ptr(), tps.data_ptr(),
+                                      fpr.data_ptr(), tpr.data_ptr(), counts.data_ptr(), auc.data_ptr(), ws.data_ptr(),
+                                      ws.numel() * ws.element_size(), _stream()), "gww_roc_curve_f64")
+    return fps, tps, fpr, tpr, counts, auc
+
+
+def roc_bootstrap_tpr(rank, pos, gend, G, idx, grid, ws=None):
+    """The bootstrap replicates' TPR at the grid's FPRs (``gww_roc_bootstrap_tpr_f64``, one workgroup per replicate, no
+    host sync): idx int32 [Rc, N] draws from 0..N-1, grid fp64 [Q] ascending in (0, 1], Q <= 1024.  Returns (tpr fp64
+    [Rc, Q], valid uint8 [Rc]); a replicate without positives or negatives has valid = 0 and a row of NaN."""
+    rank = _dev(rank, torch.int32, "rank")
+    pos = _dev(pos, torch.uint8, "pos")
+    gend = _dev(gend, torch.int32, "gend")
+    idx = _dev(idx, torch.int32, "idx")
+    grid = _dev(grid, torch.float64, "grid")
+    N = rank.numel()
+    if rank.dim() != 1 or tuple(pos.shape) != (N,) or tuple(gend.shape) != (N,) or not 2 <= N <= ROC_MAX_N:
+        raise _lib.GwwError("roc_bootstrap_tpr: rank, pos and gend must be [N] with 2 <= N <= 2^24")
+    if idx.dim() != 2 or idx.shape[1] != N or not 1 <= idx.shape[0] <= 65535:
+        raise _lib.GwwError(f"roc_bootstrap_tpr: idx must be [Rc, N = {N}] with 1 <= Rc <= 65535")
+    if grid.dim() != 1 or not 1 <= grid.numel() <= ROC_MAX_Q:
+        raise _lib.GwwError(f"roc_bootstrap_tpr: grid must be [Q] with 1 <= Q <= {ROC_MAX_Q}")
+    _state(G, torch.int32, (1,), "roc_bootstrap_tpr", "G")
+    Rc, Q, dev = idx.shape[0], grid.numel(), rank.device
+    ws = _roc_ws(ws, lib().gww_roc_bootstrap_workspace_bytes(Rc, N), dev, "roc_bootstrap_tpr")
+    tpr = torch.empty((Rc, Q), dtype=torch.float64, device=dev)
+    valid = torch.empty((Rc,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_roc_bootstrap_tpr_f64(rank.data_ptr(), pos.data_ptr(), gend.data_ptr(), G.data_ptr(), idx.data_ptr(), Rc,
+                                              N, grid.data_ptr(), Q, tpr.data_ptr(), valid.data_ptr(), ws.data_ptr(),
+                                              ws.numel() * ws.element_size(), _stream()), "gww_roc_bootstrap_tpr_f64")
+    return tpr, valid
+
+
+def roc_band(tpr, valid):
+    """(mean fp64 [Q], std fp64 [Q], n_valid int32 [1]) of tpr [R, Q] over the rows with valid != 0, summed in row order as
+    ``np.mean(axis=0)`` / ``np.std(axis=0)`` do (``gww_roc_band_f64``, one launch, no host sync)."""
+    tpr = _dev(tpr, torch.float64, "tpr")
+    valid = _dev(valid, torch.uint8, "valid")
+    if tpr.dim() != 2 or tpr.shape[0] < 1 or tuple(valid.shape) != (tpr.shape[0],) or not 1 <= tpr.shape[1] <= ROC_MAX_Q:
+        raise _lib.GwwError(f"roc_band: tpr must be [R >= 1, Q <= {ROC_MAX_Q}] and valid [R]")
+    R, Q = tpr.shape
+    mean = torch.empty((Q,), dtype=torch.float64, device=tpr.device)
+    std = torch.empty((Q,), dtype=torch.float64, device=tpr.device)
+    n_valid = torch.empty((1,), dtype=torch.int32, device=tpr.device)
+    with torch.cuda.device(tpr.device):
+        check(lib().gww_roc_band_f64(tpr.data_ptr(), valid.data_ptr(), R, Q, mean.data_ptr(), std.data_ptr(), n_valid.data_ptr(),
+                                     _stream()), "gww_roc_band_f64")
+    return mean, std, n_valid
+
+
+def binary_eval_accumulate(logits, labels, scores, offset: int, loss_sum, batches, confusion):
+    """One batch into the device-resident state of a binary evaluation (``gww_binary_eval_accumulate``, one launch, no
+    host sync): ``scores[offset : offset + B] = sigmoid(logits)``, loss_sum fp64 [1] += the batch-mean
+    BCEWithLogitsLoss, batches int64 [1] += 1, confusion int64 [2, 2] (rows = the label) += the rows by
+    ``torch.round(sigmoid)``."""
+    logits = _dev(logits, torch.float32, "logits").reshape(-1)
+    labels = _dev(labels, torch.float32, "labels").reshape(-1)
+    B = logits.numel()
+    if labels.numel() != B or B < 1:
+        raise _lib.GwwError("binary_eval_accumulate: logits and labels must hold the same B >= 1 elements")
+    if not scores.is_cuda or scores.dtype != torch.float32 or scores.dim() != 1 or not scores.is_contiguous():
+        raise _lib.GwwError("binary_eval_accumulate: scores must be a contiguous GPU torch.float32 tensor [n]")
+    if not 0 <= int(offset) <= scores.numel() - B:
+        raise _lib.GwwError(f"binary_eval_accumulate: offset={offset} + B={B} exceeds the {scores.numel()} scores")
+    _state(loss_sum, torch.float64, (1,), "binary_eval_accumulate", "loss_sum")
+    _state(batches, torch.int64, (1,), "binary_eval_accumulate", "batches")
+    _state(confusion, torch.int64, (2, 2), "binary_eval_accumulate", "confusion")
+    with torch.cuda.device(logits.device):
+        check(lib().gww_binary_eval_accumulate(logits.data_ptr(), labels.data_ptr(), B, scores.data_ptr(), int(offset),
+                                               scores.numel(), loss_sum.data_ptr(), batches.data_ptr(), confusion.data_ptr(),
+                                               _stream()), "gww_binary_eval_accumulate")

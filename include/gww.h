@@ -678,6 +678,45 @@ int gww_score_thresholds_f32(const float* scores, long N, const long long* ranks
                              size_t ws_bytes, void* stream);
 /* counts[f] (int64, device) += #{i < n: scores[i] > thr[f]}, the strict comparison of tools.py:365; F 1..8. */
 int gww_detection_counts_f32(const float* scores, long n, const float* thr, int F, long long* counts, void* stream);
+/* ---- signal-vs-noise evaluation: ROC curve, AUC and the bootstrap band (csrc/roc.hip) ----
+ * Device pointers throughout, plain launches, no host synchronisation.  N is the size of the test set, 2..2^24.  A
+ * workspace is refused before any launch when it is smaller than its *_workspace_bytes function says. */
+#define GWW_ROC_TILE 16384   /* sorted positions of one LDS tile of the bootstrap kernel */
+int gww_roc_tile(void);      /* = GWW_ROC_TILE */
+/* Stable descending sort of the scores (LSD radix sort over the order-preserving integer image; -0.0 and +0.0 are one
+ * value, +-inf ordinary values).  order [N] int32: the sample at each sorted position; rank [N] int32: its inverse;
+ * pos [N] uint8: labels[order[p]] > 0.5; gend [N] int32, of which the first G entries are written: the sorted position of
+ * the last element of each run of equal scores; G and n_nan (the number of NaN scores; they sort in front): int32 on the
+ * device.  ws 16-byte aligned. */
+size_t gww_roc_sort_workspace_bytes(long N);
+int gww_roc_sort_f32(const float* scores, const float* labels, long N, int* order, int* rank, unsigned char* pos, int* gend,
+                     int* G, int* n_nan, void* ws, size_t ws_bytes, void* stream);
+/* sklearn.metrics.roc_curve(drop_intermediate=False): vertex 0 = (0, 0), vertex g + 1 at gend[g].  fps, tps int64 and
+ * fpr = fps / Nneg, tpr = tps / P fp64 (one IEEE division each), G + 1 entries of buffers of N + 1; counts int64 [2] =
+ * (P, Nneg); auc fp64 [1] = (sum_g (fps_g - fps_{g-1}) (tps_g + tps_{g-1})) / (2 P Nneg): an int64 sum and one division,
+ * NaN when one class is absent. */
+size_t gww_roc_curve_workspace_bytes(long N);
+int gww_roc_curve_f64(const unsigned char* pos, const int* gend, const int* G, long N, long long* fps, long long* tps,
+                      double* fpr, double* tpr, long long* counts, double* auc, void* ws, size_t ws_bytes, void* stream);
+/* Rc bootstrap replicates, one workgroup each: idx [Rc, N] int32 holds N draws from 0..N-1 per replicate; tpr [Rc, Q]
+ * fp64 = np.interp(grid, fpr_r, tpr_r) of the replicate's ROC curve, bit for bit; grid [Q] fp64 ascending in (0, 1],
+ * Q 1..1024, Rc 1..65535.  valid [Rc] uint8 = 0 and a row of NaN for a replicate without positives or without negatives
+ * (or with a draw outside 0..N-1).  ws: Rc rows of N x 2 uint32, 8-byte aligned; a row is written and read by its own
+ * workgroup only. */
+size_t gww_roc_bootstrap_workspace_bytes(long Rc, long N);
+int gww_roc_bootstrap_tpr_f64(const int* rank, const unsigned char* pos, const int* gend, const int* G, const int* idx, long Rc,
+                              long N, const double* grid, int Q, double* tpr, unsigned char* valid, void* ws, size_t ws_bytes,
+                              void* stream);
+/* mean [Q], std [Q] (population, np.std) of tpr [R, Q] over the rows with valid[r] != 0, summed in row order by one thread
+ * per column (numpy's axis-0 order); n_valid int32 [1].  Both NaN when no row is valid. */
+int gww_roc_band_f64(const double* tpr, const unsigned char* valid, long R, int Q, double* mean, double* std, int* n_valid,
+                     void* stream);
+/* One batch of a binary classifier's evaluation, one one-workgroup launch: scores[offset .. offset + B) =
+ * sigmoid(logits) (scores holds `capacity` floats), loss_sum (fp64) += the batch-mean BCEWithLogitsLoss rounded to fp32,
+ * batches (int64) += 1, confusion (int64 [2][2], rows = the label > 0.5) += the rows by torch.round(sigmoid): a
+ * probability of exactly 0.5 is class 0.  B 1..65536. */
+int gww_binary_eval_accumulate(const float* logits, const float* labels, int B, float* scores, long offset, long capacity,
+                               double* loss_sum, long long* batches, long long* confusion, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
