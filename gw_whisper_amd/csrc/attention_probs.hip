@@ -155,12 +155,12 @@ __global__ __launch_bounds__(256) void k_attention_probs(const void* __restrict_
 }  // namespace
 
 int launch_attention_probs(const void* qkv, bool bf16, bool q_log2, float* probs, int B, int T, int H, hipStream_t s) {
-  GWW_REQUIRE(qkv && probs, "attention_probs: NULL operand");
   GWW_REQUIRE(B >= 0 && T > 0 && H > 0, "attention_probs: bad shape B=%d T=%d H=%d", B, T, H);
   GWW_REQUIRE(T % 4 == 0, "attention_probs: T=%d must be a multiple of 4 (16-byte row stores)", T);
-  GWW_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)probs) & 15) == 0, "attention_probs: 16-byte alignment");
   GWW_REQUIRE(bf16 || !q_log2, "attention_probs: q in log2 units is a bf16-path convention");
-  if (B == 0) return GWW_OK;
+  if (B == 0) return GWW_OK;   // an empty batch has no storage: its pointers may be NULL
+  GWW_REQUIRE(qkv && probs, "attention_probs: NULL operand");
+  GWW_REQUIRE((((uintptr_t)qkv) & 15) == 0 && (((uintptr_t)probs) & 15) == 0, "attention_probs: 16-byte alignment");
   const int q_tiles = (T + PQB - 1) / PQB;
   const long blocks = (long)q_tiles * B * H;
   GWW_REQUIRE(blocks < 2147483647L, "attention_probs: grid too large");

@@ -451,6 +451,27 @@ def attention_log2q(qkv: torch.Tensor, n_heads: int, want_lse: bool = False):
     return (ctx, lse) if want_lse else ctx
 
 
+def attention_probs(qkv: torch.Tensor, n_heads: int, q_log2: bool = False) -> torch.Tensor:
+    """qkv [B, T, 3 d] (q pre-scaled; in log2 units when q_log2, bf16 only) -> the softmax maps P [B, H, T, T], fp32:
+    the ``output_attentions`` kernel on its own.  T must be a multiple of 4."""
+    bf = qkv.dtype == torch.bfloat16
+    qkv = _dev(qkv, torch.bfloat16 if bf else torch.float32, "qkv")
+    B, T, d3 = qkv.shape
+    if d3 != 3 * n_heads * 64:
+        raise _lib.GwwError(f"attention_probs: d={d3 // 3} != n_heads*64")
+    probs = torch.empty((B, n_heads, T, T), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        if bf:
+            check(lib().gww_attention_probs_bf16(qkv.data_ptr(), int(bool(q_log2)), probs.data_ptr(), B, T, n_heads,
+                                                 _stream()), "gww_attention_probs_bf16")
+        elif q_log2:
+            raise _lib.GwwError("attention_probs: q in log2 units is a bf16-path convention")
+        else:
+            check(lib().gww_attention_probs_f32(qkv.data_ptr(), probs.data_ptr(), B, T, n_heads, _stream()),
+                  "gww_attention_probs_f32")
+    return probs
+
+
 def dora_merge(w0: torch.Tensor, a: torch.Tensor, b: torch.Tensor, m: torch.Tensor, scaling: float,
                return_norm: bool = False):
     """W_eff = (m / ||W0 + s B A||_row) * (W0 + s B A)  (peft 0.12.0 dora.py), fp32."""

@@ -529,7 +529,8 @@ int gww_attention_bwd_f32(const float* qkv, const float* ctx, const float* dctx,
 /* attention probabilities P[b,h,i,j] = softmax_j(q_i . k_j), fp32 [B, n_heads, T, T] (HF eager attn_weights) from
  * qkv [B*T, 3d] as the attention kernels read it (q pre-scaled by 1/8; bf16: times log2(e) when q_log2 != 0, the
  * encoder's packed bf16 q panels).  Scores by MFMA on the given operands (bf16: 32x32x16 bf16, fp32: 32x32x2 f32);
- * each workgroup takes the row max / sum over all keys, then recomputes and stores the normalised rows.  T % 4 == 0. */
+ * each workgroup takes the row max / sum over all keys, then recomputes and stores the normalised rows.  T % 4 == 0.
+ * B == 0 is a no-op that accepts NULL buffers (after the shape checks). */
 int gww_attention_probs_bf16(const void* qkv, int q_log2, float* probs, int B, int T, int n_heads, void* stream);
 int gww_attention_probs_f32(const float* qkv, float* probs, int B, int T, int n_heads, void* stream);
 /* LayerNorm backward: dx (+)= dLN/dx . dy   (dy fp32 or bf16; optional bf16 copy of the result) */

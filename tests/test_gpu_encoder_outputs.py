@@ -18,6 +18,10 @@ pytestmark = pytest.mark.gpu
 #   HF golden, bf16: hidden 3.6e-3 relative, attention 1.4e-4      -> 1e-2, 1e-3
 #   fp64 layers, fp32: hidden 1.5e-6 relative, attention 9.6e-8    -> 1e-5, 1e-6
 #   fp64 layers, bf16: hidden 3.3e-3 relative, attention 4.0e-4    -> 1e-2, 2e-3
+#   fp64 layers at d 1280, H 20 (two layers, B 1), fp32: hidden 2.0e-6 relative, attention 1.7e-7  -> the same 1e-5, 1e-6
+#   fp64 layers at d 1280, H 20 (two layers, B 1), bf16: hidden 3.2e-3 relative, attention 4.8e-4  -> the same 1e-2, 2e-3
+# The absolute attention bounds are loose against a typical entry of 5e-4: tests/test_gpu_attention_maps.py holds the
+# map kernel itself to a relative bound per entry.
 HF_HID_F32, HF_ATT_F32 = 1e-5, 1e-6
 HF_HID_BF16, HF_ATT_BF16 = 1e-2, 1e-3
 FP64_HID = {"fp32": 1e-5, "bf16": 1e-2}
@@ -109,22 +113,29 @@ def test_outputs_match_hf_golden(T, gww, golden, name, precision):
 
 
 # ------------------------------------------------------------------------------------ 2. full geometry vs fp64
+# the two-layer cut of whisper-large's width: 20 heads, i.e. a 3840-element qkv row and, in the attention slab, a second
+# layer that starts 20 maps in
+WIDE2 = (1280, 2, 20, 5120)
+
+
 @pytest.mark.parametrize("precision", ["fp32", "bf16"])
-@pytest.mark.parametrize("name", ["tiny", "base"])
+@pytest.mark.parametrize("name", ["tiny", "base", "wide2"])
 def test_full_geometry_against_fp64(T, gww, name, precision):
-    """whisper-tiny (fused path in bf16) and whisper-base (generic path), B = 3: attentions[l] against the float64
-    softmax of LN1(hidden_states[l])'s q . k, hidden_states[l + 1] against a float64 layer applied to hidden_states[l]
-    (relative to its max |x|; the last one with the final LayerNorm), and every map row a distribution."""
-    d, L, H, F = synth.ENCODER_SIZES[name]
+    """whisper-tiny (fused path in bf16) and whisper-base (generic path), B = 3, and two layers at whisper-large's width
+    (H = 20), B = 1: attentions[l] against the float64 softmax of LN1(hidden_states[l])'s q . k, hidden_states[l + 1]
+    against a float64 layer applied to hidden_states[l] (relative to its max |x|; the last one with the final
+    LayerNorm), and every map row a distribution."""
+    d, L, H, F = WIDE2 if name == "wide2" else synth.ENCODER_SIZES[name]
+    B = 1 if name == "wide2" else 3
     enc, sd = _enc(T, d, L, H, F, 5, precision)
     p = _p64(T, sd)
-    mel = T.from_numpy(_features(41, 3)).cuda()
+    mel = T.from_numpy(_features(41, B)).cuda()
     with T.no_grad():
         o = enc(mel, output_hidden_states=True, output_attentions=True)
         ea, eh = [], []
         for l in range(L):
-            assert o.attentions[l].shape == (3, H, 1500, 1500) and o.attentions[l].dtype == T.float32
-            assert o.hidden_states[l].shape == (3, 1500, d) and o.hidden_states[l].dtype == T.float32
+            assert o.attentions[l].shape == (B, H, 1500, 1500) and o.attentions[l].dtype == T.float32
+            assert o.hidden_states[l].shape == (B, 1500, d) and o.hidden_states[l].dtype == T.float32
             xn, P = _layer64(T, p, l, o.hidden_states[l].double(), H, final=(l == L - 1))
             ea.append(float((o.attentions[l].double() - P).abs().max()))
             eh.append(float((o.hidden_states[l + 1].double() - xn).abs().max() / xn.abs().max()))
