@@ -14,8 +14,8 @@
 //            32-row query tiles:  S = Q K^T,  P = exp(S - lse),  dV^T += dO^T P,  dP = dO V^T,  dS = P (dP - D),
 //            dK^T += Q^T dS.  128 MFMAs per tile and wave.
 //   dq       per workgroup 128 queries, 4 waves x 32 queries with Q and dO in registers; loop over 32-key tiles:
-//            S^T = K Q^T,  P^T = exp(S^T - lse),  dP^T = V dO^T,  dS^T = P^T (dP^T - D),  dQ^T += K^T dS^T.
-//            96 MFMAs per tile and wave.  Dead waves store zeros.
+//            S^T = K Q^T,  P^T = exp(S^T - lse),  dP^T = V dO^T,  dS^T = P^T (dP^T - D),  dQ^T += (K - kbar)^T dS^T
+//            (kbar: the mean key, see the kernel).  96 MFMAs per tile and wave.  Dead waves store zeros.
 // v_mfma_f32_32x32x2_f32: A[i = lane&31][k = lane>>5], B[k = lane>>5][j = lane&31]; D register v of lane l holds
 // row i = (v&3) + 8 (v>>2) + 4 (l>>5), column j = l&31.
 #include "common.h"
@@ -188,6 +188,32 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq_f32(const float* __restrict
 #pragma unroll
     for (int j = 0; j < 16; ++j) dq[n][j] = 0.f;
   if (any_live) {
+    // dQ is accumulated against the CENTRED keys, dQ = sum_k dS_k (K_k - kbar): sum_k dS_k is zero in exact arithmetic, so
+    // any kbar gives the same gradient, but in fp32 that sum is rounding noise (P is recomputed from the stored lse, D comes
+    // from the forward's O) and the product kbar * noise stays in dQ.  With pretrained weights the keys of a head share a
+    // component several times their spread (LayerNorm bias through W_k), which made that term the whole error of dQ (6.7e-5
+    // of |dQ| on such keys where the other contractions hold 3e-6).  kbar = the mean key of this (b, h), summed here: one more
+    // read of K (L2 resident), no MFMA.  Thread = (rows tid >> 4, tid >> 4 + 16, ...; float4 column tid & 15); Vs is free until
+    // the first tile is staged.
+    {
+      float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int k = tid >> 4; k < T; k += 16) {
+        const float4 kv = *reinterpret_cast<const float4*>(kp + (long)k * rs + (tid & 15) * 4);
+        a.x += kv.x; a.y += kv.y; a.z += kv.z; a.w += kv.w;
+      }
+      const int row = tid >> 4, col = (tid & 15) * 4;
+      Vs[row][col] = a.x; Vs[row][col + 1] = a.y; Vs[row][col + 2] = a.z; Vs[row][col + 3] = a.w;
+    }
+    __syncthreads();
+    float kbar[2];
+#pragma unroll
+    for (int n = 0; n < 2; ++n) {
+      float a = 0.f;
+#pragma unroll
+      for (int i = 0; i < 16; ++i) a += Vs[i][32 * n + r];
+      kbar[n] = a * (1.0f / (float)T);
+    }
+    __syncthreads();   // (the first tile overwrites Vs)
     float qf[32], gf[32];   // Q[q = r][dh = 2 s + hh], dO likewise
     const float* grow = dctx + ((long)b * T + q_ld) * d + h * BDH;
 #pragma unroll
@@ -230,7 +256,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_dq_f32(const float* __restrict
           const int k = mrow(v, hh);
 #pragma unroll
           for (int n = 0; n < 2; ++n)
-            dq[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[k][32 * n + r], dp[v], dq[n], 0, 0, 0);
+            dq[n] = __builtin_amdgcn_mfma_f32_32x32x2f32(Ks[k][32 * n + r] - kbar[n], dp[v], dq[n], 0, 0, 0);
         }
       }
       __syncthreads();

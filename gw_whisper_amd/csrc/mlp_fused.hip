@@ -1137,7 +1137,9 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
     const float mean_s = s1 * (1.0f / MF_D);
     row_rstd = rsqrtf(fmaxf(s2 * (1.0f / MF_D) - mean_s * mean_s, 0.f) + 1e-5f);
     row_mean = csh + mean_s;
-    const float nm = -row_mean * row_rstd;
+    // the operand from the SHIFTED value, ((v - csh) - mean_s) rstd: v rstd - mean rstd would round mean rstd (2^-24 of up
+    // to 316 |mean|), a common-mode error of the whole row that an exactly constant row shows as a^ = +-6e-5 instead of 0
+    const float nm = -mean_s * row_rstd;
     // (a fence between the passes: without it hipcc keeps all 192 sums O + bias of pass A alive for pass B -- fifty spills)
     asm volatile("" : "+a"(oacc[0]), "+a"(oacc[1]), "+a"(oacc[2]), "+a"(oacc[3]), "+a"(oacc[4]), "+a"(oacc[5]), "+a"(oacc[6]),
                       "+a"(oacc[7]), "+a"(oacc[8]), "+a"(oacc[9]), "+a"(oacc[10]), "+a"(oacc[11]));
@@ -1149,10 +1151,10 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
         const float4 bo_ = *reinterpret_cast<const float4*>(sb + 64 * S + 32 + 8 * cc + 4 * hh);
         const f32x16& E = oacc[2 * S];
         const f32x16& O = oacc[2 * S + 1];
-        const unsigned e0 = pack2bf(fmaf(E[4 * cc] + be.x, row_rstd, nm), fmaf(E[4 * cc + 1] + be.y, row_rstd, nm));
-        const unsigned e1 = pack2bf(fmaf(E[4 * cc + 2] + be.z, row_rstd, nm), fmaf(E[4 * cc + 3] + be.w, row_rstd, nm));
-        const unsigned o0 = pack2bf(fmaf(O[4 * cc] + bo_.x, row_rstd, nm), fmaf(O[4 * cc + 1] + bo_.y, row_rstd, nm));
-        const unsigned o1 = pack2bf(fmaf(O[4 * cc + 2] + bo_.z, row_rstd, nm), fmaf(O[4 * cc + 3] + bo_.w, row_rstd, nm));
+        const unsigned e0 = pack2bf(fmaf(E[4 * cc] + be.x - csh, row_rstd, nm), fmaf(E[4 * cc + 1] + be.y - csh, row_rstd, nm));
+        const unsigned e1 = pack2bf(fmaf(E[4 * cc + 2] + be.z - csh, row_rstd, nm), fmaf(E[4 * cc + 3] + be.w - csh, row_rstd, nm));
+        const unsigned o0 = pack2bf(fmaf(O[4 * cc] + bo_.x - csh, row_rstd, nm), fmaf(O[4 * cc + 1] + bo_.y - csh, row_rstd, nm));
+        const unsigned o1 = pack2bf(fmaf(O[4 * cc + 2] + bo_.z - csh, row_rstd, nm), fmaf(O[4 * cc + 3] + bo_.w - csh, row_rstd, nm));
         // swap(x, y): x's upper 32 lanes <-> y's lower 32 lanes.  Low lanes: [0] own half of the even block, [1] the
         // partner's; high lanes: [0] the partner's half of the odd block, [1] own
         const auto w0 = __builtin_amdgcn_permlane32_swap(e0, o0, false, false);

@@ -295,29 +295,8 @@ def test_attention_bf16(T, gww, B, Tn, H):
     np.testing.assert_allclose(got, ref, atol=6e-3, rtol=2 ** -7)
 
 
-_LOG2E = 1.4426950408889634
-
-
-def _to_log2q(qkv):
-    """q section scaled by log2(e) and rounded to bf16 once: what the LN-folded q panel of the fast path produces."""
-    d = qkv.shape[-1] // 3
-    out = qkv.copy()
-    out[..., :d] = _bf(qkv[..., :d].astype(np.float64) * _LOG2E)
-    return out
-
-
-def _attn_ref_log2q(qkv_l2, H):
-    """oracle/encoder.py::attention (bf16 emulation: un-normalised bf16 P, fp32 row sum) on q / log2(e) -- restated here
-    because the oracle would round that quotient to bf16 again."""
-    B, Tn, d3 = qkv_l2.shape
-    d = d3 // 3
-    x = qkv_l2.astype(np.float64)
-    heads = lambda a: a.reshape(B, Tn, H, 64).transpose(0, 2, 1, 3)
-    q, k, v = heads(x[..., :d] / _LOG2E), heads(x[..., d:2 * d]), heads(x[..., 2 * d:])
-    s = np.matmul(q, k.transpose(0, 1, 3, 2))
-    p = np.exp(s - s.max(axis=-1, keepdims=True))
-    o = np.matmul(_bf(p.astype(np.float32)).astype(np.float64), v) / p.sum(axis=-1, keepdims=True)
-    return o.transpose(0, 2, 1, 3).reshape(B, Tn, d)
+# (the log2-unit-q operand and its fp64 reference are shared with test_gpu_whisper_like.py)
+from tests.whisper_like import LOG2E as _LOG2E, attn_ref_log2q as _attn_ref_log2q, to_log2q as _to_log2q  # noqa: E402
 
 
 @pytest.fixture(params=["default"])
