@@ -75,6 +75,29 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+// fp64 sum over a workgroup of 256 threads in a fixed LDS tree: of one partial per thread, or of v[0 .. n) with thread t
+// taking t, t + 256, ... first.  All 256 threads call it, once per kernel; its barriers order what came before it.
+__device__ __forceinline__ double block_sum_f64(double s) {
+  __shared__ double part[256];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  return part[0];
+}
+__device__ __forceinline__ double block_sum_f64(const float* __restrict__ v, int n) {
+  double s = 0.0;
+  for (int i = threadIdx.x; i < n; i += 256) s += (double)v[i];
+  return block_sum_f64(s);
+}
+
 // exact (erf) GELU, nn.functional.gelu default
 __device__ __forceinline__ float gelu_erf(float x) {
   return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f));

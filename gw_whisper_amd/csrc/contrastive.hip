@@ -178,12 +178,6 @@ __global__ __launch_bounds__(256) void k_nce_backward(const float* __restrict__ 
 // fp64 -- in fp32 their rounding leaves an error near 1e-7 sqrt(B F T) |g p|, which exceeds 1e-5 of a sum that cancels.
 constexpr int TB_MAXW = 4096, TB_MAXT = 4096, TB_WL = TB_MAXW / 256;
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __global__ __launch_bounds__(256) void k_tail_backward(const float* __restrict__ g, long g_bstride, const float* __restrict__ y,
                                                        int Hin, int Win, int F, int Tn, const float* __restrict__ scale,
                                                        const float* __restrict__ gamma_i, float* __restrict__ dy,

@@ -1,0 +1,361 @@
+// The exact-fp32 MLP chain behind the glitch head (classify.hip) and the detection head (detect.hip): d_in -> hidden widths
+// -> C, ReLU (and optionally dropout) between the layers.  Every contraction is a v_mfma_f32_16x16x4_f32 chain (bit for
+// bit a k-ordered fmaf chain), no float atomics, every reduction in a fixed order: two identical calls give identical bits,
+// and two heads give identical bits wherever their layers agree.  One workgroup of CH_THREADS owns CH_ROWS rows and walks
+// the whole chain with the activations in two LDS buffers that take turns; the weights stream from L2.
+#pragma once
+#include <initializer_list>
+
+#include "common.h"
+
+namespace gww {
+
+constexpr int CH_ROWS = 16;                 // rows of one workgroup (one MFMA tile)
+constexpr int CH_THREADS = 512;             // 8 waves
+constexpr int CH_WAVES = CH_THREADS / 64;
+constexpr int CH_PAD = 4;                   // LDS row padding (floats): rows stay 16-byte aligned
+constexpr int CH_CMAX = 64;
+
+// A chain of L linear layers with the hidden widths H...; the last layer's width is C at run time, CH_CMAX for sizing.
+// Forward, layer i reads LDS buffer i & 1 (x is loaded into buffer 0) and writes buffer (i + 1) & 1; backward, layer i's dz
+// lives in buffer (L - 1 - i) & 1.  fwd_w / bwd_w: the widest row a buffer holds on that walk (x not counted).
+template <int... H>
+struct Chain {
+  static constexpr int L = sizeof...(H) + 1;
+  static constexpr int out(int i, int C = CH_CMAX) {
+    constexpr int h[] = {H...};
+    return i < L - 1 ? h[i] : C;
+  }
+  static constexpr int in(int i, int d_in) { return i == 0 ? d_in : out(i - 1); }
+  static constexpr int hidden_sum() { return (H + ...); }
+  static constexpr int fwd_w(int b) {
+    int w = 0;
+    for (int i = 0; i < L; ++i)
+      if (((i + 1) & 1) == b && out(i) > w) w = out(i);
+    return w;
+  }
+  static constexpr int bwd_w(int b) {
+    int w = 0;
+    for (int i = 0; i < L; ++i)
+      if (((L - 1 - i) & 1) == b && out(i) > w) w = out(i);
+    return w;
+  }
+  static constexpr size_t bwd_lds_bytes() { return (size_t)CH_ROWS * (bwd_w(0) + bwd_w(1) + 2 * CH_PAD) * sizeof(float); }
+};
+
+// torch's argmax order: a NaN is the maximum, ties go to the lowest index
+__device__ __forceinline__ bool argmax_better(float a, int ia, float b, int ib) {
+  const bool na = a != a, nb = b != b;
+  if (na != nb) return na;
+  if (!na && a != b) return a > b;
+  return ia < ib;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------
+// out[m][n] = act(sum_k in[m][k] W[n][k] + bias[n]) for the workgroup's 16 rows; in / out in LDS.  A wave owns 16-column
+// tiles; lane (c = lane & 15, q = lane >> 4) reads W[n0 + c][k + 4 q .. + 3] and in[c][k + 4 q .. + 3] as one 16-byte
+// load each and feeds four MFMAs (the k order inside a 16-block is permuted; it is the same in every call and in every
+// kernel built from this function).  DROPOUT: dr.apply(v, layer, idx4) masks and rescales the four activations of element
+// index 4 idx4 .. + 3.  save == nullptr: nothing leaves LDS.
+template <bool HIDDEN, bool DROPOUT, class Drop>
+__device__ __forceinline__ void chain_layer_fwd(const float* in, int ldi, float* out, int ldo, const float* __restrict__ W,
+                                                const float* __restrict__ bias, int K, int N, int layer, const Drop& dr,
+                                                float* __restrict__ save, long row0, int B) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+  const int ntiles = (N + 15) >> 4;
+  for (int t = wave; t < ntiles; t += CH_WAVES) {
+    const int n0 = t * 16;
+    int wr = n0 + c;
+    if (wr >= N) wr = N - 1;
+    const float* wp = W + (long)wr * K + 4 * q;
+    const float* ip = in + c * ldi + 4 * q;
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < K; k += 64) {          // K is a multiple of 64: four 16-byte loads of each operand in flight
+      float4 w[4], a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        w[u] = *reinterpret_cast<const float4*>(wp + k + 16 * u);
+        a[u] = *reinterpret_cast<const float4*>(ip + k + 16 * u);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u].x, a[u].x, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u].y, a[u].y, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u].z, a[u].z, acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_16x16x4f32(w[u].w, a[u].w, acc, 0, 0, 0);
+      }
+    }
+    // acc[r] = out[m = c][n = n0 + 4 q + r]
+    const int n = n0 + 4 * q;
+    const long row = row0 + c;
+    if (HIDDEN) {
+      const float4 bv = *reinterpret_cast<const float4*>(bias + n);
+      float v[4] = {fmaxf(acc[0] + bv.x, 0.f), fmaxf(acc[1] + bv.y, 0.f), fmaxf(acc[2] + bv.z, 0.f),
+                    fmaxf(acc[3] + bv.w, 0.f)};
+      if constexpr (DROPOUT) dr.apply(v, layer, (unsigned)((row * N + n) >> 2));
+      const float4 o = {v[0], v[1], v[2], v[3]};
+      *reinterpret_cast<float4*>(out + c * ldo + n) = o;
+      if (save && row < B) *reinterpret_cast<float4*>(save + row * N + n) = o;
+    } else {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (n + r < N) {
+          const float v = acc[r] + bias[n + r];
+          out[c * ldo + n + r] = v;
+          if (save && row < B) save[row * N + n + r] = v;
+        }
+    }
+  }
+}
+
+template <int L>
+struct ChainFwdArgs {
+  const float* W[L];
+  const float* b[L];
+  float* save[L];     // h1 .. h(L-1), logits
+};
+struct NoDrop {};
+struct ChainRows {    // the workgroup's 16 rows of something in LDS
+  const float* p;
+  int ld;
+};
+
+// x -> ... -> logits for the workgroup's rows; sm: chain_lds_bytes(d_in) of LDS.  Returns the logits' place in LDS, behind a
+// barrier.  SAVE: every layer's output also goes to P.save.
+template <class CH, bool SAVE, bool DROPOUT, class Drop>
+__device__ __forceinline__ ChainRows chain_fwd(float* sm, const float* __restrict__ x, const ChainFwdArgs<CH::L>& P, int B,
+                                               int d_in, int C, const Drop& dr) {
+  const int ld[2] = {(d_in > CH::fwd_w(0) ? d_in : CH::fwd_w(0)) + CH_PAD, CH::fwd_w(1) + CH_PAD};
+  float* const buf[2] = {sm, sm + CH_ROWS * ld[0]};
+  const long row0 = (long)blockIdx.x * CH_ROWS;
+  const int d4 = d_in >> 2;
+  for (int i = threadIdx.x; i < CH_ROWS * d4; i += CH_THREADS) {
+    const int m = i / d4, k = (i - m * d4) * 4;
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (row0 + m < B) v = *reinterpret_cast<const float4*>(x + (row0 + m) * d_in + k);
+    *reinterpret_cast<float4*>(buf[0] + m * ld[0] + k) = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 0; i < CH::L - 1; ++i) {
+    chain_layer_fwd<true, DROPOUT>(buf[i & 1], ld[i & 1], buf[(i + 1) & 1], ld[(i + 1) & 1], P.W[i], P.b[i], CH::in(i, d_in),
+                                   CH::out(i), i, dr, SAVE ? P.save[i] : nullptr, row0, B);
+    __syncthreads();
+  }
+  constexpr int l = CH::L - 1;
+  chain_layer_fwd<false, false>(buf[l & 1], ld[l & 1], buf[CH::L & 1], ld[CH::L & 1], P.W[l], P.b[l], CH::in(l, d_in), C, l, dr,
+                                SAVE ? P.save[l] : nullptr, row0, B);
+  __syncthreads();
+  return ChainRows{buf[CH::L & 1], ld[CH::L & 1]};
+}
+
+// ---- backward, input side -------------------------------------------------------------------------------------------
+// out[m][k] = sum_n dz[m][n] W[n][k] for the workgroup's 16 rows (dz in LDS, its columns zero-padded to a multiple of 16).
+// A wave owns 64-column strips: lane (c, q) reads W[n + q][k0 + 4 c .. + 3] as one 16-byte load (a 256-byte run per row)
+// and feeds four MFMAs whose outputs are the four columns k0 + 4 c + j.  acc[j][r] = out[m = 4 q + r][k0 + 4 c + j].
+// MASK: keep the lanes whose saved activation is positive (the ReLU was open and, after dropout, the unit kept; SCALED:
+// times `scale` = 1 / (1 - p)), write the layer's dz to LDS + workspace.
+template <bool MASK, bool SCALED>
+__device__ __forceinline__ void chain_layer_bwd(const float* dz, int ldz, float* out, int ldo, const float* __restrict__ W,
+                                                int N, int K, const float* __restrict__ hsave, float scale,
+                                                float* __restrict__ gout, long row0, int B) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+  const int strips = K >> 6;
+  for (int t = wave; t < strips; t += CH_WAVES) {
+    const int k0 = t * 64 + 4 * c;
+    f32x4 acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int n = 0; n < N; n += 16) {          // dz columns are zero-padded to a multiple of 16 in LDS
+      float a[4];
+      float4 w[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int nn = n + 4 * u + q;
+        a[u] = dz[c * ldz + nn];
+        w[u] = *reinterpret_cast<const float4*>(W + (long)(nn < N ? nn : N - 1) * K + k0);
+        if (nn >= N) w[u] = float4{0.f, 0.f, 0.f, 0.f};
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u].x, acc[0], 0, 0, 0);
+        acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u].y, acc[1], 0, 0, 0);
+        acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u].z, acc[2], 0, 0, 0);
+        acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], w[u].w, acc[3], 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int m = 4 * q + r;
+      const long row = row0 + m;
+      float4 v = {acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+      if (MASK) {
+        float4 h = {0.f, 0.f, 0.f, 0.f};
+        if (row < B) h = *reinterpret_cast<const float4*>(hsave + row * K + k0);
+        const float s = SCALED ? scale : 1.f;   // x * 1.f folds away: the unscaled form is a plain select
+        v.x = h.x > 0.f ? v.x * s : 0.f;
+        v.y = h.y > 0.f ? v.y * s : 0.f;
+        v.z = h.z > 0.f ? v.z * s : 0.f;
+        v.w = h.w > 0.f ? v.w * s : 0.f;
+        *reinterpret_cast<float4*>(out + m * ldo + k0) = v;
+      }
+      if (row < B) *reinterpret_cast<float4*>(gout + row * K + k0) = v;
+    }
+  }
+}
+
+template <int L>
+struct ChainBwdArgs {
+  const float* W[L];
+  const float* h[L - 1];
+  float* dz[L];       // the workspace (chain_carve)
+  float* dx;
+};
+
+// dz_L (times the device scalar gscale, if given) -> ... -> dx for the workgroup's rows, every layer's dz left in A.dz
+template <class CH, bool SCALED>
+__device__ __forceinline__ void chain_bwd(const float* __restrict__ dz_in, const float* __restrict__ gscale,
+                                          const ChainBwdArgs<CH::L>& A, int B, int d_in, int C, float scale) {
+  constexpr int L = CH::L, ld[2] = {CH::bwd_w(0) + CH_PAD, CH::bwd_w(1) + CH_PAD};
+  __shared__ __attribute__((aligned(16))) float buf0[CH_ROWS * ld[0]];
+  __shared__ __attribute__((aligned(16))) float buf1[CH_ROWS * ld[1]];
+  float* const buf[2] = {buf0, buf1};
+  const long row0 = (long)blockIdx.x * CH_ROWS;
+  const float g = gscale ? gscale[0] : 1.f;
+  const int C16 = (C + 15) & ~15;
+  for (int i = threadIdx.x; i < CH_ROWS * C16; i += CH_THREADS) {
+    const int m = i / C16, n = i - m * C16;
+    float v = 0.f;
+    if (row0 + m < B && n < C) {
+      v = g * dz_in[(row0 + m) * C + n];
+      A.dz[L - 1][(row0 + m) * C + n] = v;
+    }
+    buf0[m * ld[0] + n] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = L - 1; i > 0; --i) {
+    const int s = (L - 1 - i) & 1;
+    chain_layer_bwd<true, SCALED>(buf[s], ld[s], buf[s ^ 1], ld[s ^ 1], A.W[i], CH::out(i, C), CH::out(i - 1), A.h[i - 1], scale,
+                                  A.dz[i - 1], row0, B);
+    __syncthreads();
+  }
+  constexpr int s = (L - 1) & 1;
+  chain_layer_bwd<false, false>(buf[s], ld[s], nullptr, 0, A.W[0], CH::out(0), d_in, nullptr, 1.f, A.dx, row0, B);
+}
+
+// ---- backward, weight side ------------------------------------------------------------------------------------------
+struct ChainWgradLayer {
+  const float* dz;    // [B, N]
+  const float* h;     // [B, K]   the layer's input
+  float* dW;          // [N, K]
+  float* db;          // [N]
+  int N, K, tiles_k, first;   // first workgroup of the layer
+};
+template <int L>
+struct ChainWgradArgs {
+  ChainWgradLayer l[L];
+};
+
+// ONE launch of 256 threads for all the layers.  dW[n][k] = sum_b dz[b][n] h[b][k]: 64 x 64 tile per workgroup, wave w rows
+// n0 + 16 w .. + 15.  Lane (c, q) reads dz[b + q][n0 + 16 w + c] and h[b + q][k0 + 4 c .. + 3]; acc[j][r] =
+// dW[n0 + 16 w + 4 q + r][k0 + 4 c + j].  The k-tile 0 workgroups also run the same dz operand against ones: every column
+// of that accumulator is the bias gradient.
+template <int L>
+__device__ __forceinline__ void chain_bwd_w(const ChainWgradArgs<L>& A, int B) {
+  int li = 0;
+#pragma unroll
+  for (int i = 1; i < L; ++i)
+    if ((int)blockIdx.x >= A.l[i].first) li = i;
+  const ChainWgradLayer Y = A.l[li];
+  const int tile = blockIdx.x - Y.first;
+  const int tn = tile / Y.tiles_k, tk = tile - tn * Y.tiles_k;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+  const int nb = tn * 64 + wave * 16;
+  if (nb >= Y.N) return;                     // uniform per wave; no barrier below
+  const int na = nb + c;
+  const bool nok = na < Y.N;
+  const int k0 = tk * 64 + 4 * c;
+  const float* dzp = Y.dz + (nok ? na : Y.N - 1);
+  const float* hp = Y.h + k0;
+  f32x4 acc[4], accb = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const bool do_bias = tk == 0;
+  for (int b = 0; b < B; b += 16) {
+    float a[4], one[4];
+    float4 h[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int bb = b + 4 * u + q;
+      const bool ok = bb < B;
+      const long br = ok ? bb : B - 1;
+      a[u] = dzp[br * Y.N];
+      h[u] = *reinterpret_cast<const float4*>(hp + br * Y.K);
+      if (!ok || !nok) a[u] = 0.f;
+      if (!ok) h[u] = float4{0.f, 0.f, 0.f, 0.f};
+      one[u] = ok ? 1.f : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], h[u].x, acc[0], 0, 0, 0);
+      acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], h[u].y, acc[1], 0, 0, 0);
+      acc[2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], h[u].z, acc[2], 0, 0, 0);
+      acc[3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], h[u].w, acc[3], 0, 0, 0);
+      if (do_bias) accb = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u], one[u], accb, 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int n = nb + 4 * q + r;
+    if (n < Y.N) {
+      *reinterpret_cast<float4*>(Y.dW + (long)n * Y.K + k0) = float4{acc[0][r], acc[1][r], acc[2][r], acc[3][r]};
+      if (do_bias && c == 0) Y.db[n] = accb[r];
+    }
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------------------------------
+static int chain_check_shape(const char* who, int B, int Bmax, int d_in, int C, int Cmin) {
+  GWW_REQUIRE(B >= 1 && B <= Bmax, "%s: B=%d must be 1..%d", who, B, Bmax);
+  GWW_REQUIRE(d_in >= 128 && d_in <= 1280 && d_in % 128 == 0, "%s: d_in=%d must be a multiple of 128 in 128..1280", who, d_in);
+  GWW_REQUIRE(C >= Cmin && C <= CH_CMAX, "%s: C=%d must be %d..%d", who, C, Cmin, CH_CMAX);
+  return GWW_OK;
+}
+static bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps)
+    if (((uintptr_t)p) & 15) return false;
+  return true;
+}
+// dynamic LDS of the forward walk
+template <class CH>
+static size_t chain_lds_bytes(int d_in) {
+  return (size_t)CH_ROWS * ((d_in > CH::fwd_w(0) ? d_in : CH::fwd_w(0)) + CH::fwd_w(1) + 2 * CH_PAD) * sizeof(float);
+}
+// workspace of the backward: dz1 [B, out(0)] | dz2 [B, out(1)] | ... | dzL [B, C]
+template <class CH>
+static size_t chain_workspace_bytes(int B, int C) {
+  if (B < 1 || C < 1) return 0;
+  return (size_t)B * (CH::hidden_sum() + C) * sizeof(float);
+}
+template <class CH>
+static void chain_carve(float* ws, int B, float* (&dz)[CH::L]) {
+  for (int i = 0; i < CH::L; ++i) {
+    dz[i] = ws;
+    ws += (size_t)B * CH::out(i);
+  }
+}
+// the weight-gradient table of one step (h[0] = x); returns the grid size
+template <class CH>
+static int chain_wgrad_table(ChainWgradArgs<CH::L>& T, const float* x, const ChainBwdArgs<CH::L>& A, float* const (&dW)[CH::L],
+                             float* const (&db)[CH::L], int d_in, int C) {
+  int first = 0;
+  for (int i = 0; i < CH::L; ++i) {
+    const int N = CH::out(i, C), K = CH::in(i, d_in);
+    T.l[i] = ChainWgradLayer{A.dz[i], i ? A.h[i - 1] : x, dW[i], db[i], N, K, K / 64, first};
+    first += (int)cdiv(N, 64) * (K / 64);
+  }
+  return first;
+}
+
+}  // namespace gww

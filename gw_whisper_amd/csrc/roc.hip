@@ -390,7 +390,6 @@ __global__ __launch_bounds__(256) void k_bin_eval(const float* __restrict__ logi
                                                   float* __restrict__ scores, double* __restrict__ loss_sum,
                                                   long long* __restrict__ batches, long long* __restrict__ confusion) {
   __shared__ int cm[4];
-  __shared__ double part[256];
   const int tid = threadIdx.x;
   if (tid < 4) cm[tid] = 0;
   __syncthreads();
@@ -403,14 +402,9 @@ __global__ __launch_bounds__(256) void k_bin_eval(const float* __restrict__ logi
     const int pred = rintf(p) > 0.5f ? 1 : 0;           // torch.round: half to even, a probability of exactly 0.5 is class 0
     atomicAdd(&cm[(labels[i] > 0.5f ? 2 : 0) + pred], 1);
   }
-  part[tid] = s;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if (tid < o) part[tid] += part[tid + o];
-    __syncthreads();
-  }
+  s = block_sum_f64(s);                      // its barriers also order cm
   if (tid == 0) {
-    loss_sum[0] += (double)(float)(part[0] / (double)B);
+    loss_sum[0] += (double)(float)(s / (double)B);
     batches[0] += 1;
   }
   if (tid < 4) confusion[tid] += cm[tid];

@@ -187,15 +187,9 @@ def synthetic_tensors(n_wave: int, n_noise: int, seed: int, n_samples: int = 160
 # =============================================================================================== the HIP head step
 def _det_parameters(classifier):
     """The ten ``nn.Linear`` tensors of ``efficiency_classifier.classifier`` (slots 0 2 4 6 8)."""
-    try:
-        lin = [classifier[i] for i in (0, 2, 4, 6, 8)]
-        params = []
-        for l in lin:
-            params += [l.weight, l.bias]
-    except (IndexError, AttributeError, TypeError) as e:
-        raise _lib.GwwError("the detection head needs the nn.Sequential of models.efficiency_classifier "
-                            "(Linear ReLU x 4, Linear, Softmax)") from e
-    return params
+    from .models import linear_params
+    return linear_params(classifier, (0, 2, 4, 6, 8), "the detection head needs the nn.Sequential of "
+                         "models.efficiency_classifier (Linear ReLU x 4, Linear, Softmax)")
 
 
 class _RegBCE(torch.autograd.Function):

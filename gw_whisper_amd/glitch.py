@@ -56,18 +56,16 @@ def encode_labels(raw_labels: Sequence[str], classes: Sequence[str]) -> np.ndarr
 
 
 # =============================================================================================== the HIP head step
+_NEEDS = "head_cross_entropy needs the nn.Sequential of models.glitch_classifier (Linear ReLU Dropout x 3, Linear)"
+
+
 def _head_parameters(classifier):
     """The eight ``nn.Linear`` tensors and the dropout probability of ``glitch_classifier.classifier`` (slots 0 3 6 9)."""
-    try:
-        lin = [classifier[i] for i in (0, 3, 6, 9)]
-        p = float(classifier[2].p)
-    except (IndexError, AttributeError, TypeError) as e:
-        raise _lib.GwwError("head_cross_entropy needs the nn.Sequential of models.glitch_classifier "
-                            "(Linear ReLU Dropout x 3, Linear)") from e
-    params = []
-    for l in lin:
-        params += [l.weight, l.bias]
-    return params, p
+    from .models import linear_params
+    params = linear_params(classifier, (0, 3, 6, 9), _NEEDS)
+    if not isinstance(classifier[2], torch.nn.Dropout):
+        raise _lib.GwwError(_NEEDS)
+    return params, float(classifier[2].p)
 
 
 class _HeadCE(torch.autograd.Function):

@@ -21,12 +21,23 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
+from ._lib import GwwError
+
 
 def _pooled(encoder, mel):
     fast = getattr(encoder, "last_token", None)
     if fast is not None:
         return fast(mel)
     return encoder(mel).last_hidden_state[:, -1, :]
+
+
+def linear_params(classifier, slots, needs):
+    """[weight, bias, weight, bias, ...] of the ``nn.Linear`` modules in ``slots`` of a head's ``nn.Sequential``; a
+    classifier of another layout is a ``GwwError`` with the text ``needs``."""
+    try:
+        return [t for i in slots for t in (classifier[i].weight, classifier[i].bias)]
+    except (IndexError, AttributeError, TypeError) as e:
+        raise GwwError(needs) from e
 
 
 class two_channel_ligo_binary_classifier(nn.Module):

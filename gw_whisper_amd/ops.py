@@ -845,19 +845,45 @@ def assemble_batch(noise, wave, idx_noise, idx_wave, snr):
 
 
 HEAD_WIDTHS = (512, 256, 128)      # hidden widths of models.glitch_classifier's head (Glitch_classification/src/model.py)
+DET_WIDTHS = (512, 256, 128, 64)   # hidden widths of models.efficiency_classifier's head (Efficiency_test/src/network.py:73-85)
 
 
-def _head_params(params):
-    if len(params) != 8:
-        raise _lib.GwwError("head: expected (w1, b1, w2, b2, w3, b3, w4, b4)")
+def _mlp_params(params, widths, who, chain):
+    """The ``nn.Linear`` tensors (w1, b1, ...) of the chain d_in -> widths -> C, checked: (fp32 GPU tensors, d_in, C)."""
+    n = len(widths) + 1
+    if len(params) != 2 * n:
+        raise _lib.GwwError(f"{who}: expected ({', '.join(f'w{i}, b{i}' for i in range(1, n + 1))})")
     ps = [_dev(p, torch.float32, "head parameter") for p in params]
-    d_in, C = ps[0].shape[1], ps[6].shape[0]
-    shapes = [(512, d_in), (512,), (256, 512), (256,), (128, 256), (128,), (C, 128), (C,)]
-    for p, s in zip(ps, shapes):
+    d_in, C = ps[0].shape[1], ps[-2].shape[0]
+    dims = (d_in, *widths, C)
+    for i, p in enumerate(ps):
+        s = (dims[i // 2 + 1], dims[i // 2]) if i % 2 == 0 else (dims[i // 2 + 1],)
         if tuple(p.shape) != s:
-            raise _lib.GwwError(f"head: parameter of shape {tuple(p.shape)} where the glitch head d_in -> 512 -> 256 -> 128 "
-                                f"-> C has {s}")
+            raise _lib.GwwError(f"{who}: parameter of shape {tuple(p.shape)} where the {chain} d_in -> "
+                                f"{' -> '.join(map(str, widths))} -> C has {s}")
     return ps, d_in, C
+
+
+def _mlp_outputs(x, widths, C, n_bc):
+    """What a head's forward fills: the saved activations, ``n_bc`` [B, C] tensors, row_loss [B], loss [1]."""
+    def new(*shape):
+        return torch.empty(shape, dtype=torch.float32, device=x.device)
+    B = x.shape[0]
+    return [new(B, w) for w in widths], [new(B, C) for _ in range(n_bc)], new(B), new(1)
+
+
+def _mlp_grads(x, ps, dloss, ws, ws_bytes):
+    """What a head's backward takes and fills: dloss' pointer (or None), the fp32 workspace, dx, the parameter gradients."""
+    if dloss is not None:
+        dloss = _dev(dloss.reshape(1), torch.float32, "dloss").data_ptr()
+    if ws is None:
+        ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=x.device)
+    return dloss, _dev(ws, torch.float32, "ws"), torch.empty_like(x), [torch.empty_like(t) for t in ps]
+
+
+def _state(t, dt, shape, who, name):
+    if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+        raise _lib.GwwError(f"{who}: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
 
 
 def head_forward(x, params, labels, p: float = 0.3, train: bool = False, seed: int = 0, offset: int = 0):
@@ -866,22 +892,17 @@ def head_forward(x, params, labels, p: float = 0.3, train: bool = False, seed: i
     scalar, logits [B, C], row_loss [B], pred [B] int64, saved) with ``saved`` what ``head_backward`` needs."""
     x = _dev(x, torch.float32, "x")
     labels = _dev(labels, torch.int64, "labels")
-    ps, d_in, C = _head_params(params)
+    ps, d_in, C = _mlp_params(params, HEAD_WIDTHS, "head", "glitch head")
     if x.dim() != 2 or x.shape[1] != d_in or labels.shape != (x.shape[0],):
         raise _lib.GwwError(f"head_forward: x {tuple(x.shape)} / labels {tuple(labels.shape)} do not fit d_in = {d_in}")
     B, dev = x.shape[0], x.device
-    h = [torch.empty((B, w), dtype=torch.float32, device=dev) for w in HEAD_WIDTHS]
-    logits = torch.empty((B, C), dtype=torch.float32, device=dev)
-    dz = torch.empty((B, C), dtype=torch.float32, device=dev)
-    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    h, (logits, dz), row_loss, loss = _mlp_outputs(x, HEAD_WIDTHS, C, 2)
     pred = torch.empty((B,), dtype=torch.int64, device=dev)
-    loss = torch.empty((1,), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         check(lib().gww_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], labels.data_ptr(), B, d_in, C, float(p),
                                          int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                         h[0].data_ptr(), h[1].data_ptr(), h[2].data_ptr(), logits.data_ptr(),
-                                         row_loss.data_ptr(), pred.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
-              "gww_head_forward_f32")
+                                         *[t.data_ptr() for t in h], logits.data_ptr(), row_loss.data_ptr(),
+                                         pred.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()), "gww_head_forward_f32")
     return loss, logits, row_loss, pred, (x, ps, h, dz, float(p), bool(train))
 
 
@@ -890,17 +911,11 @@ def head_backward(saved, dloss=None):
     (``gww_head_backward_f32``, 2 launches; no host sync)."""
     x, ps, h, dz, p, train = saved
     B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
-    if dloss is not None:
-        dloss = _dev(dloss.reshape(1), torch.float32, "dloss")
-    ws = torch.empty((lib().gww_head_workspace_bytes(B, C) // 4,), dtype=torch.float32, device=dev)
-    dx = torch.empty_like(x)
-    grads = [torch.empty_like(t) for t in ps]
+    dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, None, lib().gww_head_workspace_bytes(B, C))
     with torch.cuda.device(dev):
-        check(lib().gww_head_backward_f32(x.data_ptr(), ps[0].data_ptr(), ps[2].data_ptr(), ps[4].data_ptr(),
-                                          ps[6].data_ptr(), h[0].data_ptr(), h[1].data_ptr(), h[2].data_ptr(), dz.data_ptr(),
-                                          None if dloss is None else dloss.data_ptr(), B, d_in, C, p, int(train),
-                                          ws.data_ptr(), dx.data_ptr(), *[g.data_ptr() for g in grads], _stream()),
-              "gww_head_backward_f32")
+        check(lib().gww_head_backward_f32(x.data_ptr(), *[t.data_ptr() for t in ps[0::2]], *[t.data_ptr() for t in h],
+                                          dz.data_ptr(), dloss, B, d_in, C, p, int(train), ws.data_ptr(), dx.data_ptr(),
+                                          *[g.data_ptr() for g in grads], _stream()), "gww_head_backward_f32")
     return dx, grads
 
 
@@ -926,8 +941,7 @@ def eval_accumulate(logits, labels, row_loss, confusion, loss_sum, n):
     B, C = logits.shape
     for t, dt, shape, name in ((confusion, torch.int64, (C, C), "confusion"), (loss_sum, torch.float64, (1,), "loss_sum"),
                                (n, torch.int64, (1,), "n")):
-        if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise _lib.GwwError(f"eval_accumulate: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
+        _state(t, dt, shape, "eval_accumulate", name)
     if labels.shape != (B,) or row_loss.shape != (B,):
         raise _lib.GwwError("eval_accumulate: labels and row_loss must be [B]")
     with torch.cuda.device(logits.device):
@@ -936,22 +950,8 @@ def eval_accumulate(logits, labels, row_loss, confusion, loss_sum, n):
               "gww_eval_accumulate")
 
 
-DET_WIDTHS = (512, 256, 128, 64)   # hidden widths of models.efficiency_classifier's head (Efficiency_test/src/network.py:73-85)
 SCORE_PROB0, SCORE_LOGIT_DIFF = 0, 1
 MAX_FAPS = 8
-
-
-def _det_params(params):
-    if len(params) != 10:
-        raise _lib.GwwError("det_head: expected (w1, b1, w2, b2, w3, b3, w4, b4, w5, b5)")
-    ps = [_dev(p, torch.float32, "head parameter") for p in params]
-    d_in, C = ps[0].shape[1], ps[8].shape[0]
-    shapes = [(512, d_in), (512,), (256, 512), (256,), (128, 256), (128,), (64, 128), (64,), (C, 64), (C,)]
-    for p, s in zip(ps, shapes):
-        if tuple(p.shape) != s:
-            raise _lib.GwwError(f"det_head: parameter of shape {tuple(p.shape)} where the detection head d_in -> 512 -> 256 "
-                                f"-> 128 -> 64 -> C has {s}")
-    return ps, d_in, C
 
 
 def det_head_forward(x, params, targets, epsilon: float = 1e-6):
@@ -961,19 +961,15 @@ def det_head_forward(x, params, targets, epsilon: float = 1e-6):
     ``det_head_backward`` needs."""
     x = _dev(x, torch.float32, "x")
     targets = _dev(targets, torch.float32, "targets")
-    ps, d_in, C = _det_params(params)
+    ps, d_in, C = _mlp_params(params, DET_WIDTHS, "det_head", "detection head")
     if x.dim() != 2 or x.shape[1] != d_in or tuple(targets.shape) != (x.shape[0], C):
         raise _lib.GwwError(f"det_head_forward: x {tuple(x.shape)} / targets {tuple(targets.shape)} do not fit d_in = {d_in}, "
                             f"C = {C}")
-    B, dev = x.shape[0], x.device
-    h = [torch.empty((B, w), dtype=torch.float32, device=dev) for w in DET_WIDTHS]
-    logits, probs, dz = (torch.empty((B, C), dtype=torch.float32, device=dev) for _ in range(3))
-    row_loss = torch.empty((B,), dtype=torch.float32, device=dev)
-    loss = torch.empty((1,), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().gww_det_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], targets.data_ptr(), B, d_in, C,
-                                             float(epsilon), *[t.data_ptr() for t in h], logits.data_ptr(), probs.data_ptr(),
-                                             row_loss.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
+    h, (logits, probs, dz), row_loss, loss = _mlp_outputs(x, DET_WIDTHS, C, 3)
+    with torch.cuda.device(x.device):
+        check(lib().gww_det_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], targets.data_ptr(), x.shape[0], d_in,
+                                             C, float(epsilon), *[t.data_ptr() for t in h], logits.data_ptr(),
+                                             probs.data_ptr(), row_loss.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
               "gww_det_head_forward_f32")
     return loss, logits, probs, row_loss, (x, ps, h, dz)
 
@@ -984,19 +980,11 @@ def det_head_backward(saved, dloss=None, ws=None):
     ``gww_det_head_workspace_bytes(B, C)`` bytes (allocated here when None)."""
     x, ps, h, dz = saved
     B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
-    if dloss is not None:
-        dloss = _dev(dloss.reshape(1), torch.float32, "dloss")
-    if ws is None:
-        ws = torch.empty((lib().gww_det_head_workspace_bytes(B, C) // 4,), dtype=torch.float32, device=dev)
-    ws = _dev(ws, torch.float32, "ws")
-    dx = torch.empty_like(x)
-    grads = [torch.empty_like(t) for t in ps]
+    dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, ws, lib().gww_det_head_workspace_bytes(B, C))
     with torch.cuda.device(dev):
-        check(lib().gww_det_head_backward_f32(x.data_ptr(), *[ps[i].data_ptr() for i in (0, 2, 4, 6, 8)],
-                                              *[t.data_ptr() for t in h], dz.data_ptr(),
-                                              None if dloss is None else dloss.data_ptr(), B, d_in, C, ws.data_ptr(),
-                                              ws.numel() * 4, dx.data_ptr(), *[g.data_ptr() for g in grads], _stream()),
-              "gww_det_head_backward_f32")
+        check(lib().gww_det_head_backward_f32(x.data_ptr(), *[t.data_ptr() for t in ps[0::2]], *[t.data_ptr() for t in h],
+                                              dz.data_ptr(), dloss, B, d_in, C, ws.data_ptr(), ws.numel() * 4, dx.data_ptr(),
+                                              *[g.data_ptr() for g in grads], _stream()), "gww_det_head_backward_f32")
     return dx, grads
 
 
@@ -1005,7 +993,7 @@ def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
     (mode SCORE_PROB0) or ``z0 - z1`` (SCORE_LOGIT_DIFF, C = 2).  ``out``: a 1-d fp32 GPU view of B elements, of any
     stride -- a slice of the score buffer of a whole pass."""
     x = _dev(x, torch.float32, "x")
-    ps, d_in, C = _det_params(params)
+    ps, d_in, C = _mlp_params(params, DET_WIDTHS, "det_head", "detection head")
     B = x.shape[0]
     if x.dim() != 2 or x.shape[1] != d_in:
         raise _lib.GwwError(f"det_head_scores: x {tuple(x.shape)} does not fit d_in = {d_in}")
@@ -1015,11 +1003,6 @@ def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
         check(lib().gww_det_head_scores_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d_in, C, int(mode), out.data_ptr(),
                                             max(out.stride(0), 1), _stream()), "gww_det_head_scores_f32")
     return out
-
-
-def _state(t, dt, shape, who, name):
-    if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-        raise _lib.GwwError(f"{who}: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
 
 
 def det_eval_accumulate(probs, targets, row_loss, correct, loss_sum, n, batches):
