@@ -7,6 +7,8 @@
 //   k_column_median  per-frequency MEDIAN over the Welch segments (numpy.median: mean of the two middle values for an
 //                    even count) by a 4-pass, 8-bit radix select on the float bit patterns (power >= 0: uint order ==
 //                    float order); one workgroup per frequency bin, no sort, no scratch        (L2-resident re-reads)
+//   k_fir_f64        the filter as whiten.py applies it: fp64 samples, taps and sums (detector strain keeps its in-band
+//                    content at 1e-5 of the sample peak), fp32 out; the shape of k_fir_f32 below
 //   k_fir_f32        the whitening filter applied in the TIME domain: inverse-spectrum truncation makes it a short
 //                    FIR (the reference's max_filter_duration = 0.25 s = 512 taps at 2048 Hz, plus the tail the
 //                    |.| of its spectrum adds), so  white[n] = sum_u g[u] x[n + u]  streams the strain once through
@@ -102,6 +104,46 @@ __global__ __launch_bounds__(256) void k_fir_f32(const float* __restrict__ xp, l
     if (base + 2 < avail) od[base + 2] = a2;
   }
 }
+
+// The same correlation with fp64 samples, fp64 taps and fp64 accumulators, rounded to fp32 only on the way out: detector
+// strain holds its in-band content at about 1e-5 of the sample peak under a low-frequency wall the filter removes by
+// cancellation, which fp32 samples (2^-24 of the peak each) or fp32 sums do not survive.  Same streaming shape: FIR_BLK
+// outputs per workgroup, 4 per thread, 16-byte LDS reads (two doubles).
+__global__ __launch_bounds__(256) void k_fir_f64(const double* __restrict__ xp, long xp_stride, const double* __restrict__ g,
+                                                 int taps4, float* __restrict__ out, long out_stride, long n_out) {
+  extern __shared__ __attribute__((aligned(16))) double smd[];
+  double* xs = smd;                         // FIR_BLK + taps4 samples
+  double* gs = smd + FIR_BLK + taps4;       // taps4 coefficients
+  const int d = blockIdx.y, tid = threadIdx.x;
+  const long n0 = (long)blockIdx.x * FIR_BLK;
+  const double* xd = xp + (long)d * xp_stride + n0;
+  const long avail = n_out - n0 < FIR_BLK ? n_out - n0 : FIR_BLK;       // outputs of this block
+  for (int i = tid; i < FIR_BLK + taps4; i += 256) xs[i] = i < avail + taps4 ? xd[i] : 0.0;   // xp holds n_out + taps4 samples
+  for (int i = tid; i < taps4; i += 256) gs[i] = g[(long)d * taps4 + i];
+  __syncthreads();
+  const int base = 4 * tid;
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  double2 wl = *reinterpret_cast<const double2*>(xs + base);       // window xs[base + u .. base + u + 3]
+  double2 wh = *reinterpret_cast<const double2*>(xs + base + 2);
+  for (int u = 0; u < taps4; u += 4) {
+    const double2 cl = *reinterpret_cast<const double2*>(gs + u), ch = *reinterpret_cast<const double2*>(gs + u + 2);
+    const double2 nl = *reinterpret_cast<const double2*>(xs + base + u + 4);
+    const double2 nh = *reinterpret_cast<const double2*>(xs + base + u + 6);     // <= xs[FIR_BLK + taps4 - 1]
+    a0 = fma(cl.x, wl.x, a0); a1 = fma(cl.x, wl.y, a1); a2 = fma(cl.x, wh.x, a2); a3 = fma(cl.x, wh.y, a3);
+    a0 = fma(cl.y, wl.y, a0); a1 = fma(cl.y, wh.x, a1); a2 = fma(cl.y, wh.y, a2); a3 = fma(cl.y, nl.x, a3);
+    a0 = fma(ch.x, wh.x, a0); a1 = fma(ch.x, wh.y, a1); a2 = fma(ch.x, nl.x, a2); a3 = fma(ch.x, nl.y, a3);
+    a0 = fma(ch.y, wh.y, a0); a1 = fma(ch.y, nl.x, a1); a2 = fma(ch.y, nl.y, a2); a3 = fma(ch.y, nh.x, a3);
+    wl = nl;
+    wh = nh;
+  }
+  float* od = out + (long)d * out_stride + n0;
+  if (base + 3 < avail) *reinterpret_cast<float4*>(od + base) = make_float4((float)a0, (float)a1, (float)a2, (float)a3);
+  else {
+    if (base < avail) od[base] = (float)a0;
+    if (base + 1 < avail) od[base + 1] = (float)a1;
+    if (base + 2 < avail) od[base + 2] = (float)a2;
+  }
+}
 }  // namespace
 }  // namespace gww
 
@@ -139,6 +181,24 @@ extern "C" int gww_fir_f32(const float* xp, long xp_stride, const float* g, int 
   const size_t lds = (size_t)(FIR_BLK + 2 * taps4) * sizeof(float);
   GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fir_f32), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_fir_f32, dim3((unsigned)cdiv(n_out, (long)FIR_BLK), (unsigned)D), dim3(256), lds, (hipStream_t)stream, xp,
+                     xp_stride, g, taps4, out, out_stride, n_out);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// gww_fir_f32 at fp64: xp fp64 [D, xp_stride] with at least n_out + taps4 valid samples per row; g fp64 [D, taps4] (taps4 % 4 ==
+// 0, zero padded, <= 8192: samples and taps of one block stay in LDS); out fp32 [D, out_stride], out[d][n] = the fp64 sum
+// sum_u g[d][u] xp[d][n + u] rounded once, for n < n_out.  16-byte aligned rows (xp_stride even, out_stride % 4 == 0).
+extern "C" int gww_fir_f64(const double* xp, long xp_stride, const double* g, int taps4, int D, float* out, long out_stride,
+                           long n_out, void* stream) {
+  GWW_REQUIRE(xp && g && out && D > 0 && D <= 65535 && taps4 > 0 && taps4 % 4 == 0 && taps4 <= 8192 && n_out >= 0,
+              "gww_fir_f64: bad argument (taps4=%d D=%d)", taps4, D);
+  GWW_REQUIRE(xp_stride % 2 == 0 && out_stride % 4 == 0 && ((((uintptr_t)xp) | ((uintptr_t)out) | ((uintptr_t)g)) & 15) == 0,
+              "gww_fir_f64: rows must be 16-byte aligned");
+  if (n_out == 0) return GWW_OK;
+  const size_t lds = (size_t)(FIR_BLK + 2 * taps4) * sizeof(double);
+  GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_fir_f64), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(k_fir_f64, dim3((unsigned)cdiv(n_out, (long)FIR_BLK), (unsigned)D), dim3(256), lds, (hipStream_t)stream, xp,
                      xp_stride, g, taps4, out, out_stride, n_out);
   GWW_LAUNCH_CHECK();
   return GWW_OK;

@@ -10,19 +10,28 @@ vector for this step; the arithmetic follows ``oracle/whiten.py`` (the restateme
 
 Device work:
 
-* Welch spectra: the half-overlapping segments times the hann-windowed real-DFT matrix -- one fp32-MFMA GEMM
-  (``gww_gemm_f32``) -- then ``gww_welch_power_f32`` and the per-frequency median by radix select
-  (``gww_column_median_f32``).  Whitening is invariant under a rescaling of the input, so the strain is first brought
-  to unit scale by a power of two (raw 1e-21 strain squares to 1e-42, below fp32).
+* The strain stays fp64 up to the filter's output.  Detector strain is steep: its in-band content lies at about 1e-5 of
+  the sample peak, under a low-frequency wall 1e6 higher in amplitude that the filter removes by cancellation.  fp32
+  samples (2^-24 of the peak each) lose 0.5 - 1.5 % of the whitened signal before any arithmetic
+  (``tests/test_detector_like_host.py``), so samples, spectra, taps and sums are fp64 and only results are fp32.
+* Welch spectra: the hann-windowed half-overlapping segments through the fp64 ``torch.fft.rfft`` (rocFFT, ``n_seg`` x 1024),
+  rounded to fp32 per bin -- a relative 6e-8 there, whatever the bin's level -- then ``gww_welch_power_f32`` and the
+  per-frequency median by radix select (``gww_column_median_f32``).  Whitening is invariant under a rescaling of the
+  input, so every row is first brought to unit scale by an exact power of two (raw 1e-21 strain squares to 1e-42, below
+  fp32; in-band power at unit scale is about 1e-10 of the peak's, far inside fp32).
 * Filter design (a 513-point PSD in, a short FIR out): PyCBC's own sequence -- interpolate to the segment's frequency
   resolution, ``q = ifft(1 / sqrt(psd))``, hann-tapered truncation to ``max_filter_duration``, ``|fft(q)|`` -- in fp64
   with the N-point transforms of ``torch.fft`` (rocFFT); the result is read off as the impulse response
-  ``h = irfft(|fft(q)|)``, which is ``max_filter_len`` taps long up to the tail the modulus adds (kept until it is below
-  1e-6 of the response; with a low-frequency cutoff the rectified stop-band ripple can make it too long for the FIR form
-  (> 8191 taps): the response is then applied with the N-point transform, as the reference does).
-* Filter application: ``gww_fir_f32`` -- the strain streams once through LDS against those taps (time domain, O(1)
-  extra memory; circular padding reproduces the reference's circular convolution exactly) and the
-  ``max_filter_len // 2`` corrupted samples on each side are never computed.
+  ``h = irfft(|fft(q)|)``, which is ``max_filter_len`` taps long up to the tail the modulus adds.  The tail is kept until
+  what is left out is below 1e-6 of the response in l1 AND would add less than 1e-4 of the whitened standard deviation
+  for strain of the estimated PSD (``design_filter``: under a steep low-frequency wall the second test decides -- lined
+  detector-like strain needs 1025 taps where 513 leak 0.07 - 0.13 per sample).  With a low-frequency cutoff the
+  rectified stop-band ripple makes it too long for the FIR form (> 4097 taps): the response is then applied with the
+  N-point transform, as the reference does.  Every row is designed and filtered on its own, so its result does not depend
+  on the rows it is batched with.
+* Filter application: ``gww_fir_f64`` -- the fp64 strain streams once through LDS against the fp64 taps, fp64 sums, fp32
+  out (time domain, O(1) extra memory; circular padding reproduces the reference's circular convolution exactly) and
+  the ``max_filter_len // 2`` corrupted samples on each side are never computed.
 """
 
 from __future__ import annotations
@@ -34,24 +43,6 @@ import torch
 
 from . import _lib
 from ._lib import check, lib
-
-_DFT = {}
-
-
-def _welch_dft_matrix(seg_len: int, device) -> torch.Tensor:
-    """[>= 2 (seg_len / 2 + 1) rounded up to 4, seg_len] fp32: rows (2 j, 2 j + 1) = hann[k] cos / -hann[k] sin(2 pi j k / L)."""
-    key = (seg_len, str(device))
-    if key not in _DFT:
-        j = np.arange(seg_len // 2 + 1)[:, None].astype(np.float64)
-        k = np.arange(seg_len)[None, :].astype(np.float64)
-        ang = 2 * np.pi * ((j * k) % seg_len) / seg_len
-        w = np.hanning(seg_len)[None, :]
-        rows = 2 * (seg_len // 2 + 1)
-        m = np.zeros(((rows + 3) // 4 * 4, seg_len), np.float64)
-        m[0:rows:2] = np.cos(ang) * w
-        m[1:rows:2] = -np.sin(ang) * w
-        _DFT[key] = torch.from_numpy(m.astype(np.float32)).to(device)
-    return _DFT[key]
 
 
 def median_bias(n: int) -> float:
@@ -65,9 +56,8 @@ def median_bias(n: int) -> float:
 
 
 def welch_median_psd(x: torch.Tensor, delta_t: float, segment_duration: float):
-    """``TimeSeries(x, delta_t).psd(segment_duration)`` for every row of x [D, N] (fp32, unit scale): (psd fp64 [D, L / 2 + 1],
+    """``TimeSeries(x, delta_t).psd(segment_duration)`` for every row of x [D, N] (fp64, unit scale): (psd fp64 [D, L / 2 + 1],
     delta_f)."""
-    from . import ops
     D, n = x.shape
     seg_len = int(round(segment_duration / delta_t))
     stride = int(seg_len / 2)
@@ -80,14 +70,15 @@ def welch_median_psd(x: torch.Tensor, delta_t: float, segment_duration: float):
     diff = n - data_len
     start = diff // 2 + (diff % 2)
     n_bins = seg_len // 2 + 1
-    dft = _welch_dft_matrix(seg_len, x.device)
+    hann = torch.from_numpy(np.hanning(seg_len)).to(x.device)
     delta_f = 1.0 / delta_t / seg_len
     wsum = float((np.hanning(seg_len) ** 2).sum())
     out = torch.empty((D, n_bins), dtype=torch.float64, device=x.device)
     stream = torch.cuda.current_stream().cuda_stream
     for d in range(D):
-        frames = x[d, start:start + data_len].as_strided((n_seg, seg_len), (stride, 1)).contiguous()
-        spec = ops.gemm(frames, dft, None, 0)                                     # [n_seg, 2 n_bins (+pad)]
+        frames = x[d, start:start + data_len].as_strided((n_seg, seg_len), (stride, 1)) * hann
+        # fp64 transform; each (re, im) then rounds to fp32 on its own, so a quiet bin is as exact as a loud one
+        spec = torch.view_as_real(torch.fft.rfft(frames, dim=1)).float().reshape(n_seg, 2 * n_bins)
         power = torch.empty((n_seg, n_bins), dtype=torch.float32, device=x.device)
         med = torch.empty((n_bins,), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
@@ -99,15 +90,16 @@ def welch_median_psd(x: torch.Tensor, delta_t: float, segment_duration: float):
     return out, delta_f
 
 
-K_MAX = 4095          # longest half-length of the time-domain form (gww_fir_f32 takes up to 16384 taps)
+K_MAX = 4095          # longest half-length of the time-domain form (gww_fir_f64 takes up to 8192 taps)
 
 
 def design_filter(psd_w: torch.Tensor, delta_f_w: float, n: int, delta_t: float, max_filter_len: int,
-                  low_frequency_cutoff=None, trunc_method="hann", tail: float = 1e-6):
+                  low_frequency_cutoff=None, trunc_method="hann", tail: float = 1e-6, leak: float = 1e-4):
     """PyCBC's ``interpolate`` + ``inverse_spectrum_truncation`` for every row of psd_w (fp64 [D, bins]) at the resolution of an
-    n-sample segment; returns the correlation taps g fp32 [D, taps4] (zero padded to a multiple of 4) and K with
+    n-sample segment; returns the correlation taps g fp64 [D, taps4] (zero padded to a multiple of 4) and K with
     ``white[i] = sum_u g[u] x[(i - K + u) mod n]`` -- or ``(None, wf)`` with the frequency response ``|fft(q)|`` when the
-    response does not fit ``K_MAX`` taps to within ``tail`` of its l1 norm."""
+    response does not fit ``K_MAX`` taps: the taps left out must hold less than ``tail`` of its l1 norm, and what they would
+    have added to the output, for strain of this PSD, less than ``leak`` of the whitened standard deviation in rms."""
     D, bins = psd_w.shape
     dev = psd_w.device
     delta_f = 1.0 / (n * delta_t)
@@ -136,13 +128,22 @@ def design_filter(psd_w: torch.Tensor, delta_f_w: float, n: int, delta_t: float,
     wf = (torch.fft.rfft(q, dim=1) * delta_t).abs()                 # (1 / psd_out) ** 0.5 = |fft(q)|
     h = torch.fft.irfft(wf.to(torch.complex128), n=N, dim=1)        # real, even: white = h (*) x circularly
     # keep the central taps until the rest is negligible (max_filter_len // 2 each side + what the modulus spreads: with a
-    # low-frequency cutoff the rectified stop-band ripple decays slowly).  No K <= K_MAX reaches `tail`: return the
-    # frequency response instead and let the caller apply it with the N-point transform.
+    # low-frequency cutoff the rectified stop-band ripple decays slowly).  Negligible in two senses.  In l1, against any
+    # input.  And in what it does to THIS strain: the full response is ~ 0 where the PSD is a wall 1e12 above the bucket, the
+    # truncated one is not quite, and the wall leaks through the difference dH -- an error of variance sum_k dH_k^2 psd_k
+    # delta_f next to the whitened variance 1 / (2 delta_t).  Steep detector strain fails that long before it fails the l1
+    # test.  No K <= K_MAX passes both: return the frequency response instead and let the caller apply it with the
+    # N-point transform.
     K = max(t0, 64)
     total = h.abs().sum(dim=1)
     while True:
         rest = total - h[:, :K + 1].abs().sum(dim=1) - h[:, N - K:].abs().sum(dim=1)
-        if float((rest / total).max()) < tail:
+        left_out = h.clone()
+        left_out[:, :K + 1] = 0
+        left_out[:, N - K:] = 0
+        dH = torch.fft.rfft(left_out, dim=1).real
+        leaked = ((dH * dH * psd).sum(dim=1) * delta_f * (2 * delta_t)).sqrt()
+        if float((rest / total).max()) < tail and float(leaked.max()) < leak:
             break
         if 2 * K > K_MAX or 2 * K >= N // 2 - 1:
             return None, wf
@@ -150,8 +151,8 @@ def design_filter(psd_w: torch.Tensor, delta_f_w: float, n: int, delta_t: float,
     taps = torch.cat((h[:, N - K:], h[:, :K + 1]), dim=1)            # h[-K .. K]
     g = taps.flip(1)                                                 # g[u] = h[K - u]
     taps4 = (g.shape[1] + 3) // 4 * 4
-    gp = torch.zeros((D, taps4), dtype=torch.float32, device=dev)
-    gp[:, :g.shape[1]] = g.float()
+    gp = torch.zeros((D, taps4), dtype=torch.float64, device=dev)
+    gp[:, :g.shape[1]] = g
     return gp, K
 
 
@@ -174,34 +175,33 @@ def whiten(strain, delta_t: float = 1.0 / 2048.0, segment_duration: float = 0.5,
     D, n = x.shape
     if n % 2:
         raise ValueError("whiten: an even number of samples is required")
-    # unit scale by an exact power of two (whitening is scale invariant; fp32 cannot hold the square of 1e-21)
-    peak = float(x.abs().max())
-    scale = 2.0 ** (-math.floor(math.log2(peak))) if peak > 0 and math.isfinite(peak) else 1.0
-    xs = (x.double() * scale).float().contiguous()
+    # unit scale by an exact power of two, per row (whitening is scale invariant; fp32 cannot hold the square of 1e-21).
+    # The samples stay fp64: in-band content at 1e-5 of the peak does not survive an fp32 cast.
+    peaks = x.abs().amax(dim=1).double().tolist()
+    scales = [2.0 ** (-math.floor(math.log2(p))) if p > 0 and math.isfinite(p) else 1.0 for p in peaks]
+    scale = torch.tensor(scales, dtype=torch.float64, device=x.device)[:, None]
+    xs = (x.double() * scale).contiguous()
     psd_w, df_w = welch_median_psd(xs, delta_t, segment_duration)
     max_filter_len = int(max_filter_duration * (1.0 / delta_t))
-    g, K = design_filter(psd_w, df_w, n, delta_t, max_filter_len, low_frequency_cutoff, trunc_method)
     cut = max_filter_len // 2 if remove_corrupted else 0
     n_out = n - 2 * cut
-    if g is None:
-        # long response (low-frequency cutoff): the reference's own form, irfft(rfft(x) |fft(q)|), in fp64 (rocFFT)
-        white = torch.fft.irfft(torch.fft.rfft(xs.double(), dim=1) * K, n=n, dim=1)[:, cut:n - cut].float().contiguous()
-        if one_d:
-            white = white[0]
-        if return_psd:
-            p = psd_w / (scale * scale)
-            return white, (p[0] if one_d else p)
-        return white
-    # circular padding: output i (= sample cut + i) needs x[(cut + i - K + u) mod n], u = 0 .. 2 K
-    idx = (torch.arange(n_out + g.shape[1], device=x.device) + (cut - K)) % n
-    pad = (n_out + g.shape[1] + 3) // 4 * 4
-    xp = torch.zeros((D, pad), dtype=torch.float32, device=x.device)
-    xp[:, :idx.numel()] = xs[:, idx]
     out_stride = (n_out + 3) // 4 * 4
     out = torch.empty((D, out_stride), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        check(lib().gww_fir_f32(xp.data_ptr(), pad, g.data_ptr(), g.shape[1], D, out.data_ptr(), out_stride, n_out,
-                                torch.cuda.current_stream().cuda_stream), "gww_fir_f32")
+    # row by row: the form and the length of a row's filter follow from its own PSD, never from the rows it is batched with
+    for d in range(D):
+        g, K = design_filter(psd_w[d:d + 1], df_w, n, delta_t, max_filter_len, low_frequency_cutoff, trunc_method)
+        if g is None:
+            # long response (low-frequency cutoff): the reference's own form, irfft(rfft(x) |fft(q)|), in fp64 (rocFFT)
+            out[d, :n_out] = torch.fft.irfft(torch.fft.rfft(xs[d]) * K[0], n=n)[cut:n - cut]
+            continue
+        # circular padding: output i (= sample cut + i) needs x[(cut + i - K + u) mod n], u = 0 .. 2 K
+        idx = (torch.arange(n_out + g.shape[1], device=x.device) + (cut - K)) % n
+        pad = (n_out + g.shape[1] + 3) // 4 * 4
+        xp = torch.zeros((pad,), dtype=torch.float64, device=x.device)
+        xp[:idx.numel()] = xs[d, idx]
+        with torch.cuda.device(x.device):
+            check(lib().gww_fir_f64(xp.data_ptr(), pad, g.data_ptr(), g.shape[1], 1, out[d].data_ptr(), out_stride, n_out,
+                                    torch.cuda.current_stream().cuda_stream), "gww_fir_f64")
     white = out[:, :n_out]
     if one_d:
         white = white[0]

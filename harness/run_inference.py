@@ -74,14 +74,16 @@ def _have_h5py():
 
 
 def read_segments(path: str):
-    """{key: (strain [D, N] float32, start_time, delta_t)} in the reference's layout."""
+    """{key: (strain [D, N] in the file's own type, start_time, delta_t)} in the reference's layout.  Raw strain is stored
+    as float64 and whitening needs all of it (its in-band content lies at about 1e-5 of the sample peak): no narrowing
+    here -- the slicer makes whitened strain fp32 and hands raw strain to ``whiten`` as it is."""
     segs = {}
     if path.endswith(".npz"):
         z = np.load(path)
         keys = sorted({k.split("/", 1)[1] for k in z.files if k.split("/", 1)[0] == DETECTORS[0]})
         for key in keys:
-            segs[key] = (np.stack([z[f"{d}/{key}"] for d in DETECTORS]).astype(np.float32),
-                         float(z[f"{key}/start_time"]), float(z[f"{key}/delta_t"]))
+            segs[key] = (np.stack([z[f"{d}/{key}"] for d in DETECTORS]), float(z[f"{key}/start_time"]),
+                         float(z[f"{key}/delta_t"]))
         return segs
     import h5py
     with h5py.File(path, "r") as f:
@@ -89,7 +91,7 @@ def read_segments(path: str):
             dss = [f[d][key] for d in DETECTORS]
             st = dss[0].attrs["start_time"]
             assert all(ds.attrs["start_time"] == st for ds in dss)
-            segs[key] = (np.stack([ds[()] for ds in dss]).astype(np.float32), float(st), float(dss[0].attrs["delta_t"]))
+            segs[key] = (np.stack([ds[()] for ds in dss]), float(st), float(dss[0].attrs["delta_t"]))
     return segs
 
 

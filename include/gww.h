@@ -485,10 +485,14 @@ int gww_qadapter_cnn_backward_f32(const float* qspec, const float* dy, int B, in
  * the windowed real-DFT matrix), DC / Nyquist halved.  gww_column_median_f32: numpy.median over the segments per
  * frequency bin (values >= 0).  gww_fir_f32: the inverse-spectrum-truncated whitening filter applied as a FIR in the
  * time domain, out[d][n] = sum_u g[d][u] xp[d][n + u] (xp circularly padded by the caller, taps zero-padded to a
- * multiple of 4). */
+ * multiple of 4).  gww_fir_f64: the same with fp64 samples, taps and sums and one rounding to the fp32 output (what
+ * whitening uses: detector strain holds its in-band content at about 1e-5 of the sample peak); taps4 <= 8192, xp_stride
+ * even. */
 int gww_welch_power_f32(const float* spec, long ld, long n_seg, int n_bins, float scale, float* power, void* stream);
 int gww_column_median_f32(const float* power, long n_seg, int n_bins, float* median, void* stream);
 int gww_fir_f32(const float* xp, long xp_stride, const float* g, int taps4, int D, float* out, long out_stride,
+                long n_out, void* stream);
+int gww_fir_f64(const double* xp, long xp_stride, const double* g, int taps4, int D, float* out, long out_stride,
                 long n_out, void* stream);
 /* Trigger clustering on the device (MLGWSC-1/inference.py:140-166 `get_clusters` behind :484-487): windows whose score
  * exceeds trigger_threshold, in time order, join the running cluster unless they lie more than cluster_threshold seconds

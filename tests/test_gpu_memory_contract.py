@@ -1023,6 +1023,36 @@ def test_fir(T, gww, taps4, D):
         assert np.abs(got - ref).max() < 2e-3 * 32, (n_out, np.abs(got - ref).max())
 
 
+@pytest.mark.parametrize("D", [1, 3])
+@pytest.mark.parametrize("taps4", [4, 516, 1028, 8192])
+def test_fir_f64(T, gww, taps4, D):
+    """test_fir for the fp64 form (fp64 samples, taps and sums, fp32 out): the same extents -- xp holds exactly n_out + taps4
+    samples per row, out_stride > n_out -- with xp_stride even but no multiple of 4.  Against the fp64 correlation: the sum
+    of <= 8192 products carries about 1e-13 of their l1 norm, so the output is that correlation rounded to fp32 (2^-24
+    relative), to within one more unit in the last place."""
+    from gw_whisper_amd._lib import lib
+    for n_out in (1, 1023, 1024, 1025, 5000):
+        rng = np.random.default_rng(taps4 + n_out + D)
+        xp = rng.standard_normal((D, n_out + taps4))
+        gf = rng.standard_normal((D, taps4)) * (32.0 / np.sqrt(taps4))                        # output std ~ 32, as whitened noise
+        xpd, gd = _dev(T, xp), _dev(T, gf)
+        xs, os_ = (n_out + taps4 + 3) // 4 * 4 + 2, (n_out + 3) // 4 * 4 + 4
+
+        def case(g):
+            px, pg = g.place(xpd, pitch=xs), g.place(gd)
+            out = g.empty((D, os_), T.float32)
+            _ok(lib().gww_fir_f64(px.data_ptr(), xs, pg.data_ptr(), taps4, D, out.data_ptr(), os_, n_out, _stream(T)),
+                "gww_fir_f64")
+            _untouched(g, out[:, n_out:])
+            return {"out": out[:, :n_out]}
+        got = run_contract(case)["out"].double().cpu().numpy()
+        win = np.lib.stride_tricks.sliding_window_view(xp, taps4, axis=1)[:, :n_out]
+        ref = np.einsum("dnu,du->dn", win, gf)
+        l1 = np.abs(gf).sum(axis=1, keepdims=True) * np.abs(xp).max()                          # >= every output's sum |g x|
+        excess = (np.abs(got - ref) - (2.0 ** -23 * np.abs(ref) + 1e-12 * l1)).max()
+        assert excess <= 0, (n_out, excess, np.abs(got - ref).max())
+
+
 def test_cluster_triggers_with_fewer_slots_than_clusters(T, gww):
     """100 windows one second apart, all above threshold: 100 clusters; max_clusters = 7 of a 20-entry output.  out_count
     reports 100, exactly 7 entries are written, entries 7 .. 19 keep the fill."""
