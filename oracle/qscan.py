@@ -84,8 +84,9 @@ def _cubic_weights(t: np.ndarray, A: float = -0.75):
     return np.stack([c2(t + 1.0), c1(t), c1(1.0 - t), c2(2.0 - t)], axis=-1)
 
 
-def cubic_resize_last(x: np.ndarray, n_out: int) -> np.ndarray:
-    """1-D cubic resampling of the last axis with ``F.interpolate(mode='bicubic', align_corners=False)`` rules."""
+def cubic_resize_last(x: np.ndarray, n_out: int, abs_weights: bool = False) -> np.ndarray:
+    """1-D cubic resampling of the last axis with ``F.interpolate(mode='bicubic', align_corners=False)`` rules.
+    ``abs_weights``: the same taps with the absolute values of the cubic weights (an error envelope, not a resampling)."""
     n_in = x.shape[-1]
     if n_in == n_out:
         return x.copy()
@@ -93,6 +94,8 @@ def cubic_resize_last(x: np.ndarray, n_out: int) -> np.ndarray:
     src = (np.arange(n_out) + 0.5) * scale - 0.5
     i0 = np.floor(src).astype(np.int64)
     w = _cubic_weights(src - i0)
+    if abs_weights:
+        w = np.abs(w)
     out = np.zeros(x.shape[:-1] + (n_out,), dtype=x.dtype)
     for tap in range(4):
         idx = np.clip(i0 - 1 + tap, 0, n_in - 1)
@@ -100,9 +103,18 @@ def cubic_resize_last(x: np.ndarray, n_out: int) -> np.ndarray:
     return out
 
 
+def interpolate_plane(rows, spectrogram_shape, abs_weights: bool = False) -> np.ndarray:
+    """One Q plane's tile energies ([B, ntiles(row)] per frequency row) -> [B, F, T]: time first, per row, then
+    frequency.  ``abs_weights``: sum_taps |w_f| |w_t| e instead of sum_taps w_f w_t e."""
+    num_f, num_t = spectrogram_shape
+    r = np.stack([cubic_resize_last(e, num_t, abs_weights) for e in rows], axis=-2)                  # [B, nfreq, T]
+    return np.swapaxes(cubic_resize_last(np.swapaxes(r, -1, -2), num_f, abs_weights), -1, -2)        # [B, F, T]
+
+
 def qscan(x: np.ndarray, duration=1.0, sample_rate=2048, spectrogram_shape=(128, 128), qrange=(4, 128),
-          mismatch=0.2, return_plane: bool = False):
-    """x [B, duration * sample_rate] -> [B, F, T] (``QScan(...)(x)``)."""
+          mismatch=0.2, return_plane: bool = False, return_energies: bool = False):
+    """x [B, duration * sample_rate] -> [B, F, T] (``QScan(...)(x)``).  ``return_plane``: (out, chosen plane).
+    ``return_energies``: (out, chosen plane, [[normalised tile energies [B, ntiles] per row] per plane])."""
     x = np.asarray(x, np.float64)
     X = np.fft.rfft(x, axis=-1) / x.shape[-1]          # norm="forward"
     X[..., 1:] *= 2
@@ -110,7 +122,7 @@ def qscan(x: np.ndarray, duration=1.0, sample_rate=2048, spectrogram_shape=(128,
     energies = [[t.energy(X) for t in plane] for plane in planes]
     maxima = [max(float(e.max()) for e in plane) for plane in energies]       # over tiles AND the whole batch
     best = int(np.argmax(maxima))
-    num_f, num_t = spectrogram_shape
-    rows = np.stack([cubic_resize_last(e, num_t) for e in energies[best]], axis=-2)      # [B, nfreq, T]
-    out = np.swapaxes(cubic_resize_last(np.swapaxes(rows, -1, -2), num_f), -1, -2)       # [B, F, T]
+    out = interpolate_plane(energies[best], spectrogram_shape)
+    if return_energies:
+        return out, best, energies
     return (out, best) if return_plane else out
