@@ -82,6 +82,9 @@ SIGNATURES = {
     "gww_encoder_set_split": (C.c_int, [C.c_void_p, C.c_int]),
     "gww_encoder_set_stem_shortcut": (C.c_int, [C.c_void_p, C.c_int]),
     "gww_encoder_stem_shortcut_flags": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    "gww_encoder_set_x_native": (C.c_int, [C.c_void_p, C.c_int]),
+    "gww_x_native_offset": (C.c_size_t, [C.c_long, C.c_int, C.c_long]),
+    "gww_x_native_bytes": (C.c_size_t, [C.c_long]),
     "gww_encoder_trace_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "gww_encoder_trace_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gww_encoder_trace_classes": (C.c_int, []),

@@ -155,6 +155,19 @@ __device__ __forceinline__ float dgelu_fast(float z) {
 
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
 
+// The residual stream [M, 384] fp32 in ACCUMULATOR order (k_mlp_fused, FwdPlan::x_native): between two fused blocks of the
+// inference forward x_next has one reader, the same wave and lane that wrote it, so each 32-row wave slice keeps its own
+// 48 KiB but holds them as the 48 accumulator pieces of the wave, 1 KiB each: piece 4 t + cc is the 16 bytes every lane
+// (r, hh) owns of columns 32 t + 8 cc + 4 hh .. + 3, lane after lane.  Byte offset of element (g, c); a row past M is
+// clamped to M - 1 first, as the kernel's dead lanes are.  The buffer spans whole 128-row panels: x_native_bytes.
+__host__ __device__ inline size_t x_native_offset(long g, int c, long M) {
+  if (g > M - 1) g = M - 1;
+  const size_t slice = (size_t)(g >> 5);   // 4 P + w: panel P = g >> 7, wave w = (g >> 5) & 3
+  const int r = (int)(g & 31), t = c >> 5, cc = (c >> 3) & 3, hh = (c >> 2) & 1, k = c & 3;
+  return (slice * 48 + (size_t)(4 * t + cc)) * 1024 + (size_t)(r + 32 * hh) * 16 + (size_t)(4 * k);
+}
+inline size_t x_native_bytes(long M) { return (size_t)cdiv(M, 128) * 128 * 384 * 4; }
+
 // Byte offsets of consecutive buffers carved out of one allocation, each on a 256-byte boundary
 struct Arena {
   size_t off = 0;

@@ -351,6 +351,7 @@ struct FwdPlan {
   bool fuse_final;   // the last block ends in the encoder's final LayerNorm and writes last_hidden
   bool pooled;       // only the last token wanted: the last layer runs on B rows above its attention
   bool q_log2;       // the LN-folded q panel carries log2(e) (pack_weights)
+  bool x_native;     // between the fused blocks the residual stream stays in accumulator order (x_native_offset, common.h)
 };
 FwdPlan plan_forward(const gww_encoder* e, int batch, int precision, FwdWants want) {
   const gww_enc_cfg& c = e->cfg;
@@ -380,6 +381,13 @@ FwdPlan plan_forward(const gww_encoder* e, int batch, int precision, FwdWants wa
   // states (tap_hidden reads x in HBM), a last or pooled layer 0 and the generic paths keep the fill.
   p.x0_layer0 = p.shortcut && p.lnqkv0 && p.op && !want.hidden_slab && c.n_layers > 1;
   p.q_log2 = attention_log2q_enabled();
+  // Block l's x_next has one reader where every block is the fused ctx block and the last one writes last_hidden: block l + 1,
+  // by the lanes that wrote it.  It then never needs row order in HBM.  Whoever else reads x there -- a hidden slab, the pooled
+  // last layer, a stand-alone kernel of a generic path -- keeps it in rows.  (The order lives in x alone, whose padded_rows
+  // cover whole 128-row panels; a half batch of the split has its own x, so its first row opens a panel.)
+  p.x_native = e->x_native && p.op && p.fuse_final && !p.pooled && !want.hidden_slab && c.n_layers > 1 && d == 384 &&
+               mlp_fused_x_native_supported() && !(m & GP_X_NATIVE) &&
+               x_native_bytes((long)batch * T) <= padded_rows((size_t)batch * T) * d * 4;
   return p;
 }
 }  // namespace
@@ -402,6 +410,19 @@ extern "C" int gww_encoder_set_stem_shortcut(gww_encoder* e, int on) {
   e->stem_shortcut = on != 0;
   return GWW_OK;
 }
+
+extern "C" int gww_encoder_set_x_native(gww_encoder* e, int on) {
+  GWW_REQUIRE(e != nullptr, "gww_encoder_set_x_native: NULL handle");
+  e->x_native = on != 0;
+  return GWW_OK;
+}
+
+// (host only: the layout function itself, for tests and tools)
+extern "C" size_t gww_x_native_offset(long row, int col, long M) {
+  if (row < 0 || col < 0 || col >= 384 || M <= 0) return (size_t)-1;
+  return x_native_offset(row, col, M);
+}
+extern "C" size_t gww_x_native_bytes(long M) { return M > 0 ? x_native_bytes(M) : 0; }
 
 // The device flags of the last forward that ran in `workspace` with this batch and precision (blocking; synchronise the
 // forward's stream first): flags[i] = 1 where half batch i took the shortcut, 0 where it ran the full stem, -1 where the
@@ -646,23 +667,24 @@ int Fwd::walk_astat() {
     // (layer 0 behind the compact stem forms x in registers and has no x_new: xs / tr live in that buffer until it has run)
     MlpFusedArgs a = args();
     a.x = st.xc; a.x_new = from_x0 ? nullptr : st.xn; a.ln_u = L.u1; a.ln_cb = L.cb1; a.b2 = L.b2; a.F = F;
+    // (x_native: a block reads what the block before it left in accumulator order; layer 0 reads the stem's rows, and where it
+    // forms them itself -- from_x0, an instantiation without that order -- it also writes rows and layer 1 starts the order)
+    a.x_native_in = p.x_native && i > (p.x0_layer0 ? 1 : 0);
     if (p.op) { a.ctx = ctx; a.bo = L.bo; a.Wt = L.wmlp_op; }
     else { a.delta = d1; a.Wt = L.wmlp; }
     if (p.fuse_qkv && !last) {
       // fused + the next layer's LN1 + q / k / v: x_next comes back in xc itself (xn only held x_new), no delta is pending
       with_qkv(a, e->layers[i + 1]);
       if (from_x0) a.x0 = &x0;
+      a.x_native_out = p.x_native && !from_x0;
       TR(TR_MLPQKV, launch_mlp_fused(a, s));
       st.qkv_ready = true;
     } else if (p.fuse_final) {
       // the LAST block with the encoder's final LayerNorm as its epilogue: last_hidden_state comes straight out of the
       // kernel (no bf16 delta, no second read of the residual stream, no LayerNorm launch); the pooled token is row
-      // T - 1 of it
-      a.lnf_w = e->lnw; a.lnf_b = e->lnb; a.y = last_hidden;
+      // T - 1 of it, which the lanes that own it store to last_token as well
+      a.lnf_w = e->lnw; a.lnf_b = e->lnb; a.y = last_hidden; a.last_token = last_token; a.T = T;
       TR(TR_MLPFIN, launch_mlp_fused(a, s));
-      if (last_token)
-        GWW_HIP(hipMemcpy2DAsync(last_token, (size_t)d * 4, last_hidden + (size_t)(T - 1) * d, (size_t)T * d * 4, (size_t)d * 4,
-                                 B, hipMemcpyDeviceToDevice, s));
       return tap_final();
     } else if (p.mlp_fused) {
       // fused plain: LN2 + fc1 + GELU + fc2 in one kernel, the [M, ffn] activation never leaves the CU

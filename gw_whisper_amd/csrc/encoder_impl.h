@@ -64,6 +64,7 @@ enum : int {
   GP_ASTAT_512 = 512,      // bit 9: A-stationary layer GEMMs at d = 512
   GP_CONV2_FULLN = 1024,   // bit 10: conv2 on the generic GEMM where k_gemm_fulln would take it
   GP_STEM_SHORTCUT = 2048, // bit 11: no constant-tail shortcut of the stem
+  GP_X_NATIVE = 4096,      // bit 12: the residual stream in row order between the fused blocks too
 };
 inline int generic_path_mask() {
   static const int mask = (int)lab_int("GWW_GENERIC_PATH", 0);
@@ -111,6 +112,7 @@ struct gww_encoder {
   bool ready = false;
   bool trace = false;
   bool stem_shortcut = true;        // the constant-tail shortcut of the bf16 inference stem (gww_encoder_set_stem_shortcut)
+  bool x_native = true;             // the residual stream in accumulator order between fused blocks (gww_encoder_set_x_native)
   std::vector<TraceSpan> spans;     // recorded since the last read
   std::vector<hipEvent_t> pool;     // reusable events
   // dual-stream split: two half batches on two library-owned streams, so HBM-bound kernels of one

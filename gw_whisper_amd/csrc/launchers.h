@@ -55,6 +55,7 @@ int launch_attention_bwd_bf16(const void* qkv, const void* ctx, const void* dctx
 int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_folded, void* out, int d, int F, int NQ,
                     hipStream_t s, const void* wo = nullptr);
 bool mlp_fused_supported(int d, int F);   // the fused block exists for this width / ffn (MF_D, MF_FMAX)
+bool mlp_fused_x_native_supported();      // ... and its accumulator-order instantiations (MlpFusedArgs::x_native_in / _out)
 // The operands of the compact stem (stem_tail.hip) from which layer 0 forms its rows of the residual stream: xs [B, Tt, 384],
 // tr [B, 384], pos [T, 384] where *flag == 1; x is read where it is 0 (decided in the kernel).  M = B T.
 struct MfX0 {
@@ -88,6 +89,11 @@ struct MlpFusedArgs {
   float* x_next = nullptr;         // fp32 [M, 384], != x_new; unset: x_next is written over x
   const float *lnf_w = nullptr, *lnf_b = nullptr;   // the final LayerNorm
   float* y = nullptr;              // fp32 [M, 384], != x_new
+  float* last_token = nullptr;     // (with y) fp32 [M / T, 384]: row T - 1 of every segment of y once more ...
+  int T = 0;                       // ... T: rows per segment, M % T == 0
+  // The residual stream in accumulator order (x_native_offset, common.h; ctx blocks only, [roundup(M, 128), 384] then):
+  bool x_native_in = false;        // x is read in it (neither side with x0, never with x_new kept) ...
+  bool x_native_out = false;       // ... x_next is written in it (qkv_out blocks)
   const MfX0* x0 = nullptr;         // (k_mlp_fused takes it by value)
   long M = 0;
   int d = 0, F = 0;

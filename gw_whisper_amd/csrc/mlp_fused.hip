@@ -103,6 +103,24 @@ constexpr int MF_WAVES = 4, MF_THREADS = 256, MF_BM = 128;
 #else
 #define MF_XNT ""
 #endif
+#ifndef GWW_MF_XN_LDNT
+#define GWW_MF_XN_LDNT 1   // XL (the residual stream in accumulator order, below): the x request with the non-temporal hint -- every
+                           // wave instruction reads 8 whole lines that nobody else touches, so unlike GWW_MF_XNT it costs nothing
+                           // (the four builds: profiles/x_native_layout.md)
+#endif
+#ifndef GWW_MF_XN_STNT
+#define GWW_MF_XN_STNT 1   // XL: the x_next stores (whole lines) with the non-temporal hint
+#endif
+#if GWW_MF_XN_LDNT
+#define MF_XN_LDNT " nt"
+#else
+#define MF_XN_LDNT ""
+#endif
+#if GWW_MF_XN_STNT
+#define MF_XN_STNT " nt"
+#else
+#define MF_XN_STNT ""
+#endif
 #ifndef GWW_MF_DMAGAP
 #define GWW_MF_DMAGAP 1   // (with SCHED) DMA pieces of a riding tile in the gaps the GELU schedule leaves empty (0: one per step)
 #endif
@@ -247,7 +265,11 @@ __device__ __forceinline__ const float* mf_x0_row(const MfX0& z, const float* X,
 
 struct MfNoX0 {};
 // (X0 only changes the TYPE of the last kernel argument: the instantiations without it keep their code as it was)
-template <int MODE, bool OP, bool X0 = false>
+// XL (XACC only; x_native_offset, common.h): the residual stream in ACCUMULATOR order on either side of the launch.  Bit 0: X is
+// read in that order, bit 1: x_next is written in it.  A lane's 48 requests / stores are then the 48 whole KiB of its wave's
+// slice -- 8 full lines per wave instruction instead of 32 quarter lines -- in the same number and order as in row order, so
+// every counted wait stands.  XL = 0: the code as it was.  MODE 3: q_out / NQ carry last_token and T (below).
+template <int MODE, bool OP, bool X0 = false, int XL = 0>
 __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, const unsigned short* delta, float* x_out,
                                                             const float* __restrict__ ln_u,
                                                             const float* __restrict__ ln_cb,
@@ -263,6 +285,10 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   constexpr bool QKV = MODE == 1 || MODE == 2, LNQ = MODE == 2, FIN = MODE == 3;
   static_assert(!X0 || (GWW_MF_NORM && GWW_MF_XACC && (MODE == 2 || (MODE == 1 && OP))), "X0: layer 0's two launches; stages in the u table");
   constexpr bool XACC = GWW_MF_XACC && GWW_MF_NORM && GWW_MF_SCHED && OP && (MODE == 1 || MODE == 3);
+  constexpr bool XIN = (XL & 1) != 0, XOUT = (XL & 2) != 0;
+  // (not with X0: in <1, true, true> hipcc copies a landing ctx fragment out of its registers in front of the wait that covers
+  // it as soon as the x_next stores change -- tools/audit_asm_loads.py; layer 0 behind the compact stem writes rows)
+  static_assert(XL == 0 || (XACC && !GWW_MF_XLDS && !X0 && (!XOUT || MODE == 1) && XL <= 3), "XL: the accumulator-order stream of XACC");
   constexpr int MF_NST = MF_AHEAD + 1;
   float* lds_cb = reinterpret_cast<float*>(lds + MF_OFF_CB);
   float* lds_u = reinterpret_cast<float*>(lds + MF_OFF_U);
@@ -362,6 +388,8 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   // accumulator layout of O: lane (r, hh) owns row m_base + r, columns 32 t + 8 cc + 4 hh .. + 3 in O[t][4 cc ..]
   const long xrow_l = m_base + r < M ? m_base + r : M - 1;
   const unsigned xoff = (unsigned)xrow_l * (unsigned)(MF_D * 4) + 16u * (unsigned)hh;
+  // ... and in accumulator order (XL): the row's wave slice, its lane slot there; piece 4 t + cc follows at + 1024 (4 t + cc)
+  const unsigned xoff_n = (unsigned)(xrow_l >> 5) * (unsigned)(32 * MF_D * 4) + 16u * (((unsigned)xrow_l & 31u) + 32u * (unsigned)hh);
   f32x4 xp[XACC ? MF_OT : 1][4];
   // ---- X0: the device flag (block-uniform), the panel's first segment, and what every thread stages of the shared rows: 16-byte
   // piece q of [2 segments][xs[b, Tt - 2] | tr[b]][96] (the panel's segments are seg0 and, clamped to the last one, seg0 + 1)
@@ -415,6 +443,8 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc)
         if (GWW_MF_ABL & 32) asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(xp[t][cc][0]));   // (diagnostic: no x loads)
+        else if constexpr (XIN)   // (a scalar base per 32-column block: the immediate does not reach 48 KiB)
+          asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" MF_XN_LDNT : "=a"(xp[t][cc]) : "v"(xoff_n), "s"(reinterpret_cast<const char*>(X) + 4096 * t), "n"(1024 * cc) : "memory");
         else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" MF_XNT : "=a"(xp[t][cc]) : "v"(xoff), "s"(X), "n"((32 * t + 8 * cc) * 4) : "memory");
   }
   // ---- prologue: x_new = x + delta (written back), a = bf16(x_new - c), exact fp32 row statistics
@@ -1095,7 +1125,8 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   // af[4 S + cc] of lane (r, hh) is k = 64 S + 32 hh + 8 cc .. + 7: the low lane needs the partner's half of the EVEN block
   // 2 S, the high lane the partner's half of the ODD block 2 S + 1 -- exactly one v_permlane32_swap per packed word pair
   // (attention.hip's GWW_ATT_EPI16 epilogue uses the same exchange).  One rounding, no LDS, no second normalise pass.
-  auto seam_x = [&](const float* sb, float* dst) {
+  auto seam_x = [&](const float* sb, float* dst, auto native_c, const unsigned xst_n) {   // native_c: dst in accumulator order (XL bit 1); xst_n (XL, MODE 1): the lane's byte offset in dst -- its slot there, or what xoff is for rows
+    constexpr bool NAT = decltype(native_c)::value;
     if constexpr (XACC) {
     float s1 = 0.f, s2 = 0.f, csh = 0.f;
 #pragma unroll
@@ -1107,8 +1138,15 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
         if (dst && !(GWW_MF_ABL & 16)) {
           if (GWW_MF_XLDS) {   // into the slice in accumulator layout (rows 144 bytes apart: conflict-free for the 16-lane groups)
             *reinterpret_cast<f32x4*>(slice0 + (t & 1) * (MF_WAVES * MF_SLICE_BYTES) + r * MF_SLICE_STRIDE + (8 * cc + 4 * hh) * 4) = v;
+          } else if constexpr (NAT) {
+            // (asm, as the requests are: a scalar base per 32-column block, the lane's slot, the piece as the immediate -- left to
+            // itself hipcc forms a 64-bit address in a register pair per store).  The s_nop 1 is the two wait states a store of
+            // more than 64 bits needs on gfx950 in front of a VALU write of its data registers (what hipcc itself emits behind
+            // such a store, and what store_chunk's asm store carries) -- v is shifted in place right below, and hipcc's hazard
+            // recogniser does not see a store inside an asm statement
+            asm volatile("global_store_dwordx4 %0, %1, %2 offset:%3" MF_XN_STNT "\n\ts_nop 1" : : "v"(xst_n), "v"(v), "s"(reinterpret_cast<char*>(dst) + 4096 * t), "n"(1024 * cc) : "memory");
           } else {
-            f32x4* const sp = reinterpret_cast<f32x4*>(reinterpret_cast<char*>(dst) + xoff + (32 * t + 8 * cc) * 4);
+            f32x4* const sp = reinterpret_cast<f32x4*>(reinterpret_cast<char*>(dst) + (XL != 0 && MODE == 1 ? xst_n : xoff) + (32 * t + 8 * cc) * 4);
             if (GWW_MF_XSTNT) __builtin_nontemporal_store(v, sp);
             else *sp = v;
           }
@@ -1203,7 +1241,19 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
     if constexpr (XACC) {
       // x_new = x + ctx W_o^T + bo sits in O (bo is added on the fly): LN2 statistics and the fc1 operand straight from the
       // registers; fc2 keeps accumulating on top of it
-      seam_x(lds_bo, (keep_x_new && !(GWW_MF_ABL & 256)) ? x_out : nullptr);   // (256: diagnostic, the ABI entry without x_new)
+      if constexpr (XL != 0 && MODE == 1) {
+        // The launcher never keeps x_new with XL, but the seam keeps its FORM: with the stores compiled out its 48 pieces
+        // become one basic block, hipcc contracts the row sums differently there (-ffp-contract=fast) and one row in a few
+        // thousand moves by a bf16 ulp of its operand.  The row offset is formed here, not carried from the kernel's start.
+        // Nothing in the language promises that choice: bitwise equality with the row-order build rests on it, and
+        // tests/test_gpu_x_native.py (bitwise, per row) is the guard -- after a compiler change, run it first.
+        unsigned lo = lane_off;
+        asm volatile("" : "+v"(lo));
+        const long g = m_base + (long)((lo >> 4) & 31u);
+        const unsigned gc = (unsigned)(g < M ? g : M - 1);
+        seam_x(lds_bo, (keep_x_new && !(GWW_MF_ABL & 256)) ? x_out : nullptr, std::false_type{}, gc * (unsigned)(MF_D * 4) + ((lo >> 9) << 4));
+      } else
+      seam_x(lds_bo, (keep_x_new && !(GWW_MF_ABL & 256)) ? x_out : nullptr, std::false_type{}, 0u);   // (256: diagnostic, the ABI entry without x_new)
     } else {
     // x_new = x + bf16(ctx W_o^T + bo): written to x_out, LN2 statistics, A fragments
     seam(X, x_out, lds_bo, [] {});
@@ -1328,6 +1378,19 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
         } else if (GWW_MF_XSTNT) __builtin_nontemporal_store(y, reinterpret_cast<f32x4*>(reinterpret_cast<char*>(y_out) + xoff + (32 * t + 8 * cc) * 4));
         else *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(y_out) + xoff + (32 * t + 8 * cc) * 4) = y;
       }
+    // ---- the pooled row.  q_out carries last_token [B, 384] (or null) and NQ the segment length T in this mode: the lanes that
+    // own row T - 1 of a segment copy the 48 pieces they have just stored to last_token (a thread reads its own stores; clamped
+    // duplicates of row M - 1 copy the same values again).  A rolled loop behind the epilogue, in the one wave in forty-seven
+    // that holds such a row: nothing of it is live above, and the code above keeps the form -- and the arithmetic -- it had.
+    if (float* const lt_out = reinterpret_cast<float*>(q_out)) {
+      const unsigned b = (unsigned)xrow_l / (unsigned)NQ;
+      if ((unsigned)xrow_l - b * (unsigned)NQ == (unsigned)NQ - 1u) {
+        const char* const src = reinterpret_cast<const char*>(y_out) + xoff;
+        char* const lt = reinterpret_cast<char*>(lt_out) + b * (unsigned)(MF_D * 4) + 16u * (unsigned)hh;
+#pragma unroll 1
+        for (int i = 0; i < 4 * MF_OT; ++i) *reinterpret_cast<f32x4*>(lt + 32 * i) = *reinterpret_cast<const f32x4*>(src + 32 * i);
+      }
+    }
   } else if constexpr (FIN) {
     // ---- MODE 3, the LAST block of the encoder: the epilogue is the final LayerNorm (HF:modeling_whisper.py:642).
     // x_fin = x_new + bf16(fc2 output + b2) is formed exactly as the second seam forms x_next (same roundings as the
@@ -1423,6 +1486,18 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
           *reinterpret_cast<f32x4*>(reinterpret_cast<char*>(y_out) + roff[i] + (64 * np + 32 * h2) * 4) = y;
         }
       }
+    // the pooled row (q_out: last_token or null, NQ: T), as in the accumulator-order form above: copied by the lanes that stored it
+    if (float* const lt_out = reinterpret_cast<float*>(q_out)) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const unsigned b = (unsigned)grow[i] / (unsigned)NQ;
+        if ((unsigned)grow[i] - b * (unsigned)NQ != (unsigned)NQ - 1u) continue;
+        const char* const src = reinterpret_cast<const char*>(y_out) + roff[i];
+        char* const lt = reinterpret_cast<char*>(lt_out) + b * (unsigned)(MF_D * 4) + 16u * (unsigned)cchunk;
+#pragma unroll 1
+        for (int q = 0; q < 2 * MF_KT; ++q) *reinterpret_cast<f32x4*>(lt + 128 * q) = *reinterpret_cast<const f32x4*>(src + 128 * q);
+      }
+    }
   } else if constexpr (!QKV) {
     mf_wait_vmcnt<0>();   // the re-reads issued past the end
     // ---- epilogue: + b2 -> bf16 -> wave-private LDS transpose -> whole-line stores
@@ -1457,7 +1532,16 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
     if constexpr (XACC) {
       // x_next = O + (b2 + bo), stored from the accumulator layout (48 stores per lane, all lanes live: the first two tail
       // tiles count them), LN1 statistics and the q / k / v operand from the registers
-      seam_x(lds_b2, x_next);
+      if constexpr (XOUT) {
+        // the lane's slot in the accumulator-order stream is formed HERE, from the DMA's lane offset (16 lane, live anyway), not
+        // carried through the block in a register of its own
+        unsigned lo = lane_off;
+        asm volatile("" : "+v"(lo));
+        const long g = m_base + (long)((lo >> 4) & 31u);
+        const unsigned gc = (unsigned)(g < M ? g : M - 1);
+        seam_x(lds_b2, x_next, std::true_type{}, (gc >> 5) * (unsigned)(32 * MF_D * 4) + 16u * (gc & 31u) + (lo & 512u));
+      } else
+      seam_x(lds_b2, x_next, std::false_type{}, 0u);
     } else if constexpr (!LNQ) {   // the seam (MODE 2: the prologue already produced the normalised operand of LN1)
       seam(x_out, x_next, lds_b2, [] {});
 #if GWW_MF_NORM
@@ -1866,6 +1950,9 @@ int launch_mlp_pack(const void* w1_folded, const void* w2, const void* wqkv_fold
 }
 
 bool mlp_fused_supported(int d, int F) { return d == MF_D && F > 0 && F % 128 == 0 && F <= MF_FMAX; }
+// the accumulator-order instantiations exist where the ctx blocks keep the residual stream in their accumulators
+constexpr bool MF_XL_BUILT = GWW_MF_XACC && GWW_MF_NORM && GWW_MF_SCHED && !GWW_MF_XLDS;
+bool mlp_fused_x_native_supported() { return MF_XL_BUILT; }
 
 // THE launcher of k_mlp_fused (MlpFusedArgs, launchers.h: which fields are set selects <MODE, OP, X0>).  Wt per mode:
 // launch_mlp_pack(w1_folded, w2, next q / k / v panel or NULL, ., wo with ctx); the q / k / v panel alone for <2, false>.
@@ -1875,6 +1962,12 @@ int launch_mlp_fused(const MlpFusedArgs& a, hipStream_t s) {
   const bool op = a.ctx != nullptr, lnq = !A, fin = a.y != nullptr, qkv = a.qkv_out != nullptr, x0 = a.x0 != nullptr;
   GWW_REQUIRE(!(a.ctx && a.delta) && op == (a.bo != nullptr), "%s: a pending delta, or ctx with the out_proj bias", who);
   GWW_REQUIRE(!fin || (op && !qkv && !a.C && a.lnf_w && a.lnf_b), "%s: the final LayerNorm takes ctx, bo, lnf_w, lnf_b and no other output", who);
+  GWW_REQUIRE(!a.last_token || (fin && a.T > 0 && a.M % a.T == 0 && (((uintptr_t)a.last_token) & 15) == 0 && a.last_token != a.y),
+              "%s: last_token comes with y, T rows per segment and M %% T == 0", who);
+  const int xl = (a.x_native_in ? 1 : 0) | (a.x_native_out ? 2 : 0);
+  GWW_REQUIRE(!xl || (MF_XL_BUILT && op && !a.keep_x_new && !x0 && (!a.x_native_out || (qkv && !a.x_next))),
+              "%s: the accumulator-order residual stream runs between ctx blocks that keep no x_new, in place", who);
+  GWW_REQUIRE(!xl || (long)x_native_bytes(a.M) < (1L << 32), "%s: M = %ld rows exceed the 32-bit offsets of the accumulator-order stream", who, a.M);
   GWW_REQUIRE(!lnq || (!a.x_new && !a.ln_u && !a.ln_cb && !a.b2 && !a.C && a.F == 0), "%s: LayerNorm 1 + q / k / v alone takes no block operand", who);
   GWW_REQUIRE(fin || qkv || (!lnq && a.C), "%s: no output", who);
   // x0 forms x in registers while xs / tr may live in what is x_new elsewhere: it exists for <2, false> and <1, true>, and never keeps x_new
@@ -1913,8 +2006,20 @@ int launch_mlp_fused(const MlpFusedArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(kernel, dim3((unsigned)panels), dim3(MF_THREADS), 0, s, a.x, (const unsigned short*)A, a.x_new, a.ln_u, a.ln_cb,
                        (const unsigned short*)a.Wt, a.b2, fin ? reinterpret_cast<unsigned short*>(a.y) : (unsigned short*)a.C, a.M, a.F,
                        stagger, fin ? a.lnf_w : qkv ? a.qkv_u : nullptr, fin ? a.lnf_b : qkv ? a.qkv_cb : nullptr,
-                       (unsigned short*)a.qkv_out, qkv ? a.NQ : 0, x_next, a.bo, a.keep_x_new ? 1 : 0, z);
+                       fin ? reinterpret_cast<unsigned short*>(a.last_token) : (unsigned short*)a.qkv_out,
+                       fin ? (a.last_token ? a.T : 0) : qkv ? a.NQ : 0, x_next, a.bo, a.keep_x_new ? 1 : 0, z);
   };
+  if constexpr (MF_XL_BUILT) {
+    if (xl) {   // the residual stream in accumulator order on the way in (1), out (2) or both
+      const int mode = fin ? 3 : 1;
+      if (mode == 1 && !x0 && xl == 2) launch(k_mlp_fused<1, true, false, 2>, MfNoX0{});
+      else if (mode == 1 && xl == 3) launch(k_mlp_fused<1, true, false, 3>, MfNoX0{});
+      else if (mode == 3 && xl == 1) launch(k_mlp_fused<3, true, false, 1>, MfNoX0{});
+      else return fail(GWW_ERR_ARG, "%s: no such instantiation of k_mlp_fused", who);
+      GWW_LAUNCH_CHECK();
+      return GWW_OK;
+    }
+  }
   switch ((lnq ? 2 : fin ? 3 : qkv ? 1 : 0) | (op ? 4 : 0) | (x0 ? 8 : 0)) {   // every instantiation there is (in the order the code object has always held them)
     case 5: launch(k_mlp_fused<1, true>, MfNoX0{}); break;
     case 1: launch(k_mlp_fused<1, false>, MfNoX0{}); break;

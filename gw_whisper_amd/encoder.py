@@ -493,6 +493,10 @@ class WhisperEncoder(nn.Module):
         """Constant-tail shortcut of the bf16 inference stem (see gww_encoder_set_stem_shortcut); on by default."""
         check(lib().gww_encoder_set_stem_shortcut(self._ensure_handle(), int(on)), "gww_encoder_set_stem_shortcut")
 
+    def set_x_native(self, on: bool = True):
+        """Residual stream in accumulator order between the fused blocks (see gww_encoder_set_x_native); on by default."""
+        check(lib().gww_encoder_set_x_native(self._ensure_handle(), int(on)), "gww_encoder_set_x_native")
+
     def stem_shortcut_flags(self, batch: int) -> tuple:
         """What the last inference forward of ``batch`` segments decided on the device, per half batch: 1 = shortcut
         taken, 0 = full stem, -1 = does not apply (synchronises)."""

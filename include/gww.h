@@ -161,6 +161,17 @@ int gww_encoder_set_split(gww_encoder* enc, int on);
 int gww_encoder_set_stem_shortcut(gww_encoder* enc, int on);
 int gww_encoder_stem_shortcut_flags(const gww_encoder* enc, int batch, int precision, const void* workspace, int* flags);
 
+/* The residual stream in accumulator order between the fused blocks (on by default where it applies: bf16, d = 384, every
+ * block fused with out_proj in front, last_hidden wanted, no per-layer hidden states, more than one layer).  Between two
+ * blocks the stream has one reader, the lanes that wrote it, so each 32-row slice of a 128-row panel keeps its 48 KiB of the
+ * workspace but holds them as the 48 one-KiB pieces of the wave that owns it; last_hidden / last_token stay in row order and
+ * are bit-identical either way.  `on` = 0 keeps row order everywhere.  gww_x_native_offset is the layout itself (host only,
+ * no GPU): the byte offset of element (row, col) of an [M, 384] fp32 stream, a row past M clamped to M - 1;
+ * gww_x_native_bytes(M) the bytes it spans (whole panels).  (size_t) -1 on a bad argument. */
+int gww_encoder_set_x_native(gww_encoder* enc, int on);
+size_t gww_x_native_offset(long row, int col, long M);
+size_t gww_x_native_bytes(long M);
+
 /* Optional per-kernel timing of the forward (hipEvents on the caller's stream around every
  * launch; ~30 events per forward).  Classes: gww_encoder_trace_classes() entries named by
  * gww_encoder_trace_class_name(i).  gww_encoder_trace_read sums elapsed ms and launch counts per
