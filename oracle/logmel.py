@@ -89,42 +89,57 @@ def pad_or_trim(wave: np.ndarray) -> np.ndarray:
     return out
 
 
-def stft_power(padded: np.ndarray, dtype=np.float64) -> np.ndarray:
+def stft_power(padded: np.ndarray, dtype=np.float64, window=None, return_parts: bool = False):
     """|STFT|^2 of the 480000-sample buffers, frames 0..2999 -> [N, 201, 3000].
 
-    ``torch.stft(center=True, pad_mode="reflect")`` then ``[..., :-1]``.
+    ``torch.stft(center=True, pad_mode="reflect")`` then ``[..., :-1]``.  ``window`` (400 values) replaces the exact
+    periodic Hann; ``return_parts`` adds the l2 norm of every windowed frame [N, 3000] (float64).
     """
     x = np.asarray(padded, dtype=dtype)
     n = x.shape[0]
     xp = np.pad(x, ((0, 0), (N_FFT // 2, N_FFT // 2)), mode="reflect")
-    win = hann_periodic().astype(dtype)
+    win = (hann_periodic() if window is None else np.asarray(window, np.float64).reshape(N_FFT)).astype(dtype)
     # frame t covers xp[160 t : 160 t + 400]
     idx = (np.arange(N_FRAMES)[:, None] * HOP + np.arange(N_FFT)[None, :])
     out = np.empty((n, N_FREQ, N_FRAMES), dtype=dtype)
+    norms = np.empty((n, N_FRAMES), dtype=np.float64)
     for i in range(n):
         frames = xp[i][idx] * win[None, :]
         spec = np.fft.rfft(frames.astype(np.float64), axis=1)
         out[i] = (spec.real ** 2 + spec.imag ** 2).T.astype(dtype)
-    return out
+        if return_parts:
+            norms[i] = np.sqrt((frames.astype(np.float64) ** 2).sum(axis=1))
+    return (out, norms) if return_parts else out
 
 
-def log_mel(wave: np.ndarray, dtype=np.float32) -> np.ndarray:
-    """[N, L] (or [L]) waveform -> [N, 80, 3000] ``input_features`` in ``dtype``.
+def log_mel(wave: np.ndarray, dtype=np.float32, n_mels: int = N_MELS, window=None, return_parts: bool = False):
+    """[N, L] (or [L]) waveform -> [N, n_mels, 3000] ``input_features`` in ``dtype``.
 
     ``dtype=np.float32`` follows HF's fp32 torch path (filterbank cast to f32,
     f32 matmul / log10); ``np.float64`` is the high-precision variant used to
     bound the f32 rounding noise in the tests.
+
+    ``window``: 400 values used in place of the exact fp64 periodic Hann (the tests of the kernels pass the table the
+    library holds, so that the oracle is exact arithmetic on the function the kernels compute).
+    ``return_parts=True`` returns ``(features, parts)``, ``parts`` a dict of
+    ``raw`` [N, n_mels, 3000] (log10 of the clamped mel energies, before the max - 8 clamp), ``max`` [N] (the per-segment
+    maximum of ``raw``), ``frame_norm`` [N, 3000] (l2 norm of each windowed frame) and ``mag`` [N, 201, 3000] (|X|).
     """
     padded = pad_or_trim(np.asarray(wave, dtype=np.float32))
-    power = stft_power(padded, dtype=dtype)
-    fb = mel_filter_bank().astype(dtype)                      # [201, 80]
+    power = stft_power(padded, dtype=dtype, window=window, return_parts=return_parts)
+    if return_parts:
+        power, norms = power
+    fb = mel_filter_bank(n_mels=n_mels).astype(dtype)         # [201, n_mels]
     mel = np.einsum("fm,nft->nmt", fb, power).astype(dtype)   # mel.T @ P
     # log10 evaluated in f64 and rounded once: numpy's f32 log10 is 1 ulp off at
     # 1e-10 (-10.000001) where torch gives the correctly rounded -10.0
-    log_spec = np.log10(np.maximum(mel, dtype(1e-10)).astype(np.float64)).astype(dtype)
-    mx = log_spec.reshape(log_spec.shape[0], -1).max(axis=1)[:, None, None]
-    log_spec = np.maximum(log_spec, mx - dtype(8.0))
-    return ((log_spec + dtype(4.0)) / dtype(4.0)).astype(dtype)
+    raw = np.log10(np.maximum(mel, dtype(1e-10)).astype(np.float64)).astype(dtype)
+    mx = raw.reshape(raw.shape[0], -1).max(axis=1)[:, None, None]
+    log_spec = np.maximum(raw, mx - dtype(8.0))
+    out = ((log_spec + dtype(4.0)) / dtype(4.0)).astype(dtype)
+    if return_parts:
+        return out, {"raw": raw, "max": mx[:, 0, 0], "frame_norm": norms, "mag": np.sqrt(power.astype(np.float64))}
+    return out
 
 
 def live_frames(n_samples: int) -> int:

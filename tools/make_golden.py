@@ -82,6 +82,38 @@ def make_logmel():
     print("logmel.npz", {k: v.shape for k, v in out.items()})
 
 
+def logmel_like_cols(n_samples):
+    """The frames of an item that logmel_like.npz keeps: 0..104 of a 1 s item; of a longer one every 37th, the ten around
+    the last live frame and the last ten of the buffer (the right reflect edge)."""
+    live = min(3000, -(-(n_samples + 200) // 160))
+    if live + 3 <= 105:
+        return np.arange(105)
+    edge = np.arange(max(0, live - 7), min(3000, live + 3))
+    return np.unique(np.concatenate([np.arange(0, 3000, 37), edge, np.arange(2990, 3000)]))
+
+
+def make_logmel_like():
+    """The HF extractor on the band-limited families of tests/logmel_like.py, 80 and 128 mel bins."""
+    from tests import logmel_like as ll
+    out = {}
+    for n_mels in ll.N_MELS:
+        fe = WhisperFeatureExtractor(feature_size=n_mels)
+        for family in ll.FAMILIES:
+            for b, wave in enumerate(ll.batches(family)):
+                f = fe([w for w in wave], sampling_rate=16000, return_tensors="np").input_features
+                assert f.shape == (wave.shape[0], n_mels, 3000)
+                cols = logmel_like_cols(wave.shape[1])
+                key = f"{family}_m{n_mels}_b{b}"
+                out[key + "_frames"] = f[:, :, cols].astype(np.float32)
+                out[key + "_pad_value"] = f[:, 0, 2999].astype(np.float32)
+                if wave.shape[1] != ll.N:
+                    out[key + "_cols"] = cols
+    np.savez_compressed(os.path.join(GOLD, "logmel_like.npz"), **out)
+    size = os.path.getsize(os.path.join(GOLD, "logmel_like.npz"))
+    print("logmel_like.npz", len(out), "arrays,", size, "bytes")
+    assert size < 1 << 20
+
+
 def make_encoder_small():
     """Reduced config (d=128, H=2, L=2, ffn=512): per-stage activations on selected rows."""
     d, L, H, ffn = 128, 2, 2, 512
@@ -341,8 +373,9 @@ def make_config4():
 if __name__ == "__main__":
     os.makedirs(GOLD, exist_ok=True)
     torch.manual_seed(0)
-    which = sys.argv[1:] or ["logmel", "encoder_small", "config1", "adapter_schema", "inference_host", "config4"]
+    which = sys.argv[1:] or ["logmel", "logmel_like", "encoder_small", "config1", "adapter_schema", "inference_host",
+                             "config4"]
     for w in which:
-        {"logmel": make_logmel, "encoder_small": make_encoder_small, "config1": make_config1,
+        {"logmel": make_logmel, "logmel_like": make_logmel_like, "encoder_small": make_encoder_small, "config1": make_config1,
          "adapter_schema": make_adapter_schema, "inference_host": make_inference_host,
          "config4": make_config4}[w]()
