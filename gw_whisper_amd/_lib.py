@@ -242,6 +242,16 @@ SIGNATURES = {
     "gww_roc_band_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gww_binary_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_long, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gww_score_sort_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_score_sort_f64": (C.c_int, [C.c_void_p, C.c_long] + [C.c_void_p] * 5 + [C.c_size_t, C.c_void_p]),
+    "gww_score_closest_f64": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gww_score_match_workspace_bytes": (C.c_size_t, [C.c_long, C.c_long]),
+    "gww_score_match_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long] + [C.c_void_p] * 13
+                            + [C.c_size_t, C.c_void_p]),
+    "gww_score_far_f64": (C.c_int, [C.c_void_p, C.c_long, C.c_double, C.c_void_p, C.c_void_p]),
+    "gww_score_suffix_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 6),
+    "gww_score_volume_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_double, C.c_double]
+                             + [C.c_void_p] * 7),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

@@ -1187,3 +1187,142 @@ def binary_eval_accumulate(logits, labels, scores, offset: int, loss_sum, batche
         check(lib().gww_binary_eval_accumulate(logits.data_ptr(), labels.data_ptr(), B, scores.data_ptr(), int(offset),
                                                scores.numel(), loss_sum.data_ptr(), batches.data_ptr(), confusion.data_ptr(),
                                                _stream()), "gww_binary_eval_accumulate")
+
+
+# ---- scoring a search: false-alarm rate and sensitive volume (csrc/score.hip) -------------------------------------------
+SCORE_MAX_N = 1 << 27
+
+
+def _score_count(n_dev, who):
+    if n_dev is None:
+        return 0
+    _state(n_dev, torch.int32, (1,), who, "the device count")
+    return n_dev.data_ptr()
+
+
+def score_sort(keys, n_dev=None, ws=None):
+    """Stable ascending sort of fp64 keys [n], 1 <= n <= 2^27, on the device (``gww_score_sort_f64``, no host sync).
+    ``n_dev`` int32 [1] on the device: sort the first ``n_dev[0]`` keys only.  Returns (order int32 [n] =
+    ``np.argsort(keys, kind="stable")``, sorted fp64 [n], n_nan int32 [1])."""
+    keys = _dev(keys, torch.float64, "keys")
+    n = keys.numel()
+    if keys.dim() != 1 or not 1 <= n <= SCORE_MAX_N:
+        raise _lib.GwwError(f"score_sort: keys must be [n] with 1 <= n <= 2^27, got {tuple(keys.shape)}")
+    dev = keys.device
+    cnt = _score_count(n_dev, "score_sort")
+    ws = _roc_ws(ws, lib().gww_score_sort_workspace_bytes(n), dev, "score_sort")
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    out = torch.empty((n,), dtype=torch.float64, device=dev)
+    n_nan = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_score_sort_f64(keys.data_ptr(), n, cnt, out.data_ptr(), order.data_ptr(), n_nan.data_ptr(),
+                                       ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "gww_score_sort_f64")
+    return order, out, n_nan
+
+
+def score_closest(tc, t):
+    """``find_closest_index`` of the values t fp64 [n] in the ascending tc fp64 [N] (``gww_score_closest_f64``, one launch,
+    no host sync).  Returns (idx int32 [n], diff fp64 [n] = |tc[idx] - t|)."""
+    tc = _dev(tc, torch.float64, "tc")
+    t = _dev(t, torch.float64, "t")
+    if tc.dim() != 1 or t.dim() != 1 or not 1 <= tc.numel() <= SCORE_MAX_N or not 1 <= t.numel() <= SCORE_MAX_N:
+        raise _lib.GwwError("score_closest: tc must be [N] and t [n] with 1 <= N, n <= 2^27")
+    idx = torch.empty((t.numel(),), dtype=torch.int32, device=t.device)
+    diff = torch.empty((t.numel(),), dtype=torch.float64, device=t.device)
+    with torch.cuda.device(t.device):
+        check(lib().gww_score_closest_f64(tc.data_ptr(), tc.numel(), t.data_ptr(), t.numel(), idx.data_ptr(), diff.data_ptr(),
+                                          _stream()), "gww_score_closest_f64")
+    return idx, diff
+
+
+def score_match(events, order, tc, ws=None):
+    """Events against injections (``gww_score_match_f64``, no host sync): events fp64 [3, E] (time, stat, var), order int32
+    [E] from ``score_sort(events[0])``, tc fp64 [N] ascending.  Returns a dict of device tensors: ``fg_sorted`` [3, E],
+    ``found_idx`` [E], ``tp_idx`` / ``fp_idx`` [E], ``tp_diff`` / ``fp_diff`` [E], ``tp_events`` / ``fp_events`` [3, E],
+    ``found_inj`` / ``found_stat`` / ``missed`` [N] and ``counts`` int32 [5] = (true positives, false positives, found,
+    missed, events with a NaN): the leading ``counts`` entries (columns) of the compacted buffers are written."""
+    events = _dev(events, torch.float64, "events")
+    order = _dev(order, torch.int32, "order")
+    tc = _dev(tc, torch.float64, "tc")
+    if events.dim() != 2 or events.shape[0] != 3 or not 1 <= events.shape[1] <= SCORE_MAX_N:
+        raise _lib.GwwError(f"score_match: events must be [3, E] with 1 <= E <= 2^27, got {tuple(events.shape)}")
+    E, N = events.shape[1], tc.numel()
+    if tuple(order.shape) != (E,) or tc.dim() != 1 or not 1 <= N <= SCORE_MAX_N:
+        raise _lib.GwwError(f"score_match: order must be [E = {E}] and tc [N] with 1 <= N <= 2^27")
+    dev = events.device
+    ws = _roc_ws(ws, lib().gww_score_match_workspace_bytes(E, N), dev, "score_match")
+    f64, i32 = torch.float64, torch.int32
+    r = {"fg_sorted": torch.empty((3, E), dtype=f64, device=dev), "found_idx": torch.empty((E,), dtype=i32, device=dev),
+         "tp_idx": torch.empty((E,), dtype=i32, device=dev), "fp_idx": torch.empty((E,), dtype=i32, device=dev),
+         "tp_diff": torch.empty((E,), dtype=f64, device=dev), "fp_diff": torch.empty((E,), dtype=f64, device=dev),
+         "tp_events": torch.empty((3, E), dtype=f64, device=dev), "fp_events": torch.empty((3, E), dtype=f64, device=dev),
+         "found_inj": torch.empty((N,), dtype=i32, device=dev), "found_stat": torch.empty((N,), dtype=f64, device=dev),
+         "missed": torch.empty((N,), dtype=i32, device=dev), "counts": torch.empty((5,), dtype=i32, device=dev)}
+    with torch.cuda.device(dev):
+        check(lib().gww_score_match_f64(events.data_ptr(), order.data_ptr(), E, tc.data_ptr(), N, r["fg_sorted"].data_ptr(),
+                                        r["found_idx"].data_ptr(), r["tp_idx"].data_ptr(), r["fp_idx"].data_ptr(),
+                                        r["tp_diff"].data_ptr(), r["fp_diff"].data_ptr(), r["tp_events"].data_ptr(),
+                                        r["fp_events"].data_ptr(), r["found_inj"].data_ptr(), r["found_stat"].data_ptr(),
+                                        r["missed"].data_ptr(), r["counts"].data_ptr(), ws.data_ptr(),
+                                        ws.numel() * ws.element_size(), _stream()), "gww_score_match_f64")
+    return r
+
+
+def score_far(n: int, duration: float, device, n_dev=None):
+    """far fp64 [n] with far[k] = (m - k - 1) / duration for k < m (``gww_score_far_f64``, one launch, no host sync); m = n,
+    or the device's count ``n_dev`` int32 [1] (then m entries are written)."""
+    if not 1 <= int(n) <= SCORE_MAX_N:
+        raise _lib.GwwError(f"score_far: n={n} must be 1..2^27")
+    cnt = _score_count(n_dev, "score_far")
+    far = torch.empty((int(n),), dtype=torch.float64, device=device)
+    with torch.cuda.device(far.device):
+        check(lib().gww_score_far_f64(cnt, int(n), float(duration), far.data_ptr(), _stream()), "gww_score_far_f64")
+    return far
+
+
+def score_suffix(w1, w2, found_inj, order, F):
+    """Suffix sums of the per-injection weights w1, w2 fp64 [N] gathered in found-statistic order
+    (``gww_score_suffix_f64``, one workgroup, no host sync): found_inj, order int32 [N], F int32 [1] on the device.
+    Returns (cs1, cs2) fp64 [N + 1] of which F + 1 entries are written, cs[F] = 0."""
+    w1 = _dev(w1, torch.float64, "w1")
+    w2 = _dev(w2, torch.float64, "w2")
+    found_inj = _dev(found_inj, torch.int32, "found_inj")
+    order = _dev(order, torch.int32, "order")
+    N = w1.numel()
+    if w1.dim() != 1 or not 1 <= N <= SCORE_MAX_N or any(tuple(t.shape) != (N,) for t in (w2, found_inj, order)):
+        raise _lib.GwwError("score_suffix: w1, w2, found_inj and order must be [N] with 1 <= N <= 2^27")
+    _state(F, torch.int32, (1,), "score_suffix", "F")
+    cs1 = torch.empty((N + 1,), dtype=torch.float64, device=w1.device)
+    cs2 = torch.empty((N + 1,), dtype=torch.float64, device=w1.device)
+    with torch.cuda.device(w1.device):
+        check(lib().gww_score_suffix_f64(w1.data_ptr(), w2.data_ptr(), N, found_inj.data_ptr(), order.data_ptr(), F.data_ptr(),
+                                         cs1.data_ptr(), cs2.data_ptr(), _stream()), "gww_score_suffix_f64")
+    return cs1, cs2
+
+
+def score_volume(found_sorted, F, noise_sorted, n_inj: float, prefactor: float, cs1=None, cs2=None):
+    """Per ascending background statistic (``gww_score_volume_f64``, one launch, no host sync): found_sorted fp64 [N] of
+    which F (int32 [1], device) entries count, noise_sorted fp64 [B].  Returns (nfound int64 [B], fraction, volume,
+    volume_err fp64 [B]); with cs1, cs2 from ``score_suffix`` the chirp-mass-weighted form."""
+    found_sorted = _dev(found_sorted, torch.float64, "found_sorted")
+    noise_sorted = _dev(noise_sorted, torch.float64, "noise_sorted")
+    N, B = found_sorted.numel(), noise_sorted.numel()
+    if found_sorted.dim() != 1 or noise_sorted.dim() != 1 or not 1 <= N <= SCORE_MAX_N or not 1 <= B <= SCORE_MAX_N:
+        raise _lib.GwwError("score_volume: found_sorted must be [N] and noise_sorted [B] with 1 <= N, B <= 2^27")
+    _state(F, torch.int32, (1,), "score_volume", "F")
+    if (cs1 is None) != (cs2 is None):
+        raise _lib.GwwError("score_volume: cs1 and cs2 come together")
+    if cs1 is not None:
+        _state(cs1, torch.float64, (N + 1,), "score_volume", "cs1")
+        _state(cs2, torch.float64, (N + 1,), "score_volume", "cs2")
+    dev = noise_sorted.device
+    nfound = torch.empty((B,), dtype=torch.int64, device=dev)
+    frac = torch.empty((B,), dtype=torch.float64, device=dev)
+    vol = torch.empty((B,), dtype=torch.float64, device=dev)
+    err = torch.empty((B,), dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_score_volume_f64(found_sorted.data_ptr(), F.data_ptr(), N, noise_sorted.data_ptr(), B, float(n_inj),
+                                         float(prefactor), 0 if cs1 is None else cs1.data_ptr(),
+                                         0 if cs2 is None else cs2.data_ptr(), nfound.data_ptr(), frac.data_ptr(),
+                                         vol.data_ptr(), err.data_ptr(), _stream()), "gww_score_volume_f64")
+    return nfound, frac, vol, err

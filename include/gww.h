@@ -733,6 +733,50 @@ int gww_roc_band_f64(const double* tpr, const unsigned char* valid, long R, int 
  * probability of exactly 0.5 is class 0.  B 1..65536. */
 int gww_binary_eval_accumulate(const float* logits, const float* labels, int B, float* scores, long offset, long capacity,
                                double* loss_sum, long long* batches, long long* confusion, void* stream);
+/* ---- scoring a search: false-alarm rate and sensitive volume (csrc/score.hip) ----
+ * The counterpart of MLGWSC-1/evaluate.py: get_stats.  Device pointers throughout, plain launches, no host
+ * synchronisation; identical calls give identical bits.  Every count (events E, injections N, background events B, sort
+ * elements n) is 1..2^27; more is refused before any launch, and so is a workspace smaller than its *_workspace_bytes
+ * function says.  Where a function takes a count from the device (an int32 pointer), it clamps it into 0..capacity. */
+/* Stable ascending sort of fp64 keys (LSD radix sort, eight 8-bit digits over the order-preserving 64-bit image; -0.0
+ * and +0.0 are one value, +-inf ordinary values, NaNs sort last): order [n] int32 = np.argsort(keys, kind="stable"),
+ * sorted [n] fp64 = keys[order]; n_nan int32 [1] = the number of NaN keys.  n_dev: NULL, or the device's element count
+ * m <= n: then the first m keys are sorted and only the first m entries of order and sorted are written.  ws 16-byte
+ * aligned. */
+size_t gww_score_sort_workspace_bytes(long n);
+int gww_score_sort_f64(const double* keys, long n, const int* n_dev, double* sorted, int* order, int* n_nan, void* ws,
+                       size_t ws_bytes, void* stream);
+/* find_closest_index (evaluate.py:66-97) of n values t in the ascending array tc [N]: idx [n] int32 -- an exact midpoint
+ * goes to the right neighbour -- and diff [n] fp64 = |tc[idx] - t|. */
+int gww_score_closest_f64(const double* tc, long N, const double* t, long n, int* idx, double* diff, void* stream);
+/* Events against injections (evaluate.py:152-217).  events [3, E] fp64 (rows time, stat, var), order [E] int32 = the
+ * stable argsort of the times, tc [N] fp64 ascending.  Written: fg_sorted [3, E] = events[:, order]; found_idx [E] int32 =
+ * the closest injection of every sorted event; an event is a true positive iff |tc[found_idx] - time| <= var; tp_idx /
+ * fp_idx [E] int32, tp_diff / fp_diff [E] fp64, tp_events / fp_events [3, E] fp64 (row pitch E): the sorted positions, the
+ * |dt| and the events of the true / false positives in order, counts[0] / counts[1] entries (columns) of each;
+ * found_inj [N] int32, found_stat [N] fp64: the injections whose run of events holds a true positive and the largest
+ * statistic among those, in index order, counts[2] entries; missed [N] int32: the injections no event is closest to,
+ * counts[3] entries.  counts int32 [5]: true positives, false positives, found, missed, and the number of events with a
+ * NaN in time, stat or var (the caller refuses those).  ws 16-byte aligned. */
+size_t gww_score_match_workspace_bytes(long E, long N);
+int gww_score_match_f64(const double* events, const int* order, long E, const double* tc, long N, double* fg_sorted,
+                        int* found_idx, int* tp_idx, int* fp_idx, double* tp_diff, double* fp_diff, double* tp_events,
+                        double* fp_events, int* found_inj, double* found_stat, int* missed, int* counts, void* ws,
+                        size_t ws_bytes, void* stream);
+/* far[k] = (m - k - 1) / duration for k < m (evaluate.py:185-186, 193-194); m = n, or the device's count n_dev[0] <= n. */
+int gww_score_far_f64(const int* n_dev, long n, double duration, double* far, void* stream);
+/* Chirp-mass weighting (evaluate.py:250-263): cs1[p] = the sum of w1[found_inj[order[q]]] over q = p .. F - 1, cs2 the
+ * same of w2, cs[F] = 0; F = F[0] on the device, w1, w2 [N] fp64 per injection, found_inj and order [N] int32, cs1 and
+ * cs2 [N + 1] fp64 of which F + 1 entries are written.  One workgroup; the additions happen in one fixed order. */
+int gww_score_suffix_f64(const double* w1, const double* w2, long N, const int* found_inj, const int* order, const int* F,
+                         double* cs1, double* cs2, void* stream);
+/* Per ascending background statistic (evaluate.py:244-276): fidx = searchsorted(found_sorted[:F], noise, 'right'),
+ * nfound (int64) = F - fidx, fraction = nfound / Ninj; cs1 == cs2 == NULL: volume = prefactor * nfound, variance =
+ * fraction - fraction^2; otherwise volume = prefactor * cs1[fidx], variance = cs2[fidx] / Ninj - (cs1[fidx] / Ninj)^2;
+ * volume_err = prefactor * sqrt(Ninj * variance).  found_sorted [N] fp64 of which F[0] (device) entries are read. */
+int gww_score_volume_f64(const double* found_sorted, const int* F, long N, const double* noise_sorted, long B, double Ninj,
+                         double prefactor, const double* cs1, const double* cs2, long long* nfound, double* fraction,
+                         double* volume, double* volume_err, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
