@@ -104,7 +104,9 @@ class GWWhisperClassifier(nn.Module):
             nn.Linear(hidden * n_detectors, 512), nn.ReLU(), nn.Linear(512, 256), nn.ReLU(), nn.Linear(256, 128),
             nn.ReLU(), nn.Linear(128, 64), nn.ReLU(), nn.Linear(64, num_classes), nn.Softmax(dim=1))
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def embed(self, x: torch.Tensor) -> torch.Tensor:
+        """The pooled token of every detector, ``[B, D, d]``: everything in front of the head.  Adapter and encoder run
+        per detector, so these tokens are also what a time slide pairs up (``time_slides.py``)."""
         feats = self.adapter(x)                                   # [B, D, 80, 3000]
         B, D = feats.shape[:2]
         flat = feats.reshape(B * D, *feats.shape[2:])
@@ -113,8 +115,12 @@ class GWWhisperClassifier(nn.Module):
         else:
             seq = self.encoder(flat).last_hidden_state
             tok = seq[:, -1, :] if self.use_last_token else seq.mean(dim=1)
-        combined = tok.reshape(B, D * tok.shape[-1])              # == cat of the per-detector tokens
-        return self.classifier(combined)
+        return tok.reshape(B, D, tok.shape[-1])
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        tok = self.embed(x)
+        B, D, d = tok.shape
+        return self.classifier(tok.reshape(B, D * d))             # == cat of the per-detector tokens
 
 
 def remove_softmax_from_classifier(model: GWWhisperClassifier) -> None:
@@ -188,20 +194,34 @@ class DeviceSegmentSlicer:
 def evaluate_slices(slicer: DeviceSegmentSlicer, network: nn.Module, device: str = "cuda",
                     trigger_threshold: float = 0.2, verbose: bool = False,
                     batch_size: int = 256, window_range: Optional[Tuple[int, int]] = None,
-                    cluster_threshold: Optional[float] = None):
+                    cluster_threshold: Optional[float] = None, return_tokens: bool = False):
     """Reference ``evaluate_slices`` (``inference.py:454-489``): run ``network`` over all windows in batches of 256,
     keep ``outputs[:, 0]`` as the signal score, return ``([[time, score], ...] above threshold, [scores per batch])``.
     Scores and times stay on the device; the threshold is one comparison + ``nonzero`` and everything leaves the
     GPU in two copies per segment instead of one ``.item()`` per window.  ``window_range``: evaluate only windows
     ``[w0, w1)`` (a rank's batch-aligned shard).  ``cluster_threshold``: also cluster the triggers of these windows on the
-    device (``cluster_triggers_device``) and return ``(triggers, scores per batch, (times, values, variances))``."""
+    device (``cluster_triggers_device``) and return ``(triggers, scores per batch, (times, values, variances))``.
+    ``return_tokens``: the network is a ``GWWhisperClassifier``; also return, as the last element, the pooled tokens of
+    these windows ``[n, D, d]`` fp32 on the device (what ``time_slides`` pairs up) -- the network runs as the same two
+    steps ``classifier(embed(x))`` its ``forward`` is, so every other result is what it is without the flag."""
     w0, w1 = (0, len(slicer)) if window_range is None else window_range      # one rank's shard (shard_windows)
     n = w1 - w0
     scores = torch.empty((n,), dtype=torch.float32, device=slicer.dss.device)
+    if return_tokens and not (hasattr(network, "embed") and hasattr(network, "classifier")):
+        raise _lib.GwwError("evaluate_slices: return_tokens needs a network with embed() and classifier (GWWhisperClassifier)")
+    tokens = None
     with torch.no_grad():
         for i0 in range(0, n, batch_size):
             i1 = min(n, i0 + batch_size)
-            out = network(slicer.windows(w0 + i0, w0 + i1).contiguous())
+            x = slicer.windows(w0 + i0, w0 + i1).contiguous()
+            if return_tokens:
+                tok = network.embed(x)
+                if tokens is None:
+                    tokens = torch.empty((n, *tok.shape[1:]), dtype=torch.float32, device=slicer.dss.device)
+                tokens[i0:i1] = tok
+                out = network.classifier(tok.reshape(tok.shape[0], -1))
+            else:
+                out = network(x)
             scores[i0:i1] = out[:, 0].to(torch.float32)
         keep = torch.nonzero(scores > trigger_threshold).flatten()
         times = slicer.times(w0, w1)
@@ -211,7 +231,8 @@ def evaluate_slices(slicer: DeviceSegmentSlicer, network: nn.Module, device: str
                                                                                   cluster_threshold)
     new_triggers = [[float(t), float(s)] for t, s in trig]
     all_vals = [all_scores[i0:min(n, i0 + batch_size)] for i0 in range(0, n, batch_size)]
-    return (new_triggers, all_vals) if cluster_threshold is None else (new_triggers, all_vals, clusters)
+    ret = (new_triggers, all_vals) if cluster_threshold is None else (new_triggers, all_vals, clusters)
+    return ret + (tokens,) if return_tokens else ret
 
 
 def cluster_triggers_device(times: torch.Tensor, scores: torch.Tensor, trigger_threshold: float = 0.2,

@@ -1005,6 +1005,72 @@ def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
     return out
 
 
+SLIDE_LOGIT0, SLIDE_PROB0 = 0, 1
+SLIDE_WIDTHS = (256, 128, 64)      # layers 2..5 of the search head behind its 512-wide first layer
+SLIDE_MAX_D, SLIDE_MAX_S = 4, 65535
+
+
+def slide_scores(partials, params, offsets, mode: int = SLIDE_LOGIT0, out=None):
+    """Scores of time-slid detector pairs (``gww_slide_scores_f32``, one launch): ``partials`` fp32 [D, N, 512], the first
+    layer's per-detector partial products (bias in detector 0); ``params`` the eight tensors (w2, b2, ..., w5, b5) of
+    layers 2..5; ``offsets`` the S window offsets (python ints, checked here: 0 <= o < N).  Returns fp32 [S, N] with
+    row s = the head on ``relu(sum_g partials[g][(i + g * offsets[s]) mod N])``: ``z[0]`` (SLIDE_LOGIT0) or
+    ``softmax(z)[0]`` (SLIDE_PROB0).  ``out``: a contiguous fp32 [S, N] GPU tensor to write instead of a new one."""
+    partials = _dev(partials, torch.float32, "partials")
+    if partials.dim() != 3 or partials.shape[2] != 512 or partials.shape[1] < 1:
+        raise _lib.GwwError(f"slide_scores: partials must be [D, N >= 1, 512], got {tuple(partials.shape)}")
+    D, N = int(partials.shape[0]), int(partials.shape[1])
+    if not 2 <= D <= SLIDE_MAX_D:
+        raise _lib.GwwError(f"slide_scores: D={D} detectors; time slides need 2..{SLIDE_MAX_D}")
+    ps, d_in, C = _mlp_params(params, SLIDE_WIDTHS, "slide_scores", "slide head")
+    if d_in != 512:
+        raise _lib.GwwError(f"slide_scores: w2 must be [256, 512], got {tuple(ps[0].shape)}")
+    if mode not in (SLIDE_LOGIT0, SLIDE_PROB0):
+        raise _lib.GwwError(f"slide_scores: mode={mode} must be SLIDE_LOGIT0 or SLIDE_PROB0")
+    if mode == SLIDE_PROB0 and C < 2:
+        raise _lib.GwwError("slide_scores: the softmax score needs C >= 2 classes")
+    offs = [int(o) for o in offsets]
+    if not 1 <= len(offs) <= SLIDE_MAX_S:
+        raise _lib.GwwError(f"slide_scores: {len(offs)} offsets, must be 1..{SLIDE_MAX_S}")
+    if any(o < 0 or o >= N for o in offs):
+        raise _lib.GwwError(f"slide_scores: every offset must be in [0, N = {N})")
+    S = len(offs)
+    if out is None:
+        out = torch.empty((S, N), dtype=torch.float32, device=partials.device)
+    elif not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (S, N) or not out.is_contiguous():
+        raise _lib.GwwError(f"slide_scores: out must be a contiguous fp32 GPU tensor of [{S}, {N}]")
+    offs_d = torch.tensor(offs, dtype=torch.int64).to(partials.device)
+    with torch.cuda.device(partials.device):
+        check(lib().gww_slide_scores_f32(partials.data_ptr(), *[t.data_ptr() for t in ps], offs_d.data_ptr(), N, D, S, C,
+                                         int(mode), out.data_ptr(), _stream()), "gww_slide_scores_f32")
+    return out
+
+
+def cluster_slides(times, scores, trigger_threshold: float, cluster_threshold: float, cap: int | None = None):
+    """``get_clusters`` of every row of ``scores`` fp32 [S, N] against the shared fp64 stamps ``times`` [N]
+    (``gww_cluster_slides_f64``, one launch, one wave per slide; no host sync).  Returns (out_t fp64 [S, cap], out_v fp32
+    [S, cap], count int32 [S]); a count above ``cap`` (default N, which cannot overflow) means that slide's list was cut."""
+    times = _dev(times, torch.float64, "times")
+    scores = _dev(scores, torch.float32, "scores")
+    if scores.dim() != 2 or scores.shape[1] < 1 or times.shape != (scores.shape[1],):
+        raise _lib.GwwError(f"cluster_slides: scores must be [S, N >= 1] and times [N], got {tuple(scores.shape)} and "
+                            f"{tuple(times.shape)}")
+    S, N = int(scores.shape[0]), int(scores.shape[1])
+    if not 1 <= S <= SLIDE_MAX_S:
+        raise _lib.GwwError(f"cluster_slides: S={S} slides, must be 1..{SLIDE_MAX_S}")
+    cap = N if cap is None else int(cap)
+    if cap < 1:
+        raise _lib.GwwError(f"cluster_slides: cap={cap} must be >= 1")
+    out_t = torch.empty((S, cap), dtype=torch.float64, device=scores.device)
+    out_v = torch.empty((S, cap), dtype=torch.float32, device=scores.device)
+    cnt = torch.empty((S,), dtype=torch.int32, device=scores.device)
+    with torch.cuda.device(scores.device):
+        check(lib().gww_cluster_slides_f64(times.data_ptr(), scores.data_ptr(), N, S, float(trigger_threshold),
+                                           float(cluster_threshold), out_t.data_ptr(), out_v.data_ptr(), cnt.data_ptr(), cap,
+                                           _stream()), "gww_cluster_slides_f64")
+    return out_t, out_v, cnt
+
+
 def det_eval_accumulate(probs, targets, row_loss, correct, loss_sum, n, batches):
     """One batch into the device-resident evaluation state (``gww_det_eval_accumulate``, one launch, no host sync):
     correct int64 [1], loss_sum fp64 [1] (sum of the batches' mean losses), n int64 [1], batches int64 [1]."""

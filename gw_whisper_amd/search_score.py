@@ -102,10 +102,13 @@ def _events(ev, name, device=None):
     return torch.from_numpy(np.ascontiguousarray(ev)).to(device if device is not None else "cuda")
 
 
-def get_stats(fgevents, bgevents, injparams, duration=None, chirp_distance=False):
+def get_stats(fgevents, bgevents, injparams, duration=None, chirp_distance=False, background_duration=None):
     """``get_stats`` of the reference (``evaluate.py:104-278``): fgevents, bgevents [3, n] (time, stat, var) as numpy or
     CUDA fp64 tensors, injparams a dict of numpy arrays with ``tc`` (ascending), ``distance`` and, for
-    ``chirp_distance``, ``mass1`` / ``mass2``.  Returns the reference's sixteen keys as numpy arrays (integers int64)."""
+    ``chirp_distance``, ``mass1`` / ``mass2``.  Returns the reference's sixteen keys as numpy arrays (integers int64).
+    ``background_duration``: the seconds of background the events in ``bgevents`` were found in, when that is not the
+    foreground's ``duration`` (time slides, ``time_slides.py``): ``far`` is counted per that time; ``fg-far`` and every
+    other key keep ``duration``."""
     tc = _ascending(injparams["tc"], "get_stats")
     dist = np.asarray(injparams["distance"], np.float64)
     N = tc.size
@@ -121,6 +124,8 @@ def get_stats(fgevents, bgevents, injparams, duration=None, chirp_distance=False
         raise GwwError("get_stats: no foreground events")
     if duration is None:
         duration = tc.max() - tc.min()
+    if background_duration is not None and not float(background_duration) > 0:
+        raise GwwError(f"get_stats: background_duration={background_duration} must be positive")
     # the scalars and per-injection weights, in the reference's own expressions (evaluate.py:233-242, 256-261)
     max_distance = dist.max()
     vtot = (4. / 3.) * np.pi * max_distance**3.
@@ -146,7 +151,7 @@ def get_stats(fgevents, bgevents, injparams, duration=None, chirp_distance=False
     nan_b = None
     if B > 0:
         _, noise, nan_b = ops.score_sort(bg[1])
-        far = ops.score_far(B, duration, dev)
+        far = ops.score_far(B, duration if background_duration is None else float(background_duration), dev)
         cs1 = cs2 = None
         if chirp_distance:
             cs1, cs2 = ops.score_suffix(w1, w2, m["found_inj"], f_order, n_found)

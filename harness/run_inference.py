@@ -18,6 +18,12 @@ the offline box:
   * the weights are optional (seeded random parameters without them -- there is no network for checkpoints);
     ``--encoder`` / ``--encoder-weights`` choose the base encoder the adapters were trained on (the reference loads
     ``openai/whisper-tiny`` from the hub).
+
+``--time-slides S --slide-shift SECONDS --slides-output FILE`` (one rank only) adds the search background from S time
+slides per segment: still one encoder pass, the head scored per slide on shifted pairs of the detectors' pooled tokens
+(``gw_whisper_amd/time_slides.py``).  The zero-lag output is what it is without the flag; FILE holds ``time``, ``stat``,
+``var`` as ``run_search_evaluate.py --background-events`` reads them, plus ``slide`` (int32 per event),
+``slide_livetime`` [S] and ``livetime`` (their sum, the background's duration in seconds).
 """
 from __future__ import annotations
 
@@ -61,6 +67,10 @@ def parse_args(argv=None):
     p.add_argument("--encoder-weights", type=str, default=None, help="HF WhisperEncoder state_dict (.pth / .safetensors).")
     p.add_argument("--batch-size", type=int, default=256)
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--time-slides", type=int, default=0,
+                   help="Number of time slides of background per segment (0: none; nothing changes).")
+    p.add_argument("--slide-shift", type=float, default=2.0, help="Seconds between two slides (a whole number of steps).")
+    p.add_argument("--slides-output", type=str, default=None, help="Output file of the slid background events.")
     return p.parse_args(argv)
 
 
@@ -168,6 +178,8 @@ def get_triggers(args, device, rank, world):
     else:
         segs = read_segments(args.inputfile)
     triggers, all_vals, clusters = {}, [], {}
+    S = args.time_slides
+    slid, slide_live = {}, np.zeros((max(S, 0),), np.float64)
     for key in sorted(segs, key=lambda k: segs[k][0].shape[1], reverse=True):
         strain, start, dt = segs[key]
         # --white: the file already holds whitened strain; otherwise every segment is whitened on the device first
@@ -176,7 +188,19 @@ def get_triggers(args, device, rank, world):
                                          device=device, white=args.white)
         w0, w1 = inf.shard_windows(len(slicer), rank, world, args.batch_size)
         logging.info("rank %d: segment %s, windows [%d, %d) of %d", rank, key, w0, w1, len(slicer))
-        if world == 1:
+        if world == 1 and S > 0:
+            # the same pass also hands out the pooled tokens; the slides are the head's response to shifted pairs of them
+            from gw_whisper_amd import time_slides as ts
+            trig, vals, clusters[key], tokens = inf.evaluate_slices(
+                slicer, network, trigger_threshold=args.trigger_threshold, batch_size=args.batch_size, window_range=(w0, w1),
+                cluster_threshold=args.cluster_threshold, return_tokens=True)
+            plan = ts.slide_plan(len(slicer), args.step_size, args.slide_shift, S, slicer.slice_length * slicer.delta_t,
+                                 slicer.time_step_size)
+            slid[key] = ts.slide_background(slicer, tokens, network.classifier, plan, args.trigger_threshold,
+                                            args.cluster_threshold)
+            slide_live += plan.livetime
+            del tokens
+        elif world == 1:
             # one GPU holds every score of the segment: threshold AND cluster on the device (gww_cluster_triggers_f64)
             trig, vals, clusters[key] = inf.evaluate_slices(slicer, network, trigger_threshold=args.trigger_threshold,
                                                             batch_size=args.batch_size, window_range=(w0, w1),
@@ -196,7 +220,12 @@ def get_triggers(args, device, rank, world):
     keys = sorted(triggers)
     clustered = tuple(np.concatenate([clusters[k][j] for k in keys]) if keys and all(k in clusters for k in keys) else None
                       for j in range(3))
-    return dict(sorted(triggers.items(), key=lambda x: x[0])), all_vals, clustered
+    slides = None
+    if S > 0:
+        cols = [np.concatenate([slid[k][j] for k in keys]) if keys else np.zeros((0,)) for j in range(4)]
+        slides = {"time": cols[0], "stat": cols[1], "var": cols[2], "slide": cols[3].astype(np.int32),
+                  "slide_livetime": slide_live, "livetime": np.float64(slide_live.sum())}
+    return dict(sorted(triggers.items(), key=lambda x: x[0])), all_vals, clustered, slides
 
 
 def main(argv=None) -> int:
@@ -209,6 +238,16 @@ def main(argv=None) -> int:
         raise RuntimeError("Output file exists. Use --force to overwrite.")
     if args.debug_triggers_file is not None and os.path.isfile(args.debug_triggers_file) and not args.force:
         raise RuntimeError("Triggers file exists. Use --force to overwrite.")
+    if args.time_slides < 0:
+        raise SystemExit("run_inference: --time-slides must be >= 0")
+    if args.time_slides > 0:
+        if args.slides_output is None:
+            raise SystemExit("run_inference: --time-slides needs --slides-output FILE")
+        if world > 1:
+            raise SystemExit("run_inference: --time-slides runs on one rank only (WORLD_SIZE > 1 is not supported); segments "
+                             "are independent, so split the input by segment instead")
+        if os.path.isfile(args.slides_output) and not args.force:
+            raise RuntimeError("Slides file exists. Use --force to overwrite.")
     if not torch.cuda.is_available():
         raise SystemExit("run_inference: no GPU -- gw_whisper_amd has no CPU fallback")
     device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0"))) if args.device == "cuda" else torch.device(args.device)
@@ -219,7 +258,7 @@ def main(argv=None) -> int:
         dist.init_process_group("nccl", device_id=device)
 
     from gw_whisper_amd import inference as inf
-    triggers, all_vals, clustered = get_triggers(args, device, rank, world)
+    triggers, all_vals, clustered, slides = get_triggers(args, device, rank, world)
     if rank == 0:
         logging.info("Total slices above threshold %.3f: %d", args.trigger_threshold, sum(len(v) for v in triggers.values()))
         if args.debug_triggers_file is not None:
@@ -229,6 +268,9 @@ def main(argv=None) -> int:
         time_arr, stat_arr, var_arr = clustered if clustered[0] is not None else inf.get_clusters(triggers, args.cluster_threshold)
         flat = np.concatenate(all_vals).astype("float32") if len(all_vals) else np.array([], dtype="float32")
         write_result(args.outputfile, {"time": time_arr, "stat": stat_arr, "var": var_arr, "all_vals": flat})
+        if slides is not None:
+            logging.info("%d slid background events in %.1f s of live time", len(slides["time"]), float(slides["livetime"]))
+            write_result(args.slides_output, slides)
         print(f"Total execution time: {t.time() - start:.2f} seconds")
         sys.stdout.flush()
     if world > 1:

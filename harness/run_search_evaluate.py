@@ -5,7 +5,9 @@ out, with the sorting, matching, counting and the volumes on the device (``gw_wh
 
 Same flags as the reference (``--injection-file --foreground-events --foreground-files --background-events --output-file
 --verbose --force``), the same 30 s padding at both ends of every segment, the same "contains no injections" error, the
-same refusal to overwrite without ``--force``, the same sixteen output datasets.  ``chirp_distance`` weighting is on when
+same refusal to overwrite without ``--force``, the same sixteen output datasets.  ``--background-duration SECONDS`` (or
+the ``livetime`` dataset of a single background file, which ``run_inference.py --slides-output`` writes) counts ``far``
+per that much background instead of the foreground's duration: a time-slide background is longer than the data.  ``chirp_distance`` weighting is on when
 the injection file has the ``chirp_distance`` key.  Files as ``run_inference.py`` reads and writes them, so its event
 files are accepted without conversion: HDF5 in the reference's layout when ``h5py`` is importable, otherwise the ``.npz``
 twin of the same layout (foreground files: ``<detector>/<key>`` arrays plus ``<key>/start_time`` and ``<key>/delta_t``
@@ -35,6 +37,10 @@ def parse_args(argv=None):
     p.add_argument("--foreground-files", type=str, nargs="+", required=True, help="The analysed foreground data files.")
     p.add_argument("--background-events", type=str, nargs="+", required=True, help="Events of the search on the background.")
     p.add_argument("--output-file", type=str, required=True, help="Output file (must end in .hdf, or .npz).")
+    p.add_argument("--background-duration", type=float, default=None,
+                   help="Seconds of background the background events were found in (default: the `livetime` dataset of a "
+                        "single background file, as run_inference.py --slides-output writes it; otherwise the foreground's "
+                        "duration, as in the reference).")
     p.add_argument("--verbose", action="store_true", help="Print update messages.")
     p.add_argument("--force", action="store_true", help="Overwrite existing files.")
     return p.parse_args(argv)
@@ -144,7 +150,14 @@ def main(argv=None) -> int:
     fg_events = read_events(args.foreground_events)
     logging.info("Reading background events from %s", args.background_events)
     bg_events = read_events(args.background_events)
-    stats = search_score.get_stats(fg_events, bg_events, injparams, duration=dur, chirp_distance=use_chirp_distance)
+    bg_dur = args.background_duration
+    if bg_dur is None and len(args.background_events) == 1:
+        live = read_arrays(args.background_events[0]).get("livetime")
+        if live is not None:
+            bg_dur = float(np.asarray(live).reshape(-1)[0])
+            logging.info("Background duration %.1f s from the livetime dataset of %s", bg_dur, args.background_events[0])
+    stats = search_score.get_stats(fg_events, bg_events, injparams, duration=dur, chirp_distance=use_chirp_distance,
+                                   background_duration=bg_dur)
     logging.info("Writing output to %s", output_path(args.output_file))
     write_result(args.output_file, stats)
     return 0

@@ -513,6 +513,28 @@ int gww_fir_f64(const double* xp, long xp_stride, const double* g, int taps4, in
 int gww_cluster_triggers_f64(const double* times, const float* scores, long n, float trigger_threshold,
                              double cluster_threshold, double* out_times, float* out_vals, int* out_count,
                              int max_clusters, void* stream);
+/* ---- search background from time slides (csrc/timeslide.hip) ----
+ * The detectors of the search model only meet in its head, whose first Linear splits over the concatenated tokens.
+ * P fp32 [D, N, 512]: the first layer's partial products per detector and window (P[g] = tok_g W1_g^T, the bias folded
+ * into detector 0); w2 [256, 512], w3 [128, 256], w4 [64, 128], w5 [C, 64] and their biases: layers 2..5 of the head;
+ * offsets int64 [S] on the device, each in [0, N) (the caller checks them before upload; the kernel reduces whatever
+ * arrives modulo N, so no index leaves P).  scores fp32 [S, N], every element written:
+ *   scores[s][i] = f(w5 relu(w4 relu(w3 relu(w2 relu(sum_g P[g][(i + g offsets[s]) mod N]) + b2) + b3) + b4) + b5)
+ * with f(z) = z[0] (mode 0, the head without its Softmax) or softmax(z)[0] (mode 1, C >= 2; fp64 on the fp32 logits,
+ * rounded once).  Detector 0 is never moved.  One launch, one workgroup per 16 consecutive windows of one slide; exact
+ * fp32 (v_mfma_f32_16x16x4_f32 chains), no atomics: identical calls give identical bits, and a slide's row does not
+ * depend on the other offsets of the launch.  N 1..2^31-1, D 2..4, S 1..65535, C 1..64; P, the weights and b2..b4
+ * 16-byte aligned. */
+int gww_slide_scores_f32(const float* P, const float* w2, const float* b2, const float* w3, const float* b3,
+                         const float* w4, const float* b4, const float* w5, const float* b5, const long long* offsets,
+                         long N, int D, int S, int C, int mode, float* scores, void* stream);
+/* gww_cluster_triggers_f64 over every row of scores [S, N] in one launch, one wave per slide; times fp64 [N] is shared.
+ * out_times fp64 / out_vals fp32 [S, max_clusters], out_count int32 [S] = the clusters found in each slide (may exceed
+ * max_clusters: only the first max_clusters of a slide are stored, so the caller sees an overflow).  Slides never share
+ * a cluster.  N 1..2^31-1, S 1..65535. */
+int gww_cluster_slides_f64(const double* times, const float* scores, long N, int S, float trigger_threshold,
+                           double cluster_threshold, double* out_times, float* out_vals, int* out_count,
+                           int max_clusters, void* stream);
 int gww_gemm_f32(const float* A, const float* W, const float* bias, const float* resid, float* C,
                  long M, int N, int K, int epilogue, void* stream);
 /* softmax(q k^T) v per head, q pre-scaled; qkv [B,T,3*d] (q|k|v), ctx [B,T,d]; head_dim 64 */
