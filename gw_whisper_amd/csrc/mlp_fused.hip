@@ -148,6 +148,14 @@ constexpr int MF_WAVES = 4, MF_THREADS = 256, MF_BM = 128;
                         // (1.2 GB of the launch's 4.0 GB at B = 256 and two exposed HBM round trips per panel), 96 LDS
                         // transposes per seam.  x_new is still written when the caller keeps it (training: x_mid).
 #endif
+#ifndef GWW_MF_CSPREAD
+#define GWW_MF_CSPREAD 1   // (XACC) 1: the out_proj GEMM starts on the first k-tile of ctx alone.  Loads and LDS-DMA retire in issue
+                           // order and the ring wait of tile i needs tile i + 1, which is requested in tile i - 2: whatever is
+                           // requested in front of the GEMM has to land within its first two tiles, however the waits are counted.
+                           // So the requests of k-tiles 1 .. 5 are ISSUED inside the GEMM, between the ring's pieces, three tiles
+                           // ahead of their first use -- the ring waits (with the riders added to their counts) then prove them
+                           // as they prove the tiles, and no wait is added.  0: all 24 requests and one full wait in front.
+#endif
 constexpr int MF_AHEAD = GWW_MF_AHEAD;   // tiles in flight ahead of the one being computed
 // Ring: AHEAD + 1 slots of one 16-KiB tile, one s_barrier per tile.  (One barrier per two tiles with one more slot was
 // built and measured in round 2: 1.154 vs 1.159 ms plain, 1.653 vs 1.653 ms with q/k/v -- no gain, removed.)
@@ -286,6 +294,14 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   static_assert(!X0 || (GWW_MF_NORM && GWW_MF_XACC && (MODE == 2 || (MODE == 1 && OP))), "X0: layer 0's two launches; stages in the u table");
   constexpr bool XACC = GWW_MF_XACC && GWW_MF_NORM && GWW_MF_SCHED && OP && (MODE == 1 || MODE == 3);
   constexpr bool XIN = (XL & 1) != 0, XOUT = (XL & 2) != 0;
+  // CSP (XACC): only the first k-tile of ctx is requested in the prologue; the other five ride in the out_proj GEMM, which
+  // runs k-tile major for that.  (With X0 too: the shared rows' fma then runs with 16 landing registers beside it, not 96 --
+  // with all 24 requests in flight hipcc copies a landing fragment out of its registers there, tools/audit_asm_loads.py.)
+  constexpr bool CSP = GWW_MF_CSPREAD && XACC;
+  // XPR (CSP without X0, whose shared rows' fma needs all of x first): the requests go x n-tile 0 | ctx k-tile 0 | x n-tiles 1, 2,
+  // and the GEMM starts on the first twenty of those 52 -- its k-tile major walk first touches the accumulators of n-tile nt
+  // in tile nt, and what stands in front of ring tile 3 (requested in tile 0) has to land by tile 2 in any case.
+  constexpr bool XPR = CSP && !X0 && !(GWW_MF_ABL & 32);
   // (not with X0: in <1, true, true> hipcc copies a landing ctx fragment out of its registers in front of the wait that covers
   // it as soon as the x_next stores change -- tools/audit_asm_loads.py; layer 0 behind the compact stem writes rows)
   static_assert(XL == 0 || (XACC && !GWW_MF_XLDS && !X0 && (!XOUT || MODE == 1) && XL <= 3), "XL: the accumulator-order stream of XACC");
@@ -348,9 +364,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   };
 
   MSTAMP_DECL
-  // the bias tables of the block -> LDS.  XACC: called BEHIND the x / ctx requests (below), so that their round trip -- a
-  // microsecond of L2 latency, plain loads hipcc waits for one by one -- runs under the panel's HBM round trip instead of in
-  // front of it; the first reader (the seam behind the out_proj GEMM) sits behind eighteen tile barriers
+  // the bias tables of the block -> LDS (XACC: request_tables() / publish_tables() below instead)
   auto stage_tables = [&]() {
     for (int i = tid; i < F; i += MF_THREADS) {
       lds_cb[i] = GWW_MF_SCHED ? ln_cb[i] * 0.125f : ln_cb[i];   // SCHED: the fc1 accumulators hold S / 8 (gelu_slice)
@@ -369,6 +383,60 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
       for (int i = tid; i < NQ; i += MF_THREADS) lds_qcb[i] = q_cb[i];
   };
   if constexpr (!XACC) stage_tables();
+  // XACC: the same tables as ONE batch of requests -- element tid + 256 k of each, the index clamped into the table, the store
+  // predicated -- issued between the ring's first tiles and the x requests and published behind the panel's wait.  (Left to
+  // hipcc, the run-time trip counts of stage_tables() became eight request / wait rounds, and behind the panel's requests
+  // -- loads retire in issue order -- only the first of them ran under the panel's round trip.)
+  constexpr int TB_CB = MF_FMAX / MF_THREADS, TB_D = (MF_D + MF_THREADS - 1) / MF_THREADS;
+  float tb_cb[TB_CB], tb_b2[TB_D], tb_bo[TB_D], tb_q[QKV ? TB_CB : TB_D], tb_qu[TB_D];
+  auto table_piece = [&](float& v, const float* p, int i, int n) {
+    const unsigned off = 4u * (unsigned)(i < n ? i : n - 1);
+    asm volatile("global_load_dword %0, %1, %2" : "=v"(v) : "v"(off), "s"(p) : "memory");
+  };
+  auto request_tables = [&]() {
+#pragma unroll
+    for (int k = 0; k < TB_CB; ++k) table_piece(tb_cb[k], ln_cb, tid + MF_THREADS * k, F);
+#pragma unroll
+    for (int k = 0; k < TB_D; ++k) { table_piece(tb_b2[k], b2, tid + MF_THREADS * k, MF_D); table_piece(tb_bo[k], bo, tid + MF_THREADS * k, MF_D); }
+    if constexpr (FIN) {
+#pragma unroll
+      for (int k = 0; k < TB_D; ++k) { table_piece(tb_qu[k], q_u, tid + MF_THREADS * k, MF_D); table_piece(tb_q[k], q_cb, tid + MF_THREADS * k, MF_D); }
+    }
+    if constexpr (QKV) {
+#pragma unroll
+      for (int k = 0; k < TB_CB; ++k) table_piece(tb_q[k], q_cb, tid + MF_THREADS * k, NQ);
+    }
+  };
+  // (call behind the wait that proves the requests; the first reader sits behind the out_proj GEMM's eighteen tile barriers)
+  auto publish_tables = [&]() {
+#pragma unroll
+    for (int k = 0; k < TB_CB; ++k) {
+      asm volatile("" : "+v"(tb_cb[k]));
+      if (tid + MF_THREADS * k < F) lds_cb[tid + MF_THREADS * k] = tb_cb[k] * 0.125f;   // the fc1 accumulators hold S / 8 (gelu_slice)
+    }
+#pragma unroll
+    for (int k = 0; k < TB_D; ++k) {
+      asm volatile("" : "+v"(tb_b2[k]), "+v"(tb_bo[k]));
+      if (tid + MF_THREADS * k < MF_D) {
+        lds_b2[tid + MF_THREADS * k] = tb_b2[k] + tb_bo[k];   // O holds x + ctx W_o^T + fc2, both biases are added when it is read
+        lds_bo[tid + MF_THREADS * k] = tb_bo[k];
+      }
+    }
+    if constexpr (FIN) {   // gain / bias of the encoder's final LayerNorm, in the unused u table
+#pragma unroll
+      for (int k = 0; k < TB_D; ++k) {
+        asm volatile("" : "+v"(tb_qu[k]), "+v"(tb_q[k]));
+        if (tid + MF_THREADS * k < MF_D) { lds_u[tid + MF_THREADS * k] = tb_qu[k]; lds_u[MF_D + tid + MF_THREADS * k] = tb_q[k]; }
+      }
+    }
+    if constexpr (QKV) {
+#pragma unroll
+      for (int k = 0; k < TB_CB; ++k) {
+        asm volatile("" : "+v"(tb_q[k]));
+        if (tid + MF_THREADS * k < NQ) lds_qcb[tid + MF_THREADS * k] = tb_q[k];
+      }
+    }
+  };
   // De-phase the first round of workgroups (later ones inherit the offsets as CUs free up): panels take
   // the same time everywhere, so without this every CU is in its HBM phase (prologue / epilogue) at the
   // same moment and idles HBM during the MFMA phase.
@@ -385,11 +453,14 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   // prologue's stores) at worst waits for more than it needs.
 #pragma unroll
   for (int p = 0; p < MF_AHEAD; ++p) issue(p, p);
+  if constexpr (XACC) request_tables();
   // accumulator layout of O: lane (r, hh) owns row m_base + r, columns 32 t + 8 cc + 4 hh .. + 3 in O[t][4 cc ..]
   const long xrow_l = m_base + r < M ? m_base + r : M - 1;
   const unsigned xoff = (unsigned)xrow_l * (unsigned)(MF_D * 4) + 16u * (unsigned)hh;
   // ... and in accumulator order (XL): the row's wave slice, its lane slot there; piece 4 t + cc follows at + 1024 (4 t + cc)
   const unsigned xoff_n = (unsigned)(xrow_l >> 5) * (unsigned)(32 * MF_D * 4) + 16u * (((unsigned)xrow_l & 31u) + 32u * (unsigned)hh);
+  // (XACC) the lane's 64 bytes of a ctx k-tile: row r, columns 32 hh .. + 31 of the tile
+  const unsigned coff = (unsigned)xrow_l * (unsigned)(MF_D * 2) + 64u * (unsigned)hh;
   f32x4 xp[XACC ? MF_OT : 1][4];
   // ---- X0: the device flag (block-uniform), the panel's first segment, and what every thread stages of the shared rows: 16-byte
   // piece q of [2 segments][xs[b, Tt - 2] | tr[b]][96] (the panel's segments are seg0 and, clamped to the last one, seg0 + 1)
@@ -435,11 +506,12 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   } else if constexpr (XACC) {
     // The residual stream goes straight INTO the accumulator file (48 loads of 16 bytes per lane, 32-byte row pieces
     // per lane pair), in front of the ctx loads: loads retire in issue order, so the first counted ctx wait below also
-    // proves every x piece has landed -- long before the out_proj GEMM's first MFMA reads them as its C operand.  The four
+    // proves every x piece in front of it has landed (XPR: n-tile 0; n-tiles 1 and 2 follow ctx k-tile 0 and are proven in the
+    // GEMM's tiles 1 and 2) -- before the out_proj GEMM's first MFMA on them reads them as its C operand.  The four
     // pieces of an accumulator tile are joined into O[t] BEHIND that wait (a register-sequence rename when hipcc's coalescer
     // cooperates, sixteen v_accvgpr_mov otherwise -- either way on landed data; tools/audit_asm_preload.py, build()).
 #pragma unroll
-    for (int t = 0; t < MF_OT; ++t)
+    for (int t = 0; t < (XPR ? 4 : MF_OT); ++t)   // (XPR: n-tiles 1 and 2 behind ctx k-tile 0, below)
 #pragma unroll
       for (int cc = 0; cc < 4; ++cc)
         if (GWW_MF_ABL & 32) asm volatile("v_accvgpr_write_b32 %0, 0" : "=a"(xp[t][cc][0]));   // (diagnostic: no x loads)
@@ -461,17 +533,26 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
     // is ctx[row r][64 S + 32 hh + 8 j .. + 7], 16 contiguous bytes; the four requests j = 0 .. 3 of a k-tile share each row's
     // 128-byte line through the vector L1 (no nt hint), as the x requests above do.  No staging registers, no LDS transpose
     // (24 ds_write_b128 + 24 ds_read_b128 per lane and their hand-counted waits in the row-order form below).
-    const unsigned coff = (unsigned)xrow_l * (unsigned)(MF_D * 2) + 64u * (unsigned)hh;
+    // CSP: only k-tile 0 here -- the other twenty requests ride in the out_proj GEMM, between its ring pieces (below).
 #pragma unroll
-    for (int S = 0; S < MF_KT; ++S)
+    for (int S = 0; S < (CSP ? 1 : MF_KT); ++S)
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(af[4 * S + j]) : "v"(coff), "s"(delta), "n"((64 * S + 8 * j) * 2) : "memory");
+    if constexpr (XPR) {
+#pragma unroll
+      for (int t = 4; t < MF_OT; ++t)
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+          if constexpr (XIN)
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" MF_XN_LDNT : "=a"(xp[t][cc]) : "v"(xoff_n), "s"(reinterpret_cast<const char*>(X) + 4096 * t), "n"(1024 * cc) : "memory");
+          else asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" MF_XNT : "=a"(xp[t][cc]) : "v"(xoff), "s"(X), "n"((32 * t + 8 * cc) * 4) : "memory");
+    }
     if constexpr (X0) {
       if (x0) {
-        // x and the staged pieces have landed once only the 24 ctx requests are outstanding; the shared row's fma runs on the
-        // accumulator registers while ctx is still arriving:  x[b, j] = fma(xs[b, Tt - 2], tr[b], pos[j])  (k_stem_fill)
-        asm volatile("s_waitcnt vmcnt(24)" : "+v"(x0_sg[0]), "+v"(x0_sg[1]) : : "memory");
+        // x and the staged pieces have landed once only the ctx requests (CSP: the 4 of k-tile 0, else all 24) are outstanding; the
+        // shared row's fma runs on the accumulator registers while ctx is still arriving:  x[b, j] = fma(xs[b, Tt - 2], tr[b], pos[j])  (k_stem_fill)
+        asm volatile("s_waitcnt vmcnt(%2)" : "+v"(x0_sg[0]), "+v"(x0_sg[1]) : "n"(CSP ? 4 : 4 * MF_KT) : "memory");
 #pragma unroll
         for (int t = 0; t < MF_OT; ++t) asm volatile("" : "+a"(xp[t][0]), "+a"(xp[t][1]), "+a"(xp[t][2]), "+a"(xp[t][3]));
         x0_publish(x0_sg);
@@ -488,12 +569,14 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
         }
       }
     }
-    stage_tables();
-    // one wait for the panel: ring tiles, x, ctx and the tables (loads retire in issue order; hipcc's own waits for the table
-    // values already imply it -- this one is for the reader).  The fences keep the fragments' first use behind it.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // one wait for the panel: ring tiles, the tables, x and ctx (loads retire in issue order).  The fences keep the fragments'
+    // and the table values' first use behind it.
+    // (CSP: "ctx" is k-tile 0 here; every later k-tile has its wait and its fences in the out_proj GEMM)
+    // (XPR: all but the 32 requests of x n-tiles 1 and 2, which the GEMM's tiles 1 and 2 wait for)
+    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(XPR ? 32 : 0) : "memory");
 #pragma unroll
-    for (int i = 0; i < MF_KT * 4; ++i) asm volatile("" : "+v"(af[i]));
+    for (int i = 0; i < (CSP ? 4 : MF_KT * 4); ++i) asm volatile("" : "+v"(af[i]));
+    publish_tables();
     row_rstd = 1.f; row_mean = 0.f;   // set by the seam behind the out_proj GEMM
   } else if constexpr (OP) {
     // ---- OP prologue: the attention context panel (bf16, read once in whole 128-byte lines: 16 bytes per lane, 8 lanes
@@ -681,7 +764,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
   f32x16 sacc[4], oacc[MF_OT];
   if constexpr (XACC) {   // the x pieces (landed: behind the prologue's ctx waits) become the accumulator tiles
 #pragma unroll
-    for (int t = 0; t < MF_OT; ++t) {
+    for (int t = 0; t < (XPR ? 4 : MF_OT); ++t) {   // (XPR: n-tiles 1 and 2 behind their waits in the out_proj GEMM)
       asm volatile("" : "+a"(xp[t][0]), "+a"(xp[t][1]), "+a"(xp[t][2]), "+a"(xp[t][3]));
       const auto lo = __builtin_shufflevector(xp[t][0], xp[t][1], 0, 1, 2, 3, 4, 5, 6, 7);
       const auto hi = __builtin_shufflevector(xp[t][2], xp[t][3], 0, 1, 2, 3, 4, 5, 6, 7);
@@ -810,7 +893,7 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
 
   // tile 0 landed (younger tiles may still be in flight)
   TSTAMP(10);
-  mf_wait_vmcnt<0>();   // tiles 0 .. AHEAD - 1 (requested at the kernel's start) and the prologue's stores
+  mf_wait_vmcnt<XPR ? 32 : 0>();   // tiles 0 .. AHEAD - 1 (requested at the kernel's start) and the prologue's stores (XPR: the 32 youngest x requests stay out)
   __builtin_amdgcn_s_barrier();
   TSTAMP(11);
 
@@ -1206,12 +1289,38 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
     // ======== out_proj in front of the block: O[n][m] = sum_k W_o[n][k] ctx[m][k], 3 n-tiles x 6 k-tiles of the q / k / v
     // tile format, accumulated into the (zeroed, still idle) output accumulators O[4 nt + u]
     static_assert(12 % MF_NST == 0, "OP mode relies on a ring whose depth divides the 12-tile body (4 or 6 stages)");
+    // k-tile major (all twelve accumulator tiles are live anyway; every element still takes its k-steps in ascending order, so
+    // the sums are what the n-tile major walk gave): k-tile S only needs the ctx fragments af[4 S .. 4 S + 3].
+    // CSP, the riders: tile 0 carries the four requests of k-tile 1, one behind each ring piece; tiles 3 S - 5, 3 S - 4 and
+    // 3 S - 3 carry 1, 1 and 2 requests of k-tile S >= 2, behind ring piece 1 (and 2).  Tile i issues ring tile i + 3, whose
+    // last piece the ring wait of tile i + 2 proves: a rider of tile i that is not behind that last piece has landed there,
+    // every rider of tile i by the ring wait of tile i + 3 -- k-tile S is complete at the wait of tile 3 S, its first reader.
+    // The ring wait of tile i allows the four pieces of ring tile i + 2, the riders of tile i - 1 and the rider behind the
+    // last piece of tile i - 2 (tile 0 alone has one) to be outstanding: 4, 8, 6, 5, 6, 5, 5, 6, ...; from tile 14 on, and so
+    // in the stream behind the GEMM, the counts are the ring's own again.
+    static_assert(!CSP || (MF_AHEAD == 3 && MF_GL == 4), "CSP: the riders' schedule is derived for a four-stage ring of four pieces per wave");
 #pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
+    for (int kt = 0; kt < MF_KT; ++kt) {
 #pragma unroll
-      for (int kt = 0; kt < MF_KT; ++kt) {
-        const int itile = nt * MF_KT + kt;               // compile-time: the stage is static
-        if (!(GWW_MF_ABL & 128)) mf_wait_vmcnt<MF_GL * (MF_AHEAD - 2)>();
+      for (int nt = 0; nt < 3; ++nt) {
+        const int itile = kt * 3 + nt;                   // compile-time: the stage is static
+        const int rid_prev = !CSP || itile < 1 || itile > 13 ? 0 : itile == 1 ? 4 : (itile - 2) % 3 == 2 ? 2 : 1;   // riders of tile itile - 1
+        // XPR: tile 0 starts on what the prologue proved; tile 1 needs x n-tile 1 and allows n-tile 2 (16), ring tile 3 and tile
+        // 0's riders behind it; tile 2's ring wait covers everything in front of ring tile 3 as it stands
+        const int ring_wait = XPR && itile == 0 ? 32 : XPR && itile == 1 ? 16 + MF_GL + 4 : MF_GL * (MF_AHEAD - 2) + rid_prev + (CSP && itile == 2 ? 1 : 0);
+        if (!(GWW_MF_ABL & 128)) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(ring_wait) : "memory");
+        if constexpr (XPR) {
+          if (kt == 0 && nt > 0) {   // the landed x pieces of this n-tile become its accumulator tiles
+#pragma unroll
+            for (int t = 4 * nt; t < 4 * nt + 4; ++t) {
+              asm volatile("" : "+a"(xp[t][0]), "+a"(xp[t][1]), "+a"(xp[t][2]), "+a"(xp[t][3]));
+              const auto lo = __builtin_shufflevector(xp[t][0], xp[t][1], 0, 1, 2, 3, 4, 5, 6, 7);
+              const auto hi = __builtin_shufflevector(xp[t][2], xp[t][3], 0, 1, 2, 3, 4, 5, 6, 7);
+              oacc[t] = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+            }
+          }
+        }
+        if (CSP && nt == 0 && kt > 0) asm volatile("" : "+v"(af[4 * kt]), "+v"(af[4 * kt + 1]), "+v"(af[4 * kt + 2]), "+v"(af[4 * kt + 3]));
         __builtin_amdgcn_s_barrier();
         const int st = itile % MF_NST, st_next = (itile + 1) % MF_NST, dma_st = (itile + MF_AHEAD) % MF_NST;
         const int dma_tile = itile + MF_AHEAD < total ? itile + MF_AHEAD : total - 1;
@@ -1223,6 +1332,12 @@ __global__ __launch_bounds__(MF_THREADS, 1) void k_mlp_fused(const float* X, con
           bf16x8(&nxt)[4] = wf[(q + 1) & 1];
           const unsigned char* Wn = lds + (sub == 3 ? st_next : st) * MF_TILE;
           if (!(GWW_MF_ABL & 128)) issue_piece(dma_tile, dma_st, sub);
+          if constexpr (CSP) {   // the rider behind this ring piece: fragment cp = 4 S + j, the request the prologue makes for k-tile 0
+            const int rm = (itile + 2) % 3, rS = (itile + 5) / 3;   // tile 3 S - 5 + rm of k-tile S
+            const int cp = itile == 0 ? 4 + sub : itile > 12 ? -1 : sub == 1 ? 4 * rS + rm : sub == 2 && rm == 2 ? 4 * rS + 3 : -1;
+            if (cp >= 0)
+              asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(af[cp >= 0 ? cp : 0]) : "v"(coff), "s"(delta), "n"((64 * (cp / 4) + 8 * (cp % 4)) * 2) : "memory");
+          }
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
             asm volatile(MF_PADNOP "v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(oacc[4 * nt + u]) : "v"(cur[u]), "v"(af[4 * kt + sub]));
@@ -1885,8 +2000,9 @@ __global__ __launch_bounds__(256) void k_mlp_pack(const unsigned short* __restri
     const int tile = tile_all - op_tiles;
     u32x4 v;
     if (tile < 0) {
-      // W_o [384, 384] in front of the stream (OP mode): n-tile major, 6 k-tiles each, [128 n][64 k] images
-      const int nt = tile_all / MF_KT, kt = tile_all - nt * MF_KT;
+      // W_o [384, 384] in front of the stream (OP mode): k-tile major, 3 n-tiles each, [128 n][64 k] images -- the out_proj
+      // GEMM walks k-tile by k-tile, so that its first three tiles need only the first sixth of ctx (MF_CSPREAD)
+      const int kt = tile_all / 3, nt = tile_all - 3 * kt;
       v = *reinterpret_cast<const u32x4*>(wo + (long)(128 * nt + row) * MF_D + 64 * kt + 8 * chunk);
     } else if (tile >= mlp_tiles) {
 #if GWW_MF_TAIL2
