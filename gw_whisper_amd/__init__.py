@@ -17,7 +17,7 @@ def __getattr__(name):
     # torch-dependent pieces are imported lazily so `import gw_whisper_amd` stays cheap
     import importlib
     if name in ("ops", "encoder", "synth", "feature_extraction", "peft", "models", "dist", "training", "inference", "qscan",
-                "glitch", "efficiency", "roc", "search_score"):
+                "glitch", "efficiency", "roc", "search_score", "real_events"):
         return importlib.import_module(f"{__name__}.{name}")
     if name in ("WhisperEncoder", "WhisperConfig"):
         return getattr(importlib.import_module(f"{__name__}.encoder"), name)

@@ -224,6 +224,11 @@ SIGNATURES = {
                                             C.c_void_p]),
     "gww_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "gww_cnn_head_saved_bytes": (C.c_size_t, [C.c_int, C.c_int]),
+    "gww_cnn_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gww_cnn_head_forward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3),
+    "gww_cnn_head_backward_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
+                                  + [C.c_size_t, C.c_void_p]),
     "gww_det_head_forward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 10),
     "gww_det_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
     "gww_det_head_backward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]

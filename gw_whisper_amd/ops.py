@@ -950,6 +950,66 @@ def eval_accumulate(logits, labels, row_loss, confusion, loss_sum, n):
               "gww_eval_accumulate")
 
 
+CNN_CHANNELS = (2, 64, 128, 256)   # models.TwoChannelLIGOBinaryClassifierCNN's conv chain (Signal_vs_Noise/src/model.py:63-73)
+
+
+def _cnn_params(params, who):
+    """The eight tensors of the CNN head (conv weights [Cout, Cin, 3], Linear [C, 256]) checked: (fp32 GPU tensors, C)."""
+    if len(params) != 8:
+        raise _lib.GwwError(f"{who}: expected (w1, b1, w2, b2, w3, b3, w4, b4)")
+    ps = [_dev(p, torch.float32, "head parameter") for p in params]
+    C = ps[6].shape[0] if ps[6].dim() == 2 else -1
+    shapes = []
+    for i in range(3):
+        shapes += [(CNN_CHANNELS[i + 1], CNN_CHANNELS[i], 3), (CNN_CHANNELS[i + 1],)]
+    shapes += [(C, CNN_CHANNELS[3]), (C,)]
+    for p, s in zip(ps, shapes):
+        if tuple(p.shape) != s:
+            raise _lib.GwwError(f"{who}: parameter of shape {tuple(p.shape)} where the CNN head 2 -> 64 -> 128 -> 256 -> C "
+                                f"has {s}")
+    return ps, C
+
+
+def cnn_head_forward(x, params, train: bool = False):
+    """CNN decoder head forward (``gww_cnn_head_forward_f32``, one launch): x fp32 [B, 2, d], params the eight tensors of
+    ``TwoChannelLIGOBinaryClassifierCNN.classifier`` in order.  Returns logits [B, C]; with ``train`` (logits, saved), the
+    logits bit for bit the same, ``saved`` what ``cnn_head_backward`` needs (``saved[2]``: the post-ReLU activations
+    [B, 64 + 128 + 256, d])."""
+    x = _dev(x, torch.float32, "x")
+    ps, C = _cnn_params(params, "cnn_head_forward")
+    if x.dim() != 3 or x.shape[1] != 2:
+        raise _lib.GwwError(f"cnn_head_forward: x {tuple(x.shape)} is not [B, 2, d]")
+    B, d = x.shape[0], x.shape[2]
+    logits = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    acts = torch.empty((B, sum(CNN_CHANNELS[1:]), d), dtype=torch.float32, device=x.device) if train else None
+    with torch.cuda.device(x.device):
+        check(lib().gww_cnn_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d, C, logits.data_ptr(),
+                                             acts.data_ptr() if train else None, _stream()), "gww_cnn_head_forward_f32")
+    return (logits, (x, ps, acts)) if train else logits
+
+
+def cnn_head_backward(saved, dlogits, ws=None):
+    """(dx [B, 2, d], [dw1, db1, ..., dw4, db4]) of ``cnn_head_forward(train=True)`` for the upstream gradient dlogits
+    [B, C] (``gww_cnn_head_backward_f32``; no host sync, no float atomics).  ``ws``: a caller's fp32 workspace of at least
+    ``gww_cnn_head_workspace_bytes(B, d, C)`` bytes (allocated here when None)."""
+    x, ps, acts = saved
+    B, d, C = x.shape[0], x.shape[2], ps[6].shape[0]
+    dlogits = _dev(dlogits, torch.float32, "dlogits")
+    if tuple(dlogits.shape) != (B, C):
+        raise _lib.GwwError(f"cnn_head_backward: dlogits {tuple(dlogits.shape)} is not [B, C] = {(B, C)}")
+    if ws is None:
+        ws = torch.empty((lib().gww_cnn_head_workspace_bytes(B, d, C) // 4,), dtype=torch.float32, device=x.device)
+    ws = _dev(ws, torch.float32, "ws")
+    dx = torch.empty_like(x)
+    grads = [torch.empty_like(t) for t in ps]
+    with torch.cuda.device(x.device):
+        check(lib().gww_cnn_head_backward_f32(x.data_ptr(), acts.data_ptr(), dlogits.data_ptr(),
+                                              *[t.data_ptr() for t in ps[0::2]], B, d, C, dx.data_ptr(),
+                                              *[g.data_ptr() for g in grads], ws.data_ptr(), ws.numel() * 4, _stream()),
+              "gww_cnn_head_backward_f32")
+    return dx, grads
+
+
 SCORE_PROB0, SCORE_LOGIT_DIFF = 0, 1
 MAX_FAPS = 8
 

@@ -20,6 +20,8 @@ Differences that come with the hardware path:
   * under ``torchrun`` every rank trains on its shard of each epoch and the trainable gradients are all-reduced
     in ONE flat bucket (RCCL).
 ``--method DoRA`` (the reference default), ``--method LoRA`` and ``--method full_finetune`` have a HIP backward.
+``--head cnn`` trains ``TwoChannelLIGOBinaryClassifierCNN`` (``src/model.py:57-85``) instead of the MLP head, for all three
+methods; the ``[best_]dense_layers`` artefact is then the CNN's ``classifier.state_dict()``.
 ``full_finetune`` follows ``src/train.py:243-247``: no adapters, ``requires_grad = True`` on every encoder and head
 parameter (``embed_positions`` included), AdamW over them, and the encoder saved by ``WhisperEncoder.save_pretrained``
 (``config.json`` + ``model.safetensors``, HF key names) under the reference's ``[best_]lora_weights_<r>_<alpha>`` name;
@@ -90,7 +92,7 @@ def main(args):
     from gw_whisper_amd import dist as gdist, ops, synth
     from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
     from gw_whisper_amd.feature_extraction import WhisperFeatureExtractor
-    from gw_whisper_amd.models import two_channel_ligo_binary_classifier
+    from gw_whisper_amd.models import TwoChannelLIGOBinaryClassifierCNN, two_channel_ligo_binary_classifier
     from gw_whisper_amd.peft import LoraConfig, get_peft_model
     rank, world, local = gdist.init()
     assert torch.cuda.is_available(), "run_train.py needs an MI355X (gw_whisper_amd has no CPU path)"
@@ -148,7 +150,8 @@ def main(args):
     if args.method != "full_finetune":
         for name, p in peft.named_parameters():
             p.requires_grad = "lora" in name
-    model = two_channel_ligo_binary_classifier(peft).to(device)
+    # src/train.py:23 imports both decoders; --head cnn builds the second one (its HIP chain, forward and backward)
+    model = (TwoChannelLIGOBinaryClassifierCNN(peft) if args.head == "cnn" else two_channel_ligo_binary_classifier(peft)).to(device)
     if args.method == "full_finetune":
         for p in model.parameters():   # src/train.py:246-247
             p.requires_grad = True
@@ -276,4 +279,7 @@ if __name__ == "__main__":
     parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
                         help="encoder arithmetic: bf16 (default) or exact fp32, the reference's own training arithmetic "
                              "(DoRA / LoRA only: full fine-tuning is bf16)")
+    parser.add_argument("--head", choices=("mlp", "cnn"), default="mlp",
+                        help="the decoder: two_channel_ligo_binary_classifier's MLP (default) or "
+                             "TwoChannelLIGOBinaryClassifierCNN, whose best_dense_layers artefact is the CNN's state_dict")
     main(parser.parse_args())

@@ -799,6 +799,28 @@ int gww_score_suffix_f64(const double* w1, const double* w2, long N, const int* 
 int gww_score_volume_f64(const double* found_sorted, const int* F, long N, const double* noise_sorted, long B, double Ninj,
                          double prefactor, const double* cs1, const double* cs2, long long* nfound, double* fraction,
                          double* volume, double* volume_err, void* stream);
+/* CNN decoder head of the two-detector model (cnn_head.hip; models.TwoChannelLIGOBinaryClassifierCNN, the reference's
+ * Signal_vs_Noise/src/model.py:57-85): per sample x [2, d] -> Conv1d(2, 64, 3, pad 1) -> ReLU -> Conv1d(64, 128, 3, pad 1)
+ * -> ReLU -> Conv1d(128, 256, 3, pad 1) -> ReLU -> mean over d -> Linear(256, C).  Exact fp32 (the wide convolutions are
+ * v_mfma_f32_16x16x4_f32 chains), no float atomics, every reduction in a fixed order: identical calls give identical
+ * bits, and a sample's logits and dx depend neither on B nor on its index.  Parameters are torch's own tensors, device
+ * fp32: w1 [64,2,3] b1 [64] w2 [128,64,3] b2 [128] w3 [256,128,3] b3 [256] w4 [C,256] b4 [C]; w2, w3, b2, b3 16-byte
+ * aligned.  d: an encoder width (128, 384, 512, 768, 1024, 1280); C 1..64; B 1..65535.
+ * Forward (1 launch): x fp32 [B, 2, d] -> logits [B, C].  saved == NULL: no activation leaves the chip.  Otherwise saved
+ * (gww_cnn_head_saved_bytes) receives the three post-ReLU activations, [B, 64 + 128 + 256, d]; the logits have the same
+ * bits either way.
+ * Backward (10 launches): dlogits [B, C] -> dx [B, 2, d] and the eight parameter gradients in torch's shapes
+ * (overwritten).  workspace: gww_cnn_head_workspace_bytes (0 = unsupported geometry), 16-byte aligned, scratch: its
+ * contents before the call do not matter.  GWW_ERR_WORKSPACE when it is smaller. */
+size_t gww_cnn_head_saved_bytes(int B, int d);
+size_t gww_cnn_head_workspace_bytes(int B, int d, int C);
+int gww_cnn_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* w3, const float* b3, const float* w4, const float* b4, int B, int d, int C,
+                             float* logits, float* saved, void* stream);
+int gww_cnn_head_backward_f32(const float* x, const float* saved, const float* dlogits, const float* w1, const float* w2,
+                              const float* w3, const float* w4, int B, int d, int C, float* dx, float* dw1, float* db1,
+                              float* dw2, float* db2, float* dw3, float* db3, float* dw4, float* db4, void* workspace,
+                              size_t workspace_bytes, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
 
