@@ -154,6 +154,8 @@ __device__ __forceinline__ float dgelu_fast(float z) {
 }
 
 static inline long cdiv(long a, long b) { return (a + b - 1) / b; }
+// p is a multiple of a (a power of two)
+static inline bool aligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
 
 // The residual stream [M, 384] fp32 in ACCUMULATOR order (k_mlp_fused, FwdPlan::x_native): between two fused blocks of the
 // inference forward x_next has one reader, the same wave and lane that wrote it, so each 32-row wave slice keeps its own

@@ -13,6 +13,7 @@
 //   k_sel_*          radix select over the order-preserving integer image of fp32: four 8-bit histogram passes for all
 //                    F ranks together (integer atomics only: they commute)
 //   k_det_counts     counts[f] += #{scores > thr[f]}
+#include "device_sort.h"
 #include "head_chain.h"
 
 namespace gww {
@@ -140,16 +141,8 @@ __global__ __launch_bounds__(256) void k_det_eval(const float* __restrict__ prob
 }
 
 // ---- rank selection --------------------------------------------------------------------------------------------------
-// order-preserving image of fp32 in uint32; every NaN is the largest key, as torch.sort orders it
-__device__ __forceinline__ unsigned sel_key(float v) {
-  const unsigned u = __float_as_uint(v);
-  if (v != v) return 0xFFFFFFFFu;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float sel_value(unsigned k) {
-  if (k == 0xFFFFFFFFu) return __uint_as_float(0x7FC00000u);
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
+// keys: the order-preserving image of the score (device_sort.h); every NaN is the largest key, 0xFFFFFFFF, as torch.sort
+// orders it, and comes back as the canonical NaN
 
 // workspace of one selection: hist [4 passes][F][256] uint32 | prefix [F] uint32 | remaining [F] int64
 struct SelWs {
@@ -192,7 +185,8 @@ __global__ __launch_bounds__(256) void k_sel_hist(const float* __restrict__ scor
   const int shift = 24 - 8 * pass;
   const unsigned himask = pass == 0 ? 0u : 0xFFFFFFFFu << (shift + 8);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < N; i += (long)gridDim.x * 256) {
-    const unsigned k = sel_key(scores[i]);
+    const float v = scores[i];
+    const unsigned k = v != v ? 0xFFFFFFFFu : ordered_u32(v);
     const unsigned d = (k >> shift) & 255u;
     for (int f = 0; f < F; ++f)
       if ((k & himask) == pre[f]) atomicAdd(&h[f * 256 + d], 1u);
@@ -219,7 +213,7 @@ __global__ __launch_bounds__(64) void k_sel_pick(int F, int pass, void* ws, floa
   const unsigned p = w.prefix[f] | ((unsigned)d << (24 - 8 * pass));
   w.prefix[f] = p;
   w.remaining[f] = rem;
-  if (pass == 3) thr[f] = sel_value(p);
+  if (pass == 3) thr[f] = p == 0xFFFFFFFFu ? __uint_as_float(0x7FC00000u) : from_ordered_u32(p);
 }
 
 // counts[f] += #{scores[i] > thr[f]} (strict; a NaN on either side compares false)

@@ -17,6 +17,7 @@
 // The DFT uses the real-input symmetry x[n] +- x[400-n] (half the MACs) with the
 // 400-entry twiddle table and the windowed frames in LDS; fp32 throughout.
 #include "common.h"
+#include "device_sort.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -39,15 +40,6 @@ struct Tables {
   float* sint;     // [400]
   float* fbT;      // [201][n_mels] filterbank, transposed so consecutive mels are contiguous
 };
-
-__device__ __forceinline__ unsigned int fkey(float f) {
-  unsigned int b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(unsigned int k) {
-  unsigned int b = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
-  return __uint_as_float(b);
-}
 
 // grid (tiles, n_seg), 256 threads
 template <int kNmel>
@@ -153,7 +145,7 @@ __global__ __launch_bounds__(256) void k_logmel_frames(const float* __restrict__
   __syncthreads();
   if (tid == 0) {
     float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    if (m > -INFINITY) atomicMax(&seg_max[seg], fkey(m));
+    if (m > -INFINITY) atomicMax(&seg_max[seg], ordered_u32(m));
   }
 }
 
@@ -316,7 +308,7 @@ __global__ __launch_bounds__(kMThreads) void k_logmel_frames_mfma(const float* _
   if (tid == 0) {
     float m = red[0];
     for (int w = 1; w < kMThreads / 64; ++w) m = fmaxf(m, red[w]);
-    if (m > -INFINITY) atomicMax(&seg_max[seg], fkey(m));
+    if (m > -INFINITY) atomicMax(&seg_max[seg], ordered_u32(m));
   }
   // whole 128-byte runs of a mel row per store instruction
   for (int i = tid; i < kNmel * kMT; i += kMThreads) {
@@ -330,7 +322,7 @@ template <int kNmel>
 __global__ __launch_bounds__(256) void k_logmel_finalize(float* __restrict__ out, int live,
                                                          const unsigned int* __restrict__ seg_max) {
   const int seg = blockIdx.y, m = blockIdx.x;
-  float mx = fkey_inv(seg_max[seg]);
+  float mx = from_ordered_u32(seg_max[seg]);
   mx = fmaxf(mx, live < kFrames ? -10.0f : mx);     // dead frames contribute log10(1e-10) = -10
   const float floor_v = mx - 8.0f;
   const float padv = (fmaxf(-10.0f, floor_v) + 4.0f) * 0.25f;

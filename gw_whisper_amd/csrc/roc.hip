@@ -2,8 +2,9 @@
 // AUC, and the bootstrap band of the TPR at a grid of FPRs.  Everything here is integer counting plus a few fp64 divisions
 // in a fixed order, so identical calls give identical bits and the results equal sklearn's / numpy's operation for
 // operation.  No float atomics, no cross-workgroup flags, nothing here synchronises.
-//   k_roc_keys / k_roc_hist / k_roc_scan / k_roc_scatter   LSD radix sort of (key, index) pairs, four 8-bit digits, stable;
-//                    key = the complement of the order-preserving image of the score: ascending keys = descending scores
+//   k_roc_keys       key = the complement of the order-preserving image of the score: ascending keys = descending scores;
+//                    then the shared stable radix sort of (key, index) pairs, four 8-bit digits (device_sort.h:
+//                    radix_hist / radix_scan / radix_scatter on 32-bit keys)
 //   k_roc_finish     order, rank (its inverse), pos (the label at each sorted position)
 //   k_roc_groups     one workgroup: gend[g] = the last sorted position of the g-th run of equal scores, G
 //   k_roc_curve      one workgroup: fps / tps / fpr / tpr at every run end, P, Nneg, the AUC from an int64 sum
@@ -15,6 +16,7 @@
 // This file is compiled with -ffp-contract=off (Makefile): a fused multiply-add in the interpolation or in the band would
 // lose the bit match with numpy.
 #include "common.h"
+#include "device_sort.h"
 
 namespace gww {
 
@@ -24,7 +26,6 @@ constexpr int RC_WAVES = RC_THREADS / 64;
 constexpr int RC_PER = RC_TILE / RC_THREADS;  // consecutive positions of one thread in the scan
 constexpr int RC_QMAX = 1024;
 constexpr long RC_NMAX = 1L << 24;
-constexpr int RS_CHUNK = 4096;              // elements of one workgroup of the sort (16 sub-tiles of 256)
 
 static_assert(RC_PER * RC_THREADS == RC_TILE && RC_PER % 4 == 0, "a thread scans whole uint4 groups");
 
@@ -33,28 +34,7 @@ static_assert(RC_PER * RC_THREADS == RC_TILE && RC_PER % 4 == 0, "a thread scans
 __device__ __forceinline__ unsigned roc_key(float v) {
   if (v != v) return 0u;
   if (v == 0.f) v = 0.f;
-  const unsigned u = __float_as_uint(v);
-  return ~((u & 0x80000000u) ? ~u : (u | 0x80000000u));
-}
-
-struct RocSortWs {
-  unsigned *key_a, *key_b;
-  int *idx_a, *idx_b;
-  unsigned* hist;           // [blocks][256]
-  size_t bytes;
-};
-static RocSortWs roc_sort_carve(void* ws, long N) {
-  Arena a;
-  char* base = reinterpret_cast<char*>(ws);
-  const size_t nb = (size_t)cdiv(N, RS_CHUNK);
-  RocSortWs w;
-  w.key_a = reinterpret_cast<unsigned*>(base + a.take((size_t)N * 4));
-  w.key_b = reinterpret_cast<unsigned*>(base + a.take((size_t)N * 4));
-  w.idx_a = reinterpret_cast<int*>(base + a.take((size_t)N * 4));
-  w.idx_b = reinterpret_cast<int*>(base + a.take((size_t)N * 4));
-  w.hist = reinterpret_cast<unsigned*>(base + a.take(nb * 256 * 4));
-  w.bytes = a.total();
-  return w;
+  return ~ordered_u32(v);
 }
 
 __global__ __launch_bounds__(64) void k_roc_init(int* __restrict__ G, int* __restrict__ n_nan) {
@@ -74,90 +54,6 @@ __global__ __launch_bounds__(256) void k_roc_keys(const float* __restrict__ scor
   if (v != v) atomicAdd(n_nan, 1);            // an integer count: the order of the adds does not matter
 }
 
-// hist[block][d] = the number of the block's keys with digit d
-__global__ __launch_bounds__(256) void k_roc_hist(const unsigned* __restrict__ key, int N, int shift, unsigned* __restrict__ hist) {
-  __shared__ unsigned h[256];
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const int lo = blockIdx.x * RS_CHUNK;
-  const int hi = lo + RS_CHUNK < N ? lo + RS_CHUNK : N;
-  for (int i = lo + threadIdx.x; i < hi; i += 256) atomicAdd(&h[(key[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  hist[(size_t)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
-}
-
-// one workgroup, thread d: hist[b][d] becomes the first output position of block b's keys with digit d (digit-major order)
-__global__ __launch_bounds__(256) void k_roc_scan(unsigned* __restrict__ hist, int blocks) {
-  __shared__ unsigned tot[256];
-  const int d = threadIdx.x;
-  unsigned s = 0u;
-  for (int b = 0; b < blocks; ++b) s += hist[(size_t)b * 256 + d];
-  tot[d] = s;
-  __syncthreads();
-  unsigned off = 0u;
-  for (int j = 0; j < d; ++j) off += tot[j];
-  for (int b = 0; b < blocks; ++b) {
-    const unsigned c = hist[(size_t)b * 256 + d];
-    hist[(size_t)b * 256 + d] = off;
-    off += c;
-  }
-}
-
-// the block's keys in order, 256 at a time: a key goes behind every earlier key of the same digit (stable)
-__global__ __launch_bounds__(256) void k_roc_scatter(const unsigned* __restrict__ key, const int* __restrict__ idx, int N,
-                                                     int shift, const unsigned* __restrict__ hist,
-                                                     unsigned* __restrict__ key_out, int* __restrict__ idx_out) {
-  __shared__ unsigned base[256];            // next output position of digit d
-  __shared__ unsigned wcnt[4][256];         // per wave: the count, then the first position, of digit d in this sub-tile
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  base[tid] = hist[(size_t)blockIdx.x * 256 + tid];
-  const int lo = blockIdx.x * RS_CHUNK;
-  const int hi = lo + RS_CHUNK < N ? lo + RS_CHUNK : N;
-  for (int t0 = lo; t0 < hi; t0 += 256) {
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-    __syncthreads();
-    const int i = t0 + tid;
-    const bool active = i < hi;
-    unsigned k = 0u;
-    int ix = 0;
-    if (active) {
-      k = key[i];
-      ix = idx[i];
-    }
-    const unsigned d = (k >> shift) & 255u;
-    unsigned long long peers = __ballot(active);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long vote = __ballot(active && bit);
-      peers &= bit ? vote : ~vote;
-    }
-    const unsigned before = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-    if (active && before == 0u) wcnt[wave][d] = (unsigned)__popcll(peers);
-    __syncthreads();
-    {
-      unsigned off = base[tid];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const unsigned c = wcnt[w][tid];
-        wcnt[w][tid] = off;
-        off += c;
-      }
-      base[tid] = off;
-    }
-    __syncthreads();
-    if (active) {
-      const unsigned dst = wcnt[wave][d] + before;
-      if (dst < (unsigned)N) {               // always true for a consistent histogram; never store outside the buffers
-        key_out[dst] = k;
-        idx_out[dst] = ix;
-      }
-    }
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(256) void k_roc_finish(const int* __restrict__ idx, const float* __restrict__ labels, int N,
                                                     int* __restrict__ order, int* __restrict__ rank,
                                                     unsigned char* __restrict__ pos) {
@@ -170,30 +66,6 @@ __global__ __launch_bounds__(256) void k_roc_finish(const int* __restrict__ idx,
   pos[p] = labels[i] > 0.5f ? 1 : 0;
 }
 
-// inclusive scan of v over the workgroup's RC_THREADS threads in thread order; part: RC_WAVES + 1 values of LDS.  Returns
-// the thread's inclusive prefix; *total = the sum over the workgroup.  Ends on a barrier: part may be reused at once.
-__device__ __forceinline__ unsigned long long roc_block_scan(unsigned long long v, unsigned long long* part,
-                                                             unsigned long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) part[wave] = v;
-  __syncthreads();
-  unsigned long long before = 0ull, all = 0ull;
-#pragma unroll
-  for (int w = 0; w < RC_WAVES; ++w) {
-    const unsigned long long t = part[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return v + before;
-}
-
 // one workgroup walks the sorted keys 1024 at a time: a position ends a run when the next key differs
 __global__ __launch_bounds__(RC_THREADS) void k_roc_groups(const unsigned* __restrict__ key, int N, int* __restrict__ gend,
                                                            int* __restrict__ G) {
@@ -203,7 +75,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_roc_groups(const unsigned* __res
     const int p = t0 + threadIdx.x;
     const bool end = p < N && (p == N - 1 || key[p] != key[p + 1]);
     unsigned long long tot;
-    const unsigned long long incl = roc_block_scan(end ? 1ull : 0ull, part, &tot);
+    const unsigned long long incl = block_scan<unsigned long long, RC_WAVES>(end ? 1ull : 0ull, part, &tot);
     if (end) gend[(int)(carry + incl) - 1] = p;
     carry += tot;
   }
@@ -223,7 +95,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_roc_curve(const unsigned char* _
   for (int t0 = 0; t0 < N; t0 += RC_THREADS) {
     const int p = t0 + threadIdx.x;
     unsigned long long tot;
-    const unsigned long long incl = roc_block_scan(p < N && pos[p] ? 1ull : 0ull, part, &tot);
+    const unsigned long long incl = block_scan<unsigned long long, RC_WAVES>(p < N && pos[p] ? 1ull : 0ull, part, &tot);
     if (p < N) cum[p] = (unsigned)(carry + incl);
     carry += tot;
   }
@@ -254,7 +126,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_roc_curve(const unsigned char* _
     tpr[g] = (double)tp / (double)P;
   }
   unsigned long long tot;
-  roc_block_scan(acc, part, &tot);           // an integer sum: exact in any order
+  block_scan<unsigned long long, RC_WAVES>(acc, part, &tot);           // an integer sum: exact in any order
   if (threadIdx.x == 0) {
     counts[0] = P;
     counts[1] = Nn;
@@ -314,7 +186,7 @@ __global__ __launch_bounds__(RC_THREADS) void k_roc_bootstrap(const int* __restr
       mine += y[u] ? (unsigned long long)c[u] << 32 : (unsigned long long)c[u];
     }
     unsigned long long tot;
-    unsigned long long run = carry + roc_block_scan(mine, part, &tot) - mine;
+    unsigned long long run = carry + block_scan<unsigned long long, RC_WAVES>(mine, part, &tot) - mine;
 #pragma unroll
     for (int u = 0; u < RC_PER; ++u) {
       run += y[u] ? (unsigned long long)c[u] << 32 : (unsigned long long)c[u];
@@ -410,8 +282,6 @@ __global__ __launch_bounds__(256) void k_bin_eval(const float* __restrict__ logi
   if (tid < 4) confusion[tid] += cm[tid];
 }
 
-static bool roc_aligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
-
 }  // namespace gww
 
 using namespace gww;
@@ -420,7 +290,7 @@ extern "C" int gww_roc_tile(void) { return RC_TILE; }
 
 extern "C" size_t gww_roc_sort_workspace_bytes(long N) {
   if (N < 2 || N > RC_NMAX) return 0;
-  return roc_sort_carve(nullptr, N).bytes;
+  return radix_carve<unsigned>(nullptr, N).bytes;
 }
 
 extern "C" int gww_roc_sort_f32(const float* scores, const float* labels, long N, int* order, int* rank, unsigned char* pos,
@@ -429,33 +299,21 @@ extern "C" int gww_roc_sort_f32(const float* scores, const float* labels, long N
   GWW_REQUIRE(N >= 2 && N <= RC_NMAX, "gww_roc_sort_f32: N=%ld must be 2..2^24", N);
   GWW_REQUIRE(ws_bytes >= gww_roc_sort_workspace_bytes(N), "gww_roc_sort_f32: workspace of %zu bytes, %zu needed", ws_bytes,
               gww_roc_sort_workspace_bytes(N));
-  GWW_REQUIRE(roc_aligned(ws, 16), "gww_roc_sort_f32: workspace must be 16-byte aligned");
-  const RocSortWs w = roc_sort_carve(ws, N);
+  GWW_REQUIRE(aligned(ws, 16), "gww_roc_sort_f32: workspace must be 16-byte aligned");
+  const RadixWs<unsigned> w = radix_carve<unsigned>(ws, N);
   hipStream_t s = (hipStream_t)stream;
   const int n = (int)N;
-  const unsigned blocks = (unsigned)cdiv(N, RS_CHUNK), b256 = (unsigned)cdiv(N, 256);
+  const unsigned b256 = (unsigned)cdiv(N, 256);
   hipLaunchKernelGGL(k_roc_init, dim3(1), dim3(64), 0, s, G, n_nan);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_roc_keys, dim3(b256), dim3(256), 0, s, scores, n, w.key_a, w.idx_a, n_nan);
   GWW_LAUNCH_CHECK();
-  unsigned* ka = w.key_a;
-  unsigned* kb = w.key_b;
-  int* ia = w.idx_a;
-  int* ib = w.idx_b;
-  for (int pass = 0; pass < 4; ++pass) {      // an even number of passes: the sorted pairs end in key_a / idx_a
-    hipLaunchKernelGGL(k_roc_hist, dim3(blocks), dim3(256), 0, s, (const unsigned*)ka, n, 8 * pass, w.hist);
-    GWW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_roc_scan, dim3(1), dim3(256), 0, s, w.hist, (int)blocks);
-    GWW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_roc_scatter, dim3(blocks), dim3(256), 0, s, (const unsigned*)ka, (const int*)ia, n, 8 * pass,
-                       (const unsigned*)w.hist, kb, ib);
-    GWW_LAUNCH_CHECK();
-    unsigned* tk = ka; ka = kb; kb = tk;
-    int* ti = ia; ia = ib; ib = ti;
-  }
-  hipLaunchKernelGGL(k_roc_finish, dim3(b256), dim3(256), 0, s, (const int*)ia, labels, n, order, rank, pos);
+  const unsigned* key;
+  const int* idx;
+  GWW_TRY(radix_sort_pairs(w, nullptr, N, s, &key, &idx));
+  hipLaunchKernelGGL(k_roc_finish, dim3(b256), dim3(256), 0, s, idx, labels, n, order, rank, pos);
   GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_roc_groups, dim3(1), dim3(RC_THREADS), 0, s, (const unsigned*)ka, n, gend, G);
+  hipLaunchKernelGGL(k_roc_groups, dim3(1), dim3(RC_THREADS), 0, s, key, n, gend, G);
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
@@ -472,7 +330,7 @@ extern "C" int gww_roc_curve_f64(const unsigned char* pos, const int* gend, cons
   GWW_REQUIRE(N >= 2 && N <= RC_NMAX, "gww_roc_curve_f64: N=%ld must be 2..2^24", N);
   GWW_REQUIRE(ws_bytes >= gww_roc_curve_workspace_bytes(N), "gww_roc_curve_f64: workspace of %zu bytes, %zu needed", ws_bytes,
               gww_roc_curve_workspace_bytes(N));
-  GWW_REQUIRE(roc_aligned(ws, 4), "gww_roc_curve_f64: workspace must be 4-byte aligned");
+  GWW_REQUIRE(aligned(ws, 4), "gww_roc_curve_f64: workspace must be 4-byte aligned");
   hipLaunchKernelGGL(k_roc_curve, dim3(1), dim3(RC_THREADS), 0, (hipStream_t)stream, pos, gend, G, (int)N,
                      reinterpret_cast<unsigned*>(ws), fps, tps, fpr, tpr, counts, auc);
   GWW_LAUNCH_CHECK();
@@ -493,7 +351,7 @@ extern "C" int gww_roc_bootstrap_tpr_f64(const int* rank, const unsigned char* p
   GWW_REQUIRE(Q >= 1 && Q <= RC_QMAX, "gww_roc_bootstrap_tpr_f64: Q=%d must be 1..%d", Q, RC_QMAX);
   GWW_REQUIRE(ws_bytes >= gww_roc_bootstrap_workspace_bytes(Rc, N), "gww_roc_bootstrap_tpr_f64: workspace of %zu bytes, %zu needed",
               ws_bytes, gww_roc_bootstrap_workspace_bytes(Rc, N));
-  GWW_REQUIRE(roc_aligned(ws, 8), "gww_roc_bootstrap_tpr_f64: workspace must be 8-byte aligned");
+  GWW_REQUIRE(aligned(ws, 8), "gww_roc_bootstrap_tpr_f64: workspace must be 8-byte aligned");
   const size_t lds = (size_t)RC_TILE * sizeof(unsigned) + RC_WAVES * sizeof(unsigned long long) + 16;
   GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_roc_bootstrap), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL(k_roc_bootstrap, dim3((unsigned)Rc), dim3(RC_THREADS), lds, (hipStream_t)stream, rank, pos, gend, G, idx,

@@ -4,9 +4,10 @@
 // order, so identical calls give identical bits and the results equal numpy's operation for operation; the only sums of
 // many fp64 terms, the chirp-mass-weighted suffix sums, are taken in one fixed order.  No float
 // atomics, no cross-workgroup flags, nothing here synchronises.
-//   k_sc_keys / k_sc_hist / k_sc_scan / k_sc_scatter / k_sc_finish   stable LSD radix sort of (key, index) pairs, eight
-//                    8-bit digits; key = the order-preserving 64-bit image of the double, ascending.  The element count
-//                    may live on the device (n_dev): the grid covers the capacity, the kernels read the count
+//   k_sc_keys / k_sc_finish   key = the order-preserving 64-bit image of the double, ascending; between the two the shared
+//                    stable radix sort of (key, index) pairs, eight 8-bit digits (device_sort.h: radix_hist / radix_scan /
+//                    radix_scatter on 64-bit keys).  The element count may live on the device (n_dev): the grid covers
+//                    the capacity, the kernels read the count
 //   k_sc_closest     find_closest_index for plain values
 //   k_sc_match       per time-sorted event: the gathered event, the closest injection, |dt|, the per-block (TP, FP) counts
 //   k_sc_offsets     one workgroup: the exclusive scan of the per-block count pairs, the two totals
@@ -19,10 +20,10 @@
 // This file is compiled with -ffp-contract=off (Makefile): a fused multiply-add in p - p * p would lose the bit match
 // with numpy.
 #include "common.h"
+#include "device_sort.h"
 
 namespace gww {
 
-constexpr int SC_CHUNK = 4096;              // elements of one workgroup of the sort (16 sub-tiles of 256)
 constexpr long SC_NMAX = 1L << 27;
 constexpr int SC_THREADS = 1024;
 constexpr int SC_WAVES = SC_THREADS / 64;
@@ -31,35 +32,7 @@ constexpr int SC_WAVES = SC_THREADS / 64;
 __device__ __forceinline__ unsigned long long sc_key(double v) {
   if (v != v) return ~0ull;
   if (v == 0.0) v = 0.0;
-  const unsigned long long u = (unsigned long long)__double_as_longlong(v);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-// the element count: the capacity, or the device's count clamped into 0..capacity
-__device__ __forceinline__ int sc_count(const int* __restrict__ n_dev, int cap) {
-  if (!n_dev) return cap;
-  const int n = n_dev[0];
-  return n < 0 ? 0 : (n > cap ? cap : n);
-}
-
-struct ScSortWs {
-  unsigned long long *key_a, *key_b;
-  int *idx_a, *idx_b;
-  unsigned* hist;           // [blocks][256]
-  size_t bytes;
-};
-static ScSortWs sc_sort_carve(void* ws, long n) {
-  Arena a;
-  char* base = reinterpret_cast<char*>(ws);
-  const size_t nb = (size_t)cdiv(n, SC_CHUNK);
-  ScSortWs w;
-  w.key_a = reinterpret_cast<unsigned long long*>(base + a.take((size_t)n * 8));
-  w.key_b = reinterpret_cast<unsigned long long*>(base + a.take((size_t)n * 8));
-  w.idx_a = reinterpret_cast<int*>(base + a.take((size_t)n * 4));
-  w.idx_b = reinterpret_cast<int*>(base + a.take((size_t)n * 4));
-  w.hist = reinterpret_cast<unsigned*>(base + a.take(nb * 256 * 4));
-  w.bytes = a.total();
-  return w;
+  return ordered_u64(v);
 }
 
 __global__ __launch_bounds__(64) void k_sc_zero(int* __restrict__ v, int n) {
@@ -69,7 +42,7 @@ __global__ __launch_bounds__(64) void k_sc_zero(int* __restrict__ v, int n) {
 __global__ __launch_bounds__(256) void k_sc_keys(const double* __restrict__ keys, const int* __restrict__ n_dev, int cap,
                                                  unsigned long long* __restrict__ key, int* __restrict__ idx,
                                                  int* __restrict__ n_nan) {
-  const int n = sc_count(n_dev, cap);
+  const int n = device_count(n_dev, cap);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double v = keys[i];
@@ -78,150 +51,16 @@ __global__ __launch_bounds__(256) void k_sc_keys(const double* __restrict__ keys
   if (v != v) atomicAdd(n_nan, 1);            // an integer count: the order of the adds does not matter
 }
 
-// hist[block][d] = the number of the block's keys with digit d (a block behind the count writes zeros)
-__global__ __launch_bounds__(256) void k_sc_hist(const unsigned long long* __restrict__ key, const int* __restrict__ n_dev,
-                                                 int cap, int shift, unsigned* __restrict__ hist) {
-  __shared__ unsigned h[256];
-  const int n = sc_count(n_dev, cap);
-  h[threadIdx.x] = 0u;
-  __syncthreads();
-  const long lo = (long)blockIdx.x * SC_CHUNK;
-  const long hi = lo + SC_CHUNK < n ? lo + SC_CHUNK : n;
-  for (long i = lo + threadIdx.x; i < hi; i += 256) atomicAdd(&h[(unsigned)(key[i] >> shift) & 255u], 1u);
-  __syncthreads();
-  hist[(size_t)blockIdx.x * 256 + threadIdx.x] = h[threadIdx.x];
-}
-
-// one workgroup, thread d: hist[b][d] becomes the first output position of block b's keys with digit d (digit-major order)
-__global__ __launch_bounds__(256) void k_sc_scan(unsigned* __restrict__ hist, int blocks) {
-  __shared__ unsigned tot[256];
-  const int d = threadIdx.x;
-  unsigned s = 0u;
-  for (int b = 0; b < blocks; ++b) s += hist[(size_t)b * 256 + d];
-  tot[d] = s;
-  __syncthreads();
-  unsigned off = 0u;
-  for (int j = 0; j < d; ++j) off += tot[j];
-  for (int b = 0; b < blocks; ++b) {
-    const unsigned c = hist[(size_t)b * 256 + d];
-    hist[(size_t)b * 256 + d] = off;
-    off += c;
-  }
-}
-
-// the block's keys in order, 256 at a time: a key goes behind every earlier key of the same digit (stable)
-__global__ __launch_bounds__(256) void k_sc_scatter(const unsigned long long* __restrict__ key, const int* __restrict__ idx,
-                                                    const int* __restrict__ n_dev, int cap, int shift,
-                                                    const unsigned* __restrict__ hist, unsigned long long* __restrict__ key_out,
-                                                    int* __restrict__ idx_out) {
-  __shared__ unsigned base[256];            // next output position of digit d
-  __shared__ unsigned wcnt[4][256];         // per wave: the count, then the first position, of digit d in this sub-tile
-  const int n = sc_count(n_dev, cap);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  base[tid] = hist[(size_t)blockIdx.x * 256 + tid];
-  const long lo = (long)blockIdx.x * SC_CHUNK;
-  const long hi = lo + SC_CHUNK < n ? lo + SC_CHUNK : n;
-  for (long t0 = lo; t0 < hi; t0 += 256) {   // lo, hi are the workgroup's: every thread takes the same trips
-#pragma unroll
-    for (int w = 0; w < 4; ++w) wcnt[w][tid] = 0u;
-    __syncthreads();
-    const long i = t0 + tid;
-    const bool active = i < hi;
-    unsigned long long k = 0ull;
-    int ix = 0;
-    if (active) {
-      k = key[i];
-      ix = idx[i];
-    }
-    const unsigned d = (unsigned)(k >> shift) & 255u;
-    unsigned long long peers = __ballot(active);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-      const bool bit = (d >> b) & 1u;
-      const unsigned long long vote = __ballot(active && bit);
-      peers &= bit ? vote : ~vote;
-    }
-    const unsigned before = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-    if (active && before == 0u) wcnt[wave][d] = (unsigned)__popcll(peers);
-    __syncthreads();
-    {
-      unsigned off = base[tid];
-#pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const unsigned c = wcnt[w][tid];
-        wcnt[w][tid] = off;
-        off += c;
-      }
-      base[tid] = off;
-    }
-    __syncthreads();
-    if (active) {
-      const unsigned dst = wcnt[wave][d] + before;
-      if (dst < (unsigned)n) {               // always true for a consistent histogram; never store outside the buffers
-        key_out[dst] = k;
-        idx_out[dst] = ix;
-      }
-    }
-    __syncthreads();
-  }
-}
-
 __global__ __launch_bounds__(256) void k_sc_finish(const int* __restrict__ idx, const double* __restrict__ keys,
                                                    const int* __restrict__ n_dev, int cap, int* __restrict__ order,
                                                    double* __restrict__ sorted) {
-  const int n = sc_count(n_dev, cap);
+  const int n = device_count(n_dev, cap);
   const int p = blockIdx.x * 256 + threadIdx.x;
   if (p >= n) return;
   int i = idx[p];
   if ((unsigned)i >= (unsigned)n) i = 0;     // a permutation by construction
   order[p] = i;
   sorted[p] = keys[i];
-}
-
-// inclusive scan of v over the workgroup's SC_THREADS threads in thread order; part: SC_WAVES values of LDS.  Returns the
-// thread's inclusive prefix; *total = the sum over the workgroup.  Ends on a barrier: part may be reused at once.
-__device__ __forceinline__ unsigned long long sc_block_scan(unsigned long long v, unsigned long long* part,
-                                                            unsigned long long* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o, 64);
-    if (lane >= o) v += u;
-  }
-  if (lane == 63) part[wave] = v;
-  __syncthreads();
-  unsigned long long before = 0ull, all = 0ull;
-#pragma unroll
-  for (int w = 0; w < SC_WAVES; ++w) {
-    const unsigned long long t = part[w];
-    if (w < wave) before += t;
-    all += t;
-  }
-  __syncthreads();
-  *total = all;
-  return v + before;
-}
-
-// the same in fp64: the additions of one call always happen in the same order (the shuffle tree, then the waves in order)
-__device__ __forceinline__ double sc_block_scan_f64(double v, double* part, double* total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const double u = __shfl_up(v, o, 64);
-    if (lane >= o) v = v + u;
-  }
-  if (lane == 63) part[wave] = v;
-  __syncthreads();
-  double before = 0.0, all = 0.0;
-#pragma unroll
-  for (int w = 0; w < SC_WAVES; ++w) {
-    const double t = part[w];
-    if (w < wave) before = before + t;
-    all = all + t;
-  }
-  __syncthreads();
-  *total = all;
-  return before + v;
 }
 
 // ---- closest injection --------------------------------------------------------------------------------------------------
@@ -277,7 +116,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_match(const double* __restric
     if (t != t || s != s || v != v) atomicAdd(n_nan, 1);
   }
   unsigned long long tot;
-  sc_block_scan(sc_pair(p < E && tp, p < E), part, &tot);
+  block_scan<unsigned long long, SC_WAVES>(sc_pair(p < E && tp, p < E), part, &tot);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -289,7 +128,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_offsets(unsigned long long* _
     const int b = b0 + threadIdx.x;
     const unsigned long long v = b < nb ? blk[b] : 0ull;
     unsigned long long tot;
-    const unsigned long long incl = sc_block_scan(v, part, &tot);
+    const unsigned long long incl = block_scan<unsigned long long, SC_WAVES>(v, part, &tot);
     if (b < nb) blk[b] = carry + incl - v;
     carry += tot;
   }
@@ -317,7 +156,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_compact_ev(const double* __re
   const bool tp = active && d <= v;
   const unsigned long long mine = sc_pair(tp, active);
   unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + sc_block_scan(mine, part, &tot) - mine;
+  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, SC_WAVES>(mine, part, &tot) - mine;
   if (!active) return;
   const unsigned j = tp ? (unsigned)(excl >> 32) : (unsigned)(excl & 0xFFFFFFFFull);
   if (j >= (unsigned)E) return;              // always false for consistent counts; never store outside the buffers
@@ -381,7 +220,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_inj_count(const unsigned char
   const long i = (long)blockIdx.x * SC_THREADS + threadIdx.x;
   const int f = i < N ? flag[i] : 0;
   unsigned long long tot;
-  sc_block_scan(sc_pair(f == 1, f == 2), part, &tot);
+  block_scan<unsigned long long, SC_WAVES>(sc_pair(f == 1, f == 2), part, &tot);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -394,7 +233,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_compact_inj(const unsigned ch
   const int f = i < N ? flag[i] : 0;
   const unsigned long long mine = sc_pair(f == 1, f == 2);
   unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + sc_block_scan(mine, part, &tot) - mine;
+  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, SC_WAVES>(mine, part, &tot) - mine;
   if (f == 1) {
     const unsigned j = (unsigned)(excl >> 32);
     if (j < (unsigned)N) {
@@ -410,7 +249,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_compact_inj(const unsigned ch
 // ---- rates and volumes ----------------------------------------------------------------------------------------------------
 // far[k] = (n - k - 1) / duration over n ascending noise statistics (evaluate.py:185-186): an exact integer, one division
 __global__ __launch_bounds__(256) void k_sc_far(const int* __restrict__ n_dev, int cap, double duration, double* __restrict__ far) {
-  const int n = sc_count(n_dev, cap);
+  const int n = device_count(n_dev, cap);
   const long k = (long)blockIdx.x * 256 + threadIdx.x;
   if (k >= n) return;
   far[k] = (double)((long)n - k - 1) / duration;
@@ -423,7 +262,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_suffix(const double* __restri
                                                           const int* __restrict__ F_dev, double* __restrict__ cs1,
                                                           double* __restrict__ cs2) {
   __shared__ double part[SC_WAVES];
-  const int F = sc_count(F_dev, N);
+  const int F = device_count(F_dev, N);
   double c1 = 0.0, c2 = 0.0;
   if (threadIdx.x == 0) {
     cs1[F] = 0.0;
@@ -441,8 +280,8 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_suffix(const double* __restri
       b = w2[i];
     }
     double t1, t2;
-    const double s1 = sc_block_scan_f64(a, part, &t1);
-    const double s2 = sc_block_scan_f64(b, part, &t2);
+    const double s1 = block_scan<double, SC_WAVES>(a, part, &t1);
+    const double s2 = block_scan<double, SC_WAVES>(b, part, &t2);
     if (p >= 0) {
       cs1[p] = c1 + s1;
       cs2[p] = c2 + s2;
@@ -458,7 +297,7 @@ __global__ __launch_bounds__(256) void k_sc_volume(const double* __restrict__ fo
                                                    const double* __restrict__ cs1, const double* __restrict__ cs2,
                                                    long long* __restrict__ nfound, double* __restrict__ frac,
                                                    double* __restrict__ vol, double* __restrict__ vol_err) {
-  const int F = sc_count(F_dev, cap);
+  const int F = device_count(F_dev, cap);
   const long k = (long)blockIdx.x * 256 + threadIdx.x;
   if (k >= B) return;
   const double x = noise[k];
@@ -486,8 +325,6 @@ __global__ __launch_bounds__(256) void k_sc_volume(const double* __restrict__ fo
   vol_err[k] = prefactor * __dsqrt_rn(Ninj * sv);
 }
 
-static bool sc_aligned(const void* p, uintptr_t a) { return (((uintptr_t)p) & (a - 1)) == 0; }
-
 struct ScMatchWs {
   double* diff;             // [E]
   double* best;             // [N]
@@ -514,7 +351,7 @@ using namespace gww;
 
 extern "C" size_t gww_score_sort_workspace_bytes(long n) {
   if (n < 1 || n > SC_NMAX) return 0;
-  return sc_sort_carve(nullptr, n).bytes;
+  return radix_carve<unsigned long long>(nullptr, n).bytes;
 }
 
 extern "C" int gww_score_sort_f64(const double* keys, long n, const int* n_dev, double* sorted, int* order, int* n_nan, void* ws,
@@ -523,31 +360,19 @@ extern "C" int gww_score_sort_f64(const double* keys, long n, const int* n_dev, 
   GWW_REQUIRE(n >= 1 && n <= SC_NMAX, "gww_score_sort_f64: n=%ld must be 1..2^27", n);
   GWW_REQUIRE(ws_bytes >= gww_score_sort_workspace_bytes(n), "gww_score_sort_f64: workspace of %zu bytes, %zu needed", ws_bytes,
               gww_score_sort_workspace_bytes(n));
-  GWW_REQUIRE(sc_aligned(ws, 16), "gww_score_sort_f64: workspace must be 16-byte aligned");
-  const ScSortWs w = sc_sort_carve(ws, n);
+  GWW_REQUIRE(aligned(ws, 16), "gww_score_sort_f64: workspace must be 16-byte aligned");
+  const RadixWs<unsigned long long> w = radix_carve<unsigned long long>(ws, n);
   hipStream_t s = (hipStream_t)stream;
   const int cap = (int)n;
-  const unsigned blocks = (unsigned)cdiv(n, SC_CHUNK), b256 = (unsigned)cdiv(n, 256);
+  const unsigned b256 = (unsigned)cdiv(n, 256);
   hipLaunchKernelGGL(k_sc_zero, dim3(1), dim3(64), 0, s, n_nan, 1);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sc_keys, dim3(b256), dim3(256), 0, s, keys, n_dev, cap, w.key_a, w.idx_a, n_nan);
   GWW_LAUNCH_CHECK();
-  unsigned long long* ka = w.key_a;
-  unsigned long long* kb = w.key_b;
-  int* ia = w.idx_a;
-  int* ib = w.idx_b;
-  for (int pass = 0; pass < 8; ++pass) {      // an even number of passes: the sorted pairs end in key_a / idx_a
-    hipLaunchKernelGGL(k_sc_hist, dim3(blocks), dim3(256), 0, s, (const unsigned long long*)ka, n_dev, cap, 8 * pass, w.hist);
-    GWW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sc_scan, dim3(1), dim3(256), 0, s, w.hist, (int)blocks);
-    GWW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(k_sc_scatter, dim3(blocks), dim3(256), 0, s, (const unsigned long long*)ka, (const int*)ia, n_dev, cap,
-                       8 * pass, (const unsigned*)w.hist, kb, ib);
-    GWW_LAUNCH_CHECK();
-    unsigned long long* tk = ka; ka = kb; kb = tk;
-    int* ti = ia; ia = ib; ib = ti;
-  }
-  hipLaunchKernelGGL(k_sc_finish, dim3(b256), dim3(256), 0, s, (const int*)ia, keys, n_dev, cap, order, sorted);
+  const unsigned long long* key;
+  const int* idx;
+  GWW_TRY(radix_sort_pairs(w, n_dev, n, s, &key, &idx));
+  hipLaunchKernelGGL(k_sc_finish, dim3(b256), dim3(256), 0, s, idx, keys, n_dev, cap, order, sorted);
   GWW_LAUNCH_CHECK();
   return GWW_OK;
 }
@@ -577,7 +402,7 @@ extern "C" int gww_score_match_f64(const double* events, const int* order, long 
   GWW_REQUIRE(N >= 1 && N <= SC_NMAX, "gww_score_match_f64: N=%ld must be 1..2^27", N);
   GWW_REQUIRE(ws_bytes >= gww_score_match_workspace_bytes(E, N), "gww_score_match_f64: workspace of %zu bytes, %zu needed",
               ws_bytes, gww_score_match_workspace_bytes(E, N));
-  GWW_REQUIRE(sc_aligned(ws, 16), "gww_score_match_f64: workspace must be 16-byte aligned");
+  GWW_REQUIRE(aligned(ws, 16), "gww_score_match_f64: workspace must be 16-byte aligned");
   const ScMatchWs w = sc_match_carve(ws, E, N);
   hipStream_t s = (hipStream_t)stream;
   const int e = (int)E, n = (int)N;

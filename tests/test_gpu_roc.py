@@ -51,7 +51,7 @@ def _score_kinds(n, seed):
             "descending": asc[::-1].copy()}
 
 
-@pytest.mark.parametrize("n", [2, 3, 63, 64, 65, 255, 257, 4097])
+@pytest.mark.parametrize("n", [2, 3, 63, 64, 65, 255, 257, 4096, 4097, 8193])
 def test_sort(T, gww, n):
     labels = (np.random.default_rng(n).random(n) < 0.5).astype(np.float32)
     for kind, scores in _score_kinds(n, 100 + n).items():
