@@ -261,6 +261,20 @@ SIGNATURES = {
     "gww_score_suffix_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 6),
     "gww_score_volume_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_double, C.c_double]
                              + [C.c_void_p] * 7),
+    "gww_trig_triggers_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_trig_triggers_f64": (C.c_int, [C.c_void_p, C.c_int, C.c_long, C.c_long, C.c_double, C.c_double, C.c_double]
+                              + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "gww_trig_events_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_trig_events_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_double] + [C.c_void_p] * 4
+                            + [C.c_size_t, C.c_void_p]),
+    "gww_trig_split_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_trig_split_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_double] + [C.c_void_p] * 4
+                           + [C.c_size_t, C.c_void_p]),
+    "gww_trig_steps_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_trig_steps_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_double, C.c_double,
+                                     C.c_double] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
+    "gww_det_head_scores2_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
+                                           C.c_void_p]),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

@@ -29,6 +29,8 @@ struct DetTail {
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
 // MODE -1: the training / evaluation forward (saves, loss tail).  MODE 0: score = probs[:, 0].  MODE 1: score = z0 - z1.
+// MODE 2: every column of probs, MODE 3: (z0 - z1, z1 - z0) -- score [B, C] with row pitch score_stride (the efficiency
+// study's test stage writes both outputs of the network, test_network.py:89-99).
 // LDS: buffer 0 x [16][d_in], then h2 [16][256], then h4 [16][64]; buffer 1 h1 [16][512], then h3 [16][128], then the
 // logits [16][C]
 template <int MODE>
@@ -47,6 +49,10 @@ __global__ __launch_bounds__(CH_THREADS) void k_det_fwd(const float* __restrict_
       if (lane == 0) score[row * score_stride] = Z.p[m * Z.ld] - Z.p[m * Z.ld + 1];
       continue;
     }
+    if (MODE == 3) {
+      if (lane < 2) score[row * score_stride + lane] = Z.p[m * Z.ld + lane] - Z.p[m * Z.ld + 1 - lane];
+      continue;
+    }
     // Everything behind the logits is fp64, rounded to fp32 once per output: the last layer's bias gradient is a batch sum
     // of dz columns that cancel (for C = 2 the two columns are each other's negatives), which amplifies whatever rounding
     // dz carries; the tail is B x C elements, its cost does not show.
@@ -57,6 +63,10 @@ __global__ __launch_bounds__(CH_THREADS) void k_det_fwd(const float* __restrict_
     const double p = e / se;
     if (MODE == 0) {
       if (lane == 0) score[row * score_stride] = (float)p;
+      continue;
+    }
+    if (MODE == 2) {
+      if (lane < C) score[row * score_stride + lane] = (float)p;
       continue;
     }
     // 1 - p_c as (the sum of the OTHER lanes' e) / se, summed in lane order: 1 - e / se would cancel to the rounding of se
@@ -317,6 +327,32 @@ extern "C" int gww_det_head_scores_f32(const float* x, const float* w1, const fl
   } else {
     GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(k_det_fwd<1>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
+  }
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+extern "C" int gww_det_head_scores2_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                                        const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                                        const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride,
+                                        void* stream) {
+  GWW_TRY(chain_check_shape("gww_det_head_scores2_f32", B, 65536, d_in, C, 2));
+  GWW_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && w5 && b5 && out, "gww_det_head_scores2_f32: NULL argument");
+  GWW_REQUIRE(mode == 0 || mode == 1, "gww_det_head_scores2_f32: mode=%d must be 0 (probs) or 1 (z0 - z1, z1 - z0)", mode);
+  GWW_REQUIRE(mode == 0 || C == 2, "gww_det_head_scores2_f32: mode 1 (z0 - z1, z1 - z0) needs C = 2, not %d", C);
+  GWW_REQUIRE(out_stride >= C, "gww_det_head_scores2_f32: out_stride=%ld must be >= C = %d", out_stride, C);
+  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, w5, b1, b2, b3, b4}), "gww_det_head_scores2_f32: operands must be 16-byte aligned");
+  const size_t lds = chain_lds_bytes<DetChain>(d_in);
+  hipStream_t s = (hipStream_t)stream;
+  const ChainFwdArgs<DetChain::L> P{{w1, w2, w3, w4, w5}, {b1, b2, b3, b4, b5}, {}};
+  const DetTail S{};
+  const dim3 grid((unsigned)cdiv(B, CH_ROWS));
+  if (mode == 0) {
+    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_det_fwd<2>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
+  } else {
+    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k_det_fwd<3>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
   }
   GWW_LAUNCH_CHECK();
   return GWW_OK;

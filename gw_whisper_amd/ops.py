@@ -1065,6 +1065,27 @@ def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
     return out
 
 
+def det_head_scores2(x, params, out=None, remove_softmax: bool = False):
+    """Both outputs of the detection head per row of x (``gww_det_head_scores2_f32``, one launch, inference only): the
+    softmax ``probs`` [B, C], or with ``remove_softmax`` (C = 2) the pair ``(z0 - z1, z1 - z0)`` of the reference's
+    mutual-subtraction layer (``test_network.py:89-99``).  ``out``: a 2-d fp32 GPU view [B, C] with unit column stride and
+    any row pitch >= C -- rows of the output of a whole file -- allocated here when None."""
+    x = _dev(x, torch.float32, "x")
+    ps, d_in, C = _mlp_params(params, DET_WIDTHS, "det_head", "detection head")
+    B = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != d_in:
+        raise _lib.GwwError(f"det_head_scores2: x {tuple(x.shape)} does not fit d_in = {d_in}")
+    if out is None:
+        out = torch.empty((B, C), dtype=torch.float32, device=x.device)
+    if (not out.is_cuda or out.dtype != torch.float32 or tuple(out.shape) != (B, C) or out.stride(1) != 1
+            or (B > 1 and out.stride(0) < C)):
+        raise _lib.GwwError(f"det_head_scores2: out must be an fp32 GPU view [{B}, {C}] with unit column stride")
+    with torch.cuda.device(x.device):
+        check(lib().gww_det_head_scores2_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d_in, C, 1 if remove_softmax else 0,
+                                             out.data_ptr(), max(out.stride(0), C), _stream()), "gww_det_head_scores2_f32")
+    return out
+
+
 SLIDE_LOGIT0, SLIDE_PROB0 = 0, 1
 SLIDE_WIDTHS = (256, 128, 64)      # layers 2..5 of the search head behind its 512-wide first layer
 SLIDE_MAX_D, SLIDE_MAX_S = 4, 65535
@@ -1452,3 +1473,108 @@ def score_volume(found_sorted, F, noise_sorted, n_inj: float, prefactor: float, 
                                          0 if cs2 is None else cs2.data_ptr(), nfound.data_ptr(), frac.data_ptr(),
                                          vol.data_ptr(), err.data_ptr(), _stream()), "gww_score_volume_f64")
     return nfound, frac, vol, err
+
+
+# ---- the efficiency study's test stage: triggers, events, ranking steps (csrc/trigger_stats.hip) -------------------------
+TRIG_MAX_N = 1 << 27
+
+
+def _trig_vec(t, n, who, name):
+    t = _dev(t, torch.float64, name)
+    if tuple(t.shape) != (n,):
+        raise _lib.GwwError(f"{who}: {name} must be fp64 [{n}], got {tuple(t.shape)}")
+    return t
+
+
+def trig_triggers(series, delta_t: float, epoch: float, threshold: float, cap=None, ws=None):
+    """The samples of ``series`` (fp32 or fp64 [n], 1 <= n <= 2^27) above ``threshold``, in order
+    (``gww_trig_triggers_f64``, 4 launches, no host sync).  Returns (times fp64 [cap], values fp64 [cap], counts int32 [2] =
+    (triggers, NaN samples)): the first min(counts[0], cap) entries are written; cap defaults to n."""
+    if not series.is_cuda:
+        raise _lib.GwwError(f"trig_triggers: series must live on the GPU (got {series.device}); gw_whisper_amd has no CPU path")
+    if series.dtype not in (torch.float32, torch.float64):
+        raise _lib.GwwError(f"trig_triggers: series must be torch.float32 or torch.float64, got {series.dtype}")
+    series = series.contiguous()
+    n = series.numel()
+    if series.dim() != 1 or not 1 <= n <= TRIG_MAX_N:
+        raise _lib.GwwError(f"trig_triggers: series must be [n] with 1 <= n <= 2^27, got {tuple(series.shape)}")
+    cap = n if cap is None else int(cap)
+    if not 1 <= cap <= n:
+        raise _lib.GwwError(f"trig_triggers: cap={cap} must be 1..n = {n}")
+    dev = series.device
+    ws = _roc_ws(ws, lib().gww_trig_triggers_workspace_bytes(n), dev, "trig_triggers")
+    times = torch.empty((cap,), dtype=torch.float64, device=dev)
+    values = torch.empty((cap,), dtype=torch.float64, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_trig_triggers_f64(series.data_ptr(), int(series.dtype == torch.float64), n, cap, float(delta_t),
+                                          float(epoch), float(threshold), times.data_ptr(), values.data_ptr(),
+                                          counts.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+              "gww_trig_triggers_f64")
+    return times, values, counts
+
+
+def trig_events(times, values, tolerance: float, n_dev=None, ws=None):
+    """Clusters of the ascending trigger times (a gap >= ``tolerance`` opens one) and per cluster the time and value of its
+    first maximum (``gww_trig_events_f64``, 4 launches, no host sync).  times, values fp64 [cap]; ``n_dev`` int32 [1]: the
+    device's trigger count.  Returns (ev_times [cap], ev_values [cap], counts int32 [2] = (events, NaN values))."""
+    times = _dev(times, torch.float64, "times")
+    cap = times.numel()
+    if times.dim() != 1 or not 1 <= cap <= TRIG_MAX_N:
+        raise _lib.GwwError(f"trig_events: times must be [cap] with 1 <= cap <= 2^27, got {tuple(times.shape)}")
+    values = _trig_vec(values, cap, "trig_events", "values")
+    cnt = _score_count(n_dev, "trig_events")
+    dev = times.device
+    ws = _roc_ws(ws, lib().gww_trig_events_workspace_bytes(cap), dev, "trig_events")
+    ev_t = torch.empty((cap,), dtype=torch.float64, device=dev)
+    ev_v = torch.empty((cap,), dtype=torch.float64, device=dev)
+    counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_trig_events_f64(times.data_ptr(), values.data_ptr(), cnt, cap, float(tolerance), ev_t.data_ptr(),
+                                        ev_v.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                        _stream()), "gww_trig_events_f64")
+    return ev_t, ev_v, counts
+
+
+def trig_split(values, diff, tolerance: float, n_dev=None, ws=None):
+    """The event values split by ``diff <= tolerance`` (``gww_trig_split_f64``, 4 launches, no host sync): values, diff fp64
+    [cap].  Returns (tp_values [cap], fp_values [cap], counts int32 [3] = (true positives, false positives, NaN values))."""
+    values = _dev(values, torch.float64, "values")
+    cap = values.numel()
+    if values.dim() != 1 or not 1 <= cap <= TRIG_MAX_N:
+        raise _lib.GwwError(f"trig_split: values must be [cap] with 1 <= cap <= 2^27, got {tuple(values.shape)}")
+    diff = _trig_vec(diff, cap, "trig_split", "diff")
+    cnt = _score_count(n_dev, "trig_split")
+    dev = values.device
+    ws = _roc_ws(ws, lib().gww_trig_split_workspace_bytes(cap), dev, "trig_split")
+    tp = torch.empty((cap,), dtype=torch.float64, device=dev)
+    fp = torch.empty((cap,), dtype=torch.float64, device=dev)
+    counts = torch.empty((3,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_trig_split_f64(values.data_ptr(), diff.data_ptr(), cnt, cap, float(tolerance), tp.data_ptr(),
+                                       fp.data_ptr(), counts.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       _stream()), "gww_trig_split_f64")
+    return tp, fp, counts
+
+
+def trig_steps(fp_sorted, n_fp, tp_sorted, n_tp, duration: float, prefactor: float, n_inj: float, ws=None):
+    """The ranking steps over the ascending false-positive values (``gww_trig_steps_f64``, 4 launches, no host sync):
+    fp_sorted fp64 [cap] of which n_fp (int32 [1], device) count, tp_sorted fp64 [cap_tp] of which n_tp count.  Returns
+    (ranking, far, sens_frac, sens_vol, sens_vol_err fp64 [cap], n_steps int32 [1])."""
+    fp_sorted = _dev(fp_sorted, torch.float64, "fp_sorted")
+    tp_sorted = _dev(tp_sorted, torch.float64, "tp_sorted")
+    cap, cap_tp = fp_sorted.numel(), tp_sorted.numel()
+    if fp_sorted.dim() != 1 or tp_sorted.dim() != 1 or not 1 <= cap <= TRIG_MAX_N or not 1 <= cap_tp <= TRIG_MAX_N:
+        raise _lib.GwwError("trig_steps: fp_sorted must be [cap] and tp_sorted [cap_tp] with 1 <= cap, cap_tp <= 2^27")
+    _state(n_fp, torch.int32, (1,), "trig_steps", "n_fp")
+    _state(n_tp, torch.int32, (1,), "trig_steps", "n_tp")
+    dev = fp_sorted.device
+    ws = _roc_ws(ws, lib().gww_trig_steps_workspace_bytes(cap), dev, "trig_steps")
+    outs = [torch.empty((cap,), dtype=torch.float64, device=dev) for _ in range(5)]
+    n_steps = torch.empty((1,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_trig_steps_f64(fp_sorted.data_ptr(), n_fp.data_ptr(), cap, tp_sorted.data_ptr(), n_tp.data_ptr(), cap_tp,
+                                       float(duration), float(prefactor), float(n_inj), *[o.data_ptr() for o in outs],
+                                       n_steps.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+              "gww_trig_steps_f64")
+    return (*outs, n_steps)

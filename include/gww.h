@@ -799,6 +799,48 @@ int gww_score_suffix_f64(const double* w1, const double* w2, long N, const int* 
 int gww_score_volume_f64(const double* found_sorted, const int* F, long N, const double* noise_sorted, long B, double Ninj,
                          double prefactor, const double* cs1, const double* cs2, long long* nfound, double* fraction,
                          double* volume, double* volume_err, void* stream);
+/* ---- the efficiency study's test stage: triggers, events, false-alarm rate (csrc/trigger_stats.hip)
+ * The counterpart of Efficiency_test/src/evaluate_test_data.py.  Device pointers throughout, plain launches, no host
+ * synchronisation; identical calls give identical bits and no result depends on the launch geometry.  Every size and
+ * capacity is 1..2^27; more is refused before any launch, and so is a workspace (16-byte aligned) smaller than its
+ * *_workspace_bytes function says.  A count taken from the device (an int32 pointer) is clamped into 0..capacity. */
+/* get_triggers: the samples with series[i] > threshold, compared in fp64 (series fp64, or fp32 when is_f64 == 0: widened
+ * exactly; equality is no trigger, a NaN never is), in order: times[j] = double(i) * delta_t + epoch (two roundings, no
+ * fused multiply-add), values[j] = series[i].  times, values [cap], cap <= n.  counts int32 [2] = (the number of
+ * triggers -- of which the first cap are stored --, the number of NaN samples). */
+size_t gww_trig_triggers_workspace_bytes(long n);
+int gww_trig_triggers_f64(const void* series, int is_f64, long n, long cap, double delta_t, double epoch, double threshold,
+                          double* times, double* values, int* counts, void* ws, size_t ws_bytes, void* stream);
+/* Clusters and events over ascending trigger times: trigger j opens a cluster iff j == 0 or times[j] - times[j-1] >=
+ * tolerance; per cluster, in order, the time and value of the FIRST maximum of its values (np.argmax), however many
+ * workgroups the cluster spans.  times, values, ev_times, ev_values [cap] fp64; n_dev: NULL (cap triggers) or the device's
+ * count.  counts int32 [2] = (events, NaN values). */
+size_t gww_trig_events_workspace_bytes(long cap);
+int gww_trig_events_f64(const double* times, const double* values, const int* n_dev, long cap, double tolerance,
+                        double* ev_times, double* ev_values, int* counts, void* ws, size_t ws_bytes, void* stream);
+/* True positive iff diff[j] <= tolerance (diff: the distance to the nearest injection, gww_score_closest_f64); the values
+ * of the true and of the false positives in order into tp_values / fp_values [cap].  counts int32 [3] = (true positives,
+ * false positives, NaN values). */
+size_t gww_trig_split_workspace_bytes(long cap);
+int gww_trig_split_f64(const double* values, const double* diff, const int* n_dev, long cap, double tolerance,
+                       double* tp_values, double* fp_values, int* counts, void* ws, size_t ws_bytes, void* stream);
+/* Ranking steps (evaluate_test_data.py:555-612) over the ascending false-positive values fp_sorted (n_fp[0] of cap) and
+ * true-positive values tp_sorted (n_tp[0] of cap_tp): one step per run [a, b] of equal values; ranking = v[a]; count =
+ * n_fp - b - 1, except n_fp for a first run of length one; far = count / duration * 2592000; tidx =
+ * searchsorted(tp_sorted, ranking, 'right'); sens_frac = 1 - tidx / n_tp; s = n_tp - tidx, q = s / Ninj, sens_vol =
+ * prefactor * s, sens_vol_err = prefactor * sqrt(Ninj * (q - q * q)).  Outputs [cap] fp64 of which n_steps[0] (int32,
+ * device) entries are written.  duration > 0. */
+size_t gww_trig_steps_workspace_bytes(long cap);
+int gww_trig_steps_f64(const double* fp_sorted, const int* n_fp, long cap, const double* tp_sorted, const int* n_tp,
+                       long cap_tp, double duration, double prefactor, double Ninj, double* ranking, double* far,
+                       double* sens_frac, double* sens_vol, double* sens_vol_err, int* n_steps, void* ws, size_t ws_bytes,
+                       void* stream);
+/* Both outputs of the detection head per row, inference only, one launch (test_network.py): out [B, C] fp32 with row
+ * pitch out_stride >= C.  mode 0: the softmax, the bits of gww_det_head_forward_f32's probs; mode 1 (C = 2): (z0 - z1,
+ * z1 - z0), the reference's --remove-softmax layer.  Operands as gww_det_head_scores_f32. */
+int gww_det_head_scores2_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                             const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride, void* stream);
 /* CNN decoder head of the two-detector model (cnn_head.hip; models.TwoChannelLIGOBinaryClassifierCNN, the reference's
  * Signal_vs_Noise/src/model.py:57-85): per sample x [2, d] -> Conv1d(2, 64, 3, pad 1) -> ReLU -> Conv1d(64, 128, 3, pad 1)
  * -> ReLU -> Conv1d(128, 256, 3, pad 1) -> ReLU -> mean over d -> Linear(256, C).  Exact fp32 (the wide convolutions are
