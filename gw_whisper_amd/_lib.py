@@ -275,6 +275,11 @@ SIGNATURES = {
                                      C.c_double] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
     "gww_det_head_scores2_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
                                            C.c_void_p]),
+    "gww_bin_head_forward_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "gww_bin_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "gww_bin_head_backward_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
+                                  + [C.c_void_p] * 12),
+    "gww_bin_head_scores_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against

@@ -149,6 +149,94 @@ __device__ __forceinline__ ChainRows chain_fwd(float* sm, const float* __restric
   return ChainRows{buf[CH::L & 1], ld[CH::L & 1]};
 }
 
+// ---- forward, x walked in k chunks ---------------------------------------------------------------------------------------
+// The same chain for a first layer whose input row does not fit LDS next to the widest hidden row (Chain<1024, 512, 256> at
+// d_in >= 1536: 16 (d_in + 1024 + 8) 4 bytes pass the 163 840 of a workgroup).  Buffer 0 is fwd_w(0) wide and holds x one
+// chunk of fwd_w(0) columns at a time; a wave keeps the accumulators of all its first-layer tiles across the chunks.  Every
+// accumulator sees k in the order of chain_layer_fwd (ascending 64-blocks, u, x y z w), so the bits are those of chain_fwd
+// wherever both can run.
+template <class CH>
+static size_t chain_chunked_lds_bytes() {
+  return (size_t)CH_ROWS * (CH::fwd_w(0) + CH::fwd_w(1) + 2 * CH_PAD) * sizeof(float);
+}
+
+template <class CH, bool SAVE>
+__device__ __forceinline__ ChainRows chain_fwd_chunked(float* sm, const float* __restrict__ x, const ChainFwdArgs<CH::L>& P,
+                                                       int B, int d_in, int C) {
+  constexpr int KC = CH::fwd_w(0), N0 = CH::out(0), TPW = N0 / 16 / CH_WAVES, TG = TPW % 4 == 0 ? 4 : 1;
+  static_assert(KC % 64 == 0 && N0 % (16 * CH_WAVES) == 0 && N0 <= CH::fwd_w(1), "chunked first layer: whole tiles per wave");
+  constexpr int ld[2] = {KC + CH_PAD, CH::fwd_w(1) + CH_PAD};
+  float* const buf[2] = {sm, sm + CH_ROWS * ld[0]};
+  const long row0 = (long)blockIdx.x * CH_ROWS;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, c = lane & 15, q = lane >> 4;
+  f32x4 acc[TPW];
+#pragma unroll
+  for (int j = 0; j < TPW; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = 0; k0 < d_in; k0 += KC) {
+    const int kc = d_in - k0 < KC ? d_in - k0 : KC;      // a multiple of 64
+    const int k4 = kc >> 2;
+    if (k0) __syncthreads();                             // the previous chunk has been read
+    for (int i = threadIdx.x; i < CH_ROWS * k4; i += CH_THREADS) {
+      const int m = i / k4, k = (i - m * k4) * 4;
+      float4 v = {0.f, 0.f, 0.f, 0.f};
+      if (row0 + m < B) v = *reinterpret_cast<const float4*>(x + (row0 + m) * d_in + k0 + k);
+      *reinterpret_cast<float4*>(buf[0] + m * ld[0] + k) = v;
+    }
+    __syncthreads();
+    // k outside, the wave's tiles inside in groups of TG: one read of the x operand serves TG tiles, whose weight loads are
+    // in flight together and whose MFMA chains are independent of one another
+    const float* ip = buf[0] + c * ld[0] + 4 * q;
+    const float* wp = P.W[0] + (long)(wave * 16 + c) * d_in + k0 + 4 * q;
+    for (int k = 0; k < kc; k += 64) {
+      float4 a[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) a[u] = *reinterpret_cast<const float4*>(ip + k + 16 * u);
+#pragma unroll
+      for (int j0 = 0; j0 < TPW; j0 += TG) {
+        float4 w[TG][4];
+#pragma unroll
+        for (int j = 0; j < TG; ++j)
+#pragma unroll
+          for (int u = 0; u < 4; ++u)
+            w[j][u] = *reinterpret_cast<const float4*>(wp + (long)(j0 + j) * (CH_WAVES * 16) * d_in + k + 16 * u);
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+          for (int j = 0; j < TG; ++j) {
+            f32x4& A = acc[j0 + j];
+            A = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u].x, a[u].x, A, 0, 0, 0);
+            A = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u].y, a[u].y, A, 0, 0, 0);
+            A = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u].z, a[u].z, A, 0, 0, 0);
+            A = __builtin_amdgcn_mfma_f32_16x16x4f32(w[j][u].w, a[u].w, A, 0, 0, 0);
+          }
+      }
+    }
+  }
+  // acc[j][r] = h1[m = c][n = 16 (wave + 8 j) + 4 q + r]: the HIDDEN epilogue of chain_layer_fwd
+  const long row = row0 + c;
+#pragma unroll
+  for (int j = 0; j < TPW; ++j) {
+    const int n = (wave + j * CH_WAVES) * 16 + 4 * q;
+    const float4 bv = *reinterpret_cast<const float4*>(P.b[0] + n);
+    const float4 o = {fmaxf(acc[j][0] + bv.x, 0.f), fmaxf(acc[j][1] + bv.y, 0.f), fmaxf(acc[j][2] + bv.z, 0.f),
+                      fmaxf(acc[j][3] + bv.w, 0.f)};
+    *reinterpret_cast<float4*>(buf[1] + c * ld[1] + n) = o;
+    if (SAVE && P.save[0] && row < B) *reinterpret_cast<float4*>(P.save[0] + row * N0 + n) = o;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = 1; i < CH::L - 1; ++i) {
+    chain_layer_fwd<true, false>(buf[i & 1], ld[i & 1], buf[(i + 1) & 1], ld[(i + 1) & 1], P.W[i], P.b[i], CH::out(i - 1),
+                                 CH::out(i), i, NoDrop{}, SAVE ? P.save[i] : nullptr, row0, B);
+    __syncthreads();
+  }
+  constexpr int l = CH::L - 1;
+  chain_layer_fwd<false, false>(buf[l & 1], ld[l & 1], buf[CH::L & 1], ld[CH::L & 1], P.W[l], P.b[l], CH::out(l - 1), C, l,
+                                NoDrop{}, SAVE ? P.save[l] : nullptr, row0, B);
+  __syncthreads();
+  return ChainRows{buf[CH::L & 1], ld[CH::L & 1]};
+}
+
 // ---- backward, input side -------------------------------------------------------------------------------------------
 // out[m][k] = sum_n dz[m][n] W[n][k] for the workgroup's 16 rows (dz in LDS, its columns zero-padded to a multiple of 16).
 // A wave owns 64-column strips: lane (c, q) reads W[n + q][k0 + 4 c .. + 3] as one 16-byte load (a 256-byte run per row)
@@ -238,6 +326,37 @@ __device__ __forceinline__ void chain_bwd(const float* __restrict__ dz_in, const
     const int s = (L - 1 - i) & 1;
     chain_layer_bwd<true, SCALED>(buf[s], ld[s], buf[s ^ 1], ld[s ^ 1], A.W[i], CH::out(i, C), CH::out(i - 1), A.h[i - 1], scale,
                                   A.dz[i - 1], row0, B);
+    __syncthreads();
+  }
+  constexpr int s = (L - 1) & 1;
+  chain_layer_bwd<false, false>(buf[s], ld[s], nullptr, 0, A.W[0], CH::out(0), d_in, nullptr, 1.f, A.dx, row0, B);
+}
+
+// chain_bwd over the caller's LDS (sm: CH::bwd_lds_bytes(), 16-byte aligned): a chain whose two buffers pass the 64 KiB of
+// static LDS takes them from the launch.  Same layer walk, same bits.
+template <class CH>
+__device__ __forceinline__ void chain_bwd_at(float* sm, const float* __restrict__ dz_in, const float* __restrict__ gscale,
+                                             const ChainBwdArgs<CH::L>& A, int B, int d_in, int C) {
+  constexpr int L = CH::L, ld[2] = {CH::bwd_w(0) + CH_PAD, CH::bwd_w(1) + CH_PAD};
+  float* const buf[2] = {sm, sm + CH_ROWS * ld[0]};
+  const long row0 = (long)blockIdx.x * CH_ROWS;
+  const float g = gscale ? gscale[0] : 1.f;
+  const int C16 = (C + 15) & ~15;
+  for (int i = threadIdx.x; i < CH_ROWS * C16; i += CH_THREADS) {
+    const int m = i / C16, n = i - m * C16;
+    float v = 0.f;
+    if (row0 + m < B && n < C) {
+      v = g * dz_in[(row0 + m) * C + n];
+      A.dz[L - 1][(row0 + m) * C + n] = v;
+    }
+    buf[0][m * ld[0] + n] = v;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int i = L - 1; i > 0; --i) {
+    const int s = (L - 1 - i) & 1;
+    chain_layer_bwd<true, false>(buf[s], ld[s], buf[s ^ 1], ld[s ^ 1], A.W[i], CH::out(i, C), CH::out(i - 1), A.h[i - 1], 1.f,
+                                 A.dz[i - 1], row0, B);
     __syncthreads();
   }
   constexpr int s = (L - 1) & 1;

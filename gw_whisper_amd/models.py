@@ -14,7 +14,9 @@ call ``encoder(mel).last_hidden_state[:, -1, :]`` and read ``encoder.config.d_mo
 these copies exist because the reference tree does not travel to the GPU box, and they use
 the encoder's ``last_token`` fast path when it is available (inference: only token 1499 goes
 through the final LayerNorm; training: the last layer's row-wise ops and their backward run on
-the pooled rows only).  The MLP heads are plain ``torch.nn`` on the GPU; the CNN head is HIP.
+the pooled rows only).  The MLP heads are plain ``torch.nn`` on the GPU unless a trainer asks for their HIP
+step (``binary.head_bce_with_logits`` on ``pooled(...)``, ``glitch.head_cross_entropy``, ``efficiency.reg_bce_head``); the
+CNN head is HIP.
 """
 
 from __future__ import annotations
@@ -50,6 +52,12 @@ class two_channel_ligo_binary_classifier(nn.Module):
             nn.Linear(1024, 512), nn.ReLU(),
             nn.Linear(512, 256), nn.ReLU(),
             nn.Linear(256, num_classes))
+
+    def pooled(self, mel_tensor_0, mel_tensor_1):
+        """[B, 2 d_model]: what ``forward`` feeds the classifier (the input of ``binary.head_bce_with_logits``)"""
+        n = mel_tensor_0.shape[0]
+        both = _pooled(self.encoder, torch.cat((mel_tensor_0, mel_tensor_1), dim=0))
+        return torch.cat((both[:n], both[n:]), dim=1)
 
     def forward(self, mel_tensor_0, mel_tensor_1):
         # both detectors share the encoder weights: one pass over the stacked batch (same arithmetic
@@ -129,6 +137,10 @@ class one_channel_ligo_binary_classifier(nn.Module):
             nn.Linear(256, 128), nn.ReLU(),
             nn.Linear(128, 64), nn.ReLU(),
             nn.Linear(64, num_classes))
+
+    def pooled(self, mel_tensor_0):
+        """[B, d_model]: what ``forward`` feeds the classifier (the input of ``binary.head_bce_with_logits``)"""
+        return _pooled(self.encoder, mel_tensor_0)
 
     def forward(self, mel_tensor_0):
         return self.classifier(_pooled(self.encoder, mel_tensor_0))

@@ -1086,6 +1086,71 @@ def det_head_scores2(x, params, out=None, remove_softmax: bool = False):
     return out
 
 
+BIN_HEAD_ONE, BIN_HEAD_TWO = 1, 2           # include/gww.h GWW_BIN_HEAD_*: the number of detectors
+# hidden widths of models.one_channel_ligo_binary_classifier / two_channel_ligo_binary_classifier (Signal_vs_Noise/src/model.py)
+BIN_HEAD_WIDTHS = {BIN_HEAD_ONE: (512, 256, 128, 64), BIN_HEAD_TWO: (1024, 512, 256)}
+
+
+def _bin_layout(layout, params, who):
+    if layout not in BIN_HEAD_WIDTHS:
+        raise _lib.GwwError(f"{who}: layout={layout!r} must be BIN_HEAD_ONE ({BIN_HEAD_ONE}) or BIN_HEAD_TWO ({BIN_HEAD_TWO})")
+    widths = BIN_HEAD_WIDTHS[layout]
+    return (widths, *_mlp_params(params, widths, who, "one-detector binary head" if layout == BIN_HEAD_ONE
+                                 else "two-detector binary head"))
+
+
+def _ptrs(ts, n):
+    """data pointers of ``ts`` padded with NULL to the ``n`` slots of the C entry"""
+    return [t.data_ptr() for t in ts] + [None] * (n - len(ts))
+
+
+def bin_head_forward(layout: int, x, params, targets):
+    """Binary head + BCEWithLogitsLoss forward (``gww_bin_head_forward_f32``, 2 launches): x fp32 [B, d_in], params the
+    ``nn.Linear`` tensors of the classifier in order (ten for BIN_HEAD_ONE, eight for BIN_HEAD_TWO), targets fp32 [B, C] in
+    [0, 1].  Returns (loss [1] device scalar, logits [B, C], probs [B, C], row_loss [B], saved) with ``saved`` what
+    ``bin_head_backward`` needs (``saved[3]``: the post-ReLU activations, ``saved[4]``: dz)."""
+    x = _dev(x, torch.float32, "x")
+    targets = _dev(targets, torch.float32, "targets")
+    widths, ps, d_in, C = _bin_layout(layout, params, "bin_head_forward")
+    if x.dim() != 2 or x.shape[1] != d_in or tuple(targets.shape) != (x.shape[0], C):
+        raise _lib.GwwError(f"bin_head_forward: x {tuple(x.shape)} / targets {tuple(targets.shape)} do not fit d_in = {d_in}, "
+                            f"C = {C}")
+    h, (logits, probs, dz), row_loss, loss = _mlp_outputs(x, widths, C, 3)
+    with torch.cuda.device(x.device):
+        check(lib().gww_bin_head_forward_f32(int(layout), x.data_ptr(), *_ptrs(ps, 10), targets.data_ptr(), x.shape[0], d_in, C,
+                                             *_ptrs(h, 4), logits.data_ptr(), probs.data_ptr(), row_loss.data_ptr(),
+                                             dz.data_ptr(), loss.data_ptr(), _stream()), "gww_bin_head_forward_f32")
+    return loss, logits, probs, row_loss, (int(layout), x, ps, h, dz)
+
+
+def bin_head_backward(saved, dloss=None, ws=None):
+    """(dx [B, d_in], [dw1, db1, ...]) of ``bin_head_forward``'s loss times the device scalar ``dloss``
+    (``gww_bin_head_backward_f32``, 2 launches; no host sync).  ``ws``: a caller's fp32 workspace of at least
+    ``gww_bin_head_workspace_bytes(layout, B, C)`` bytes (allocated here when None)."""
+    layout, x, ps, h, dz = saved
+    B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
+    dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, ws, lib().gww_bin_head_workspace_bytes(layout, B, C))
+    with torch.cuda.device(dev):
+        check(lib().gww_bin_head_backward_f32(layout, x.data_ptr(), *_ptrs(ps[0::2], 5), *_ptrs(h, 4), dz.data_ptr(), dloss, B,
+                                              d_in, C, ws.data_ptr(), ws.numel() * 4, dx.data_ptr(), *_ptrs(grads, 10),
+                                              _stream()), "gww_bin_head_backward_f32")
+    return dx, grads
+
+
+def bin_head_scores(layout: int, x, params):
+    """logits [B, C] of the binary head (``gww_bin_head_scores_f32``, one launch, inference only): bit for bit what
+    ``bin_head_forward`` gives."""
+    x = _dev(x, torch.float32, "x")
+    _widths, ps, d_in, C = _bin_layout(layout, params, "bin_head_scores")
+    if x.dim() != 2 or x.shape[1] != d_in:
+        raise _lib.GwwError(f"bin_head_scores: x {tuple(x.shape)} does not fit d_in = {d_in}")
+    logits = torch.empty((x.shape[0], C), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        check(lib().gww_bin_head_scores_f32(int(layout), x.data_ptr(), *_ptrs(ps, 10), x.shape[0], d_in, C, logits.data_ptr(),
+                                            _stream()), "gww_bin_head_scores_f32")
+    return logits
+
+
 SLIDE_LOGIT0, SLIDE_PROB0 = 0, 1
 SLIDE_WIDTHS = (256, 128, 64)      # layers 2..5 of the search head behind its 512-wide first layer
 SLIDE_MAX_D, SLIDE_MAX_S = 4, 65535

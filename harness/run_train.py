@@ -26,6 +26,17 @@ methods; the ``[best_]dense_layers`` artefact is then the CNN's ``classifier.sta
 parameter (``embed_positions`` included), AdamW over them, and the encoder saved by ``WhisperEncoder.save_pretrained``
 (``config.json`` + ``model.safetensors``, HF key names) under the reference's ``[best_]lora_weights_<r>_<alpha>`` name;
 ``--encoder-weights <dir>/model.safetensors`` loads it back.
+``--detectors 1`` is the reference's single-detector twin ``src/sd_train.py``: ``l1_timeseries`` only
+(``one_channel_LigoBinaryData``, ``src/dataset.py:28-46``; with ``--synthetic`` the L1 half), the head of
+``one_channel_ligo_binary_classifier`` (d -> 512 -> 256 -> 128 -> 64 -> 1, ``src/model.py:31-52``), the same loop, artefact
+names and resume flags, for all three methods.  It has no CNN decoder: ``--detectors 1 --head cnn`` is refused.
+``--head-step hip`` runs the MLP head's forward, ``BCEWithLogitsLoss`` and backward as one HIP step
+(``gw_whisper_amd.binary.head_bce_with_logits``, csrc/binary_head.hip: exact fp32, four launches) and takes the host
+synchronisations out of the loop: the step losses stay device tensors and are read once per epoch, validation goes through
+``binary.head_logits`` + ``roc.BinaryEvalState`` with one host read per pass.  Its validation loss is the reference's (sum of
+the batch means) / (number of batches) (``src/train.py:91,105``, ``sd_train.py:91,105``); the default ``--head-step torch``
+branch weights every batch mean by its number of samples, so the two differ whenever the last validation batch is short.
+``--head-step hip --head cnn`` is refused (the CNN decoder has its own HIP chain).
 """
 import argparse
 import fnmatch
@@ -77,6 +88,7 @@ def synthetic_dataset(n, seed):
 
 
 def load_arrays(args):
+    """(h1, l1, labels, snr); h1 is None with --detectors 1 on a dataset directory (sd_train.py never reads it)."""
     if args.synthetic:
         return synthetic_dataset(args.synthetic, args.seed)
     from datasets import concatenate_datasets, load_from_disk
@@ -84,15 +96,28 @@ def load_arrays(args):
     chunks = sorted(p for p in os.listdir(path) if p.startswith("chunk")) if os.path.isdir(path) else []
     ds = concatenate_datasets([load_from_disk(os.path.join(path, c)) for c in chunks]) if chunks else load_from_disk(path)
     cols = ds.with_format("numpy")
-    return (np.asarray(cols["h1_timeseries"], np.float32), np.asarray(cols["l1_timeseries"], np.float32),
+    single = getattr(args, "detectors", 2) == 1
+    return (None if single else np.asarray(cols["h1_timeseries"], np.float32), np.asarray(cols["l1_timeseries"], np.float32),
             np.asarray(cols["labels"], np.float32), np.asarray(cols["injection_snr"], np.float32))
 
 
+def check_args(args):
+    """The flag combinations that name no model of the reference."""
+    if args.detectors == 1 and args.head == "cnn":
+        raise ValueError("--detectors 1 --head cnn: the single-detector trainer (src/sd_train.py) has the MLP head only; the "
+                         "CNN decoder stacks the pooled tokens of two detectors")
+    if args.head_step == "hip" and args.head == "cnn":
+        raise ValueError("--head-step hip --head cnn: the HIP step is the MLP heads' (csrc/binary_head.hip); the CNN decoder "
+                         "already runs its own HIP chain")
+
+
 def main(args):
-    from gw_whisper_amd import dist as gdist, ops, synth
+    check_args(args)
+    from gw_whisper_amd import binary, dist as gdist, ops, roc, synth
     from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
     from gw_whisper_amd.feature_extraction import WhisperFeatureExtractor
-    from gw_whisper_amd.models import TwoChannelLIGOBinaryClassifierCNN, two_channel_ligo_binary_classifier
+    from gw_whisper_amd.models import (TwoChannelLIGOBinaryClassifierCNN, one_channel_ligo_binary_classifier,
+                                       two_channel_ligo_binary_classifier)
     from gw_whisper_amd.peft import LoraConfig, get_peft_model
     rank, world, local = gdist.init()
     assert torch.cuda.is_available(), "run_train.py needs an MI355X (gw_whisper_amd has no CPU path)"
@@ -151,7 +176,10 @@ def main(args):
         for name, p in peft.named_parameters():
             p.requires_grad = "lora" in name
     # src/train.py:23 imports both decoders; --head cnn builds the second one (its HIP chain, forward and backward)
-    model = (TwoChannelLIGOBinaryClassifierCNN(peft) if args.head == "cnn" else two_channel_ligo_binary_classifier(peft)).to(device)
+    if args.detectors == 1:        # sd_train.py:23, :275
+        model = one_channel_ligo_binary_classifier(peft).to(device)
+    else:
+        model = (TwoChannelLIGOBinaryClassifierCNN(peft) if args.head == "cnn" else two_channel_ligo_binary_classifier(peft)).to(device)
     if args.method == "full_finetune":
         for p in model.parameters():   # src/train.py:246-247
             p.requires_grad = True
@@ -168,18 +196,37 @@ def main(args):
     log = open(os.path.join(args.log_dir, "train_log.jsonl"), "a") if rank == 0 else None
 
     def features(idx):
+        if args.detectors == 1:    # one_channel_LigoBinaryData: the L1 strain alone
+            return (ops.logmel(torch.from_numpy(l1[idx]).to(device), n_mels=n_mels),)
         w = torch.from_numpy(np.concatenate((h1[idx], l1[idx]))).to(device)
         mel = ops.logmel(w, n_mels=n_mels)
         return mel[: len(idx)], mel[len(idx):]
 
+    def evaluate_hip():
+        """The validation pass without a host read per batch: the state lives on the device, ``read`` is the one copy."""
+        model.eval()
+        state = roc.BinaryEvalState(max(len(val_idx), 1), device, with_snr=False)
+        with torch.no_grad():
+            for i in range(0, len(val_idx), args.batch_size):
+                idx = val_idx[i:i + args.batch_size]
+                state.add(binary.head_logits(model.classifier, model.pooled(*features(idx))),
+                          torch.from_numpy(labels[idx]).to(device))
+        r = state.read()
+        auc = float("nan")
+        if len(set(r["labels"].tolist())) > 1:
+            from sklearn.metrics import roc_auc_score
+            auc = float(roc_auc_score(r["labels"], r["scores"]))
+        return r["loss"], auc
+
     def evaluate():
+        if args.head_step == "hip":
+            return evaluate_hip()
         model.eval()
         tot, cnt, probs, ys = 0.0, 0, [], []
         with torch.no_grad():
             for i in range(0, len(val_idx), args.batch_size):
                 idx = val_idx[i:i + args.batch_size]
-                a, b = features(idx)
-                out = model(a, b)
+                out = model(*features(idx))
                 y = torch.from_numpy(labels[idx]).view(-1, 1).to(device)
                 tot += criterion(out, y).item() * len(idx)
                 cnt += len(idx)
@@ -201,7 +248,7 @@ def main(args):
     for epoch in range(args.num_epochs):
         model.train()
         order = np.random.default_rng(args.seed + 1 + epoch).permutation(train_idx)
-        t0, run, nb, seen = time.time(), 0.0, 0, 0
+        t0, run, nb, seen, step_losses = time.time(), 0.0, 0, 0, []
         # every rank runs the SAME number of steps (one all-reduce each); the bucket takes the SAMPLE-weighted mean over
         # the ranks (a rank without a batch in the last step contributes zero samples), i.e. the gradient of the mean loss
         # over the whole global batch whatever the number of ranks
@@ -210,15 +257,21 @@ def main(args):
             bucket.zero()
             if sl is not None:
                 idx = order[sl[0]:sl[1]]
-                a, b = features(idx)
                 y = torch.from_numpy(labels[idx]).view(-1, 1).to(device)
-                loss = criterion(model(a, b), y)
-                loss.backward()
-                run += loss.item()
+                if args.head_step == "hip":
+                    loss, _ = binary.head_bce_with_logits(model.classifier, model.pooled(*features(idx)), y)
+                    loss.backward()
+                    step_losses.append(loss.detach())
+                else:
+                    loss = criterion(model(*features(idx)), y)
+                    loss.backward()
+                    run += loss.item()
                 nb += 1
                 seen += len(idx)
             bucket.all_reduce_mean(world, n_local=0 if sl is None else sl[1] - sl[0])
             optimizer.step()
+        if step_losses:            # the epoch's one read of the step losses (summed in fp64, as the host sum of .item()s is)
+            run = float(torch.stack(step_losses).double().sum())
         train_loss = run / max(nb, 1)
         val_loss, val_auc = evaluate()
         val_loss = gdist.broadcast_scalar(val_loss, world, device)     # one decision for all ranks
@@ -252,7 +305,7 @@ def _resume_path(base: str, name: str) -> str:
     raise FileNotFoundError(f"neither {base + name!r} nor {os.path.join(base, name)!r} exists")
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(description="Training pipeline for the LIGO binary classification model (MI355X path)")
     parser.add_argument("--data-path", type=str, default="Detection/data/Whisper_train_mass-8to100_resampled_train")
     parser.add_argument("--models-path", type=str, default="Detection/results/Two_detectors/models")
@@ -282,4 +335,14 @@ if __name__ == "__main__":
     parser.add_argument("--head", choices=("mlp", "cnn"), default="mlp",
                         help="the decoder: two_channel_ligo_binary_classifier's MLP (default) or "
                              "TwoChannelLIGOBinaryClassifierCNN, whose best_dense_layers artefact is the CNN's state_dict")
-    main(parser.parse_args())
+    parser.add_argument("--detectors", type=int, choices=(2, 1), default=2,
+                        help="2: src/train.py (H1 + L1, two_channel_ligo_binary_classifier, the default); 1: src/sd_train.py "
+                             "(L1 only, one_channel_ligo_binary_classifier)")
+    parser.add_argument("--head-step", choices=("torch", "hip"), default="torch",
+                        help="the MLP head's forward + BCEWithLogitsLoss + backward: torch.nn (default) or one HIP step with a "
+                             "sync-free loop around it (validation loss: sum of batch means / batches)")
+    return parser
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

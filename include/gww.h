@@ -865,6 +865,41 @@ int gww_cnn_head_backward_f32(const float* x, const float* saved, const float* d
                               size_t workspace_bytes, void* stream);
 /* fp32 -> bf16 (round to nearest even), n elements */
 int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
+/* Binary head step of the signal-vs-noise trainers (binary_head.hip; the conventions of the detection head: exact fp32
+ * MFMA chains, no float atomics, identical calls give identical bits, plain launches, no synchronisation).  Two layouts of
+ * the reference's Signal_vs_Noise/src/model.py, ReLU between the layers, BCEWithLogitsLoss against targets [B, C] (float in
+ * [0, 1]):
+ *   GWW_BIN_HEAD_ONE  one_channel_ligo_binary_classifier: x [B, d_in] -> 512 -> 256 -> 128 -> 64 -> C, five layers,
+ *                     d_in a multiple of 128 in 128..1280
+ *   GWW_BIN_HEAD_TWO  two_channel_ligo_binary_classifier: x [B, d_in] -> 1024 -> 512 -> 256 -> C, four layers, d_in a
+ *                     multiple of 256 in 256..2560; w5, b5, h4, dw5, db5 are ignored (pass NULL)
+ * C 1..64, B 1..65536; w_i [out, in] and b_i [out] as nn.Linear stores them; x, w_i, the hidden layers' b_i, h_i, ws, dx
+ * and dw_i 16-byte aligned.
+ * Forward (2 launches): writes the post-ReLU activations h_i [B, width_i], logits [B, C], probs [B, C] = sigmoid(z),
+ * row_loss [B] = sum over c of max(z, 0) - z t + log1p(exp(-|z|)) (torch's form), the device scalar loss = sum(row_loss) /
+ * (B C) (fp64 partial sums in a fixed tree, rounded once) and dz [B, C] = (sigmoid(z) - t) / (B C), formed as
+ * ((1 - t) p - t (1 - p)) / (B C) with 1 - p from the exponential, never by subtraction.  Everything behind the fp32
+ * logits is evaluated in fp64 and rounded to fp32 once per output.  At equal weights and C the logits of GWW_BIN_HEAD_ONE
+ * are the bits of gww_det_head_forward_f32's.
+ * Backward (2 launches): reads the upstream gradient of the loss from the device scalar dloss (NULL: 1), writes
+ * dx [B, d_in] and every parameter gradient (not accumulated); ws: gww_bin_head_workspace_bytes(layout, B, C) bytes (0 for
+ * an unknown layout), refused before any launch when ws_bytes is smaller.
+ * Scores (1 launch, inference only): logits [B, C], bit for bit the forward's. */
+#define GWW_BIN_HEAD_ONE 1
+#define GWW_BIN_HEAD_TWO 2
+int gww_bin_head_forward_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                             const float* b5, const float* targets, int B, int d_in, int C, float* h1, float* h2, float* h3,
+                             float* h4, float* logits, float* probs, float* row_loss, float* dz, float* loss, void* stream);
+size_t gww_bin_head_workspace_bytes(int layout, int B, int C);
+int gww_bin_head_backward_f32(int layout, const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
+                              const float* w5, const float* h1, const float* h2, const float* h3, const float* h4,
+                              const float* dz, const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes,
+                              float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dw4,
+                              float* db4, float* dw5, float* db5, void* stream);
+int gww_bin_head_scores_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
+                            const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
+                            const float* b5, int B, int d_in, int C, float* logits, void* stream);
 
 #ifdef __cplusplus
 }
