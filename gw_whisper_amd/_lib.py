@@ -57,6 +57,11 @@ class DoraMergeItem(C.Structure):
                 ("norm_out", C.c_void_p), ("scaling", C.c_float), ("d_out", C.c_int), ("d_in", C.c_int), ("r", C.c_int)]
 
 
+class FrontendCfg(C.Structure):
+    _fields_ = [("n_mels", C.c_int), ("sampling_rate", C.c_int), ("n_fft", C.c_int), ("hop_length", C.c_int),
+                ("n_samples", C.c_int), ("min_frequency", C.c_float), ("max_frequency", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/gww.h declares
 SIGNATURES = {
     "gww_version": (C.c_int, []),
@@ -68,6 +73,13 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p]),
     "gww_logmel_host_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]),
     "gww_logmel_host_nmel_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_void_p]),
+    "gww_frontend_validate_cfg": (C.c_int, [C.POINTER(FrontendCfg)]),
+    "gww_frontend_create_cfg": (C.c_int, [C.POINTER(FrontendCfg), C.POINTER(C.c_void_p)]),
+    "gww_frontend_frames": (C.c_int, [C.c_void_p]),
+    "gww_frontend_mel_filters_f32": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gww_frontend_mel_filters_host_f32": (C.c_int, [C.POINTER(FrontendCfg), C.c_void_p]),
+    "gww_frontend_set_general": (C.c_int, [C.c_void_p, C.c_int]),
+    "gww_logmel_host_cfg_f32": (C.c_int, [C.POINTER(FrontendCfg), C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]),
     "gww_encoder_create": (C.c_int, [C.POINTER(EncCfg), C.POINTER(C.c_void_p)]),
     "gww_encoder_destroy": (None, [C.c_void_p]),
     "gww_encoder_set_weights": (C.c_int, [C.c_void_p, C.POINTER(EncGlobals), C.POINTER(EncLayer),

@@ -14,6 +14,22 @@ int launch_layernorm_rows(const float* x, long row_stride, const float* w, const
 int launch_pack_weight(const float* w, void* out, int out_bf16, int N, int C, int taps, int Kpad,
                        float scale, hipStream_t s);
 
+// ---- the front end of any configuration: logmel_host.cpp (plain C++: the supported set, the frame arithmetic and the
+// tables, shared by both twins), logmel_any.hip
+int frontend_validate(const gww_frontend_cfg* c, const char* who);
+int frontend_live_frames(const gww_frontend_cfg* c, int n_eff);
+void frontend_tables(const gww_frontend_cfg* c, float* win, float* cost, float* sint, float* fbT);
+struct LogmelAnyPlan {
+  int n_mels, n_fft, hop, chunk, n_frames;
+  int S;               // row stride of the folded frames in LDS: n_fft / 2 + 1 rounded up to 4
+  int ft, groups;      // frames per thread (8 or 4), thread groups per workgroup (1, 2 or 4)
+  size_t lds_bytes;
+};
+int logmel_any_plan(const gww_frontend_cfg* c, LogmelAnyPlan* p);
+// tables: win | cost | sint [n_fft] each, then fbT [n_fft / 2 + 1][n_mels] (device)
+int launch_logmel_any(const LogmelAnyPlan& p, const float* tables, const float* wave, int n_seg, int n_eff, int live,
+                      long wave_stride, float* out, float* seg_max, hipStream_t s);
+
 // ---- the conv stem: conv1_mel.hip, stem_tail.hip, gemm_bf16.hip
 bool conv1_mel_supported(int n_mels, int d, int kpad);
 int launch_conv1_mel(const float* mel, const void* W, const float* bias, void* c1, int B, int T, int d, hipStream_t s,

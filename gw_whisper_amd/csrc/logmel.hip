@@ -365,6 +365,10 @@ struct gww_frontend {
   Tables tb{};
   float* blob = nullptr;
   int n_mels = 80;
+  // the configuration; `published`: Whisper's own (the kernels above), `general`: run logmel_any.hip's kernels
+  gww_frontend_cfg cfg{80, 16000, kNfft, kHop, kChunk, 0.0f, 8000.0f};
+  bool published = true, general = false;
+  LogmelAnyPlan plan{};
 };
 
 extern "C" int gww_frontend_create_nmel(int n_mels, gww_frontend** out) {
@@ -395,6 +399,11 @@ extern "C" int gww_frontend_create_nmel(int n_mels, gww_frontend** out) {
   }
   gww_frontend* fe = new gww_frontend();
   fe->n_mels = n_mels;
+  fe->cfg.n_mels = n_mels;
+  if (logmel_any_plan(&fe->cfg, &fe->plan) != GWW_OK) {
+    delete fe;
+    return GWW_ERR_ARG;
+  }
   hipError_t e = hipMalloc(&fe->blob, h.size() * sizeof(float));
   if (e != hipSuccess) {
     delete fe;
@@ -415,6 +424,65 @@ extern "C" int gww_frontend_create_nmel(int n_mels, gww_frontend** out) {
 }
 
 extern "C" int gww_frontend_create(gww_frontend** out) { return gww_frontend_create_nmel(80, out); }
+
+extern "C" int gww_frontend_create_cfg(const gww_frontend_cfg* cfg, gww_frontend** out) {
+  GWW_REQUIRE(out != nullptr, "gww_frontend_create_cfg: out is NULL");
+  GWW_TRY(frontend_validate(cfg, "gww_frontend_create_cfg"));
+  if (cfg->sampling_rate == 16000 && cfg->n_fft == kNfft && cfg->hop_length == kHop && cfg->n_samples == kChunk &&
+      cfg->min_frequency == 0.0f && cfg->max_frequency == 8000.0f)
+    return gww_frontend_create_nmel(cfg->n_mels, out);   // the published configuration: the same handle, tables and kernels
+  gww_frontend* fe = new gww_frontend();
+  fe->cfg = *cfg;
+  fe->n_mels = cfg->n_mels;
+  fe->published = false;
+  fe->general = true;
+  if (logmel_any_plan(cfg, &fe->plan) != GWW_OK) {
+    delete fe;
+    return GWW_ERR_ARG;
+  }
+  const int N = cfg->n_fft, nfreq = N / 2 + 1;
+  std::vector<float> h(3 * (size_t)N + (size_t)nfreq * cfg->n_mels);
+  frontend_tables(cfg, h.data(), h.data() + N, h.data() + 2 * N, h.data() + 3 * N);
+  hipError_t e = hipMalloc(&fe->blob, h.size() * sizeof(float));
+  if (e != hipSuccess) {
+    delete fe;
+    return fail(GWW_ERR_HIP, "hipMalloc(frontend tables) failed: %s", hipGetErrorString(e));
+  }
+  e = hipMemcpy(fe->blob, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipFree(fe->blob);
+    delete fe;
+    return fail(GWW_ERR_HIP, "hipMemcpy(frontend tables) failed: %s", hipGetErrorString(e));
+  }
+  fe->tb.win = fe->blob;
+  fe->tb.cost = fe->blob + N;
+  fe->tb.sint = fe->blob + 2 * N;
+  fe->tb.fbT = fe->blob + 3 * N;
+  *out = fe;
+  return GWW_OK;
+}
+
+extern "C" int gww_frontend_frames(const gww_frontend* fe) {
+  GWW_REQUIRE(fe != nullptr, "gww_frontend_frames: NULL handle");
+  return fe->cfg.n_samples / fe->cfg.hop_length;
+}
+
+extern "C" int gww_frontend_mel_filters_f32(const gww_frontend* fe, float* out) {
+  GWW_REQUIRE(fe && out, "gww_frontend_mel_filters_f32: NULL argument");
+  const int nfreq = fe->cfg.n_fft / 2 + 1, nm = fe->n_mels;
+  std::vector<float> h((size_t)nfreq * nm);
+  GWW_HIP(hipMemcpy(h.data(), fe->tb.fbT, h.size() * sizeof(float), hipMemcpyDeviceToHost));
+  for (int k = 0; k < nfreq; ++k)
+    for (int m = 0; m < nm; ++m) out[(size_t)m * nfreq + k] = h[(size_t)k * nm + m];
+  return GWW_OK;
+}
+
+extern "C" int gww_frontend_set_general(gww_frontend* fe, int on) {
+  GWW_REQUIRE(fe != nullptr, "gww_frontend_set_general: NULL handle");
+  GWW_REQUIRE(on || fe->published, "gww_frontend_set_general: only the published configuration has other kernels");
+  fe->general = on != 0;
+  return GWW_OK;
+}
 
 extern "C" void gww_frontend_destroy(gww_frontend* fe) {
   if (!fe) return;
@@ -447,6 +515,14 @@ extern "C" int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, in
                               long wave_stride, float* out, float* seg_max, void* stream) {
   GWW_REQUIRE(fe && wave && out && seg_max, "gww_logmel_f32: NULL argument");
   GWW_REQUIRE(n_seg >= 0 && n_samples >= 0, "gww_logmel_f32: negative size");
+  if (fe->general) {
+    const int chunk = fe->cfg.n_samples, n_eff = n_samples < chunk ? n_samples : chunk;   // HF truncates at chunk_length
+    GWW_REQUIRE(wave_stride >= n_eff, "gww_logmel_f32: wave_stride %ld < n_samples %d", wave_stride, n_samples);
+    if (n_seg == 0) return GWW_OK;
+    GWW_HIP(hipMemsetAsync(seg_max, 0, sizeof(float) * (size_t)n_seg, (hipStream_t)stream));
+    return launch_logmel_any(fe->plan, fe->blob, wave, n_seg, n_eff, frontend_live_frames(&fe->cfg, n_eff), wave_stride, out,
+                             seg_max, (hipStream_t)stream);
+  }
   GWW_REQUIRE(wave_stride >= (n_samples < kChunk ? n_samples : kChunk),
               "gww_logmel_f32: wave_stride %ld < n_samples %d", wave_stride, n_samples);
   if (n_seg == 0) return GWW_OK;

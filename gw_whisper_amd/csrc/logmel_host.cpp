@@ -198,3 +198,212 @@ extern "C" int gww_logmel_host_nmel_f32(const float* wave, int n_seg, int n_samp
 extern "C" int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out) {
   return gww_logmel_host_nmel_f32(wave, n_seg, n_samples, wave_stride, 80, out);
 }
+
+// ---- any configuration (HF: WhisperFeatureExtractor(feature_size, sampling_rate, hop_length, chunk_length, n_fft)) ----
+// The supported set, the frame arithmetic and the tables are defined once, here, in plain C++: the device handle
+// (logmel.hip) calls the same three functions, so both twins hold one window and one filterbank.
+namespace gww {
+
+// GWW_OK, or GWW_ERR_ARG with a message that names the offending field
+int frontend_validate(const gww_frontend_cfg* c, const char* who) {
+  if (!c) return fail(GWW_ERR_ARG, "%s: cfg is NULL", who);
+  if (c->n_mels != 80 && c->n_mels != 128) return fail(GWW_ERR_ARG, "%s: n_mels=%d (80 or 128)", who, c->n_mels);
+  if (c->sampling_rate < 2) return fail(GWW_ERR_ARG, "%s: sampling_rate=%d must be at least 2", who, c->sampling_rate);
+  if (c->n_fft < 16 || c->n_fft > 1024 || c->n_fft % 2)
+    return fail(GWW_ERR_ARG, "%s: n_fft=%d must be even and in [16, 1024]", who, c->n_fft);
+  if (c->hop_length < 1 || c->hop_length > c->n_fft)
+    return fail(GWW_ERR_ARG, "%s: hop_length=%d must be in [1, n_fft=%d]", who, c->hop_length, c->n_fft);
+  if (c->n_samples <= c->n_fft / 2)
+    return fail(GWW_ERR_ARG, "%s: n_samples=%d must exceed n_fft / 2 = %d (the reflect pad)", who, c->n_samples, c->n_fft / 2);
+  const long frames = (long)c->n_samples / c->hop_length;
+  if (frames < 1 || frames > 3000)
+    return fail(GWW_ERR_ARG, "%s: n_frames=%ld (n_samples / hop_length) must be in [1, 3000]", who, frames);
+  if (!(c->min_frequency >= 0.0f)) return fail(GWW_ERR_ARG, "%s: min_frequency=%g must be >= 0", who, (double)c->min_frequency);
+  if (!(c->max_frequency > c->min_frequency))
+    return fail(GWW_ERR_ARG, "%s: max_frequency=%g must exceed min_frequency=%g", who, (double)c->max_frequency,
+                (double)c->min_frequency);
+  return GWW_OK;
+}
+
+// frames that can see a non-zero sample of an input of n_eff samples: frame t covers [hop t - n_fft / 2, hop t + n_fft / 2)
+// of the zero-padded buffer; the reflection at its far end reaches back less than n_fft samples
+int frontend_live_frames(const gww_frontend_cfg* c, int n_eff) {
+  const int frames = c->n_samples / c->hop_length;
+  if (n_eff >= c->n_samples - c->n_fft) return frames;
+  long live = ((long)n_eff + c->n_fft / 2 + c->hop_length - 1) / c->hop_length;
+  if (live > frames) live = frames;
+  if (live < 1) live = 1;
+  return (int)live;
+}
+
+// win / cost / sint [n_fft]: the periodic Hann and the twiddles, rounded to fp32 once; fbT [n_fft / 2 + 1][n_mels]: HF's
+// mel_filter_bank(n_fft / 2 + 1, n_mels, min_frequency, max_frequency, sampling_rate, "slaney", "slaney"), rounded to fp32
+void frontend_tables(const gww_frontend_cfg* c, float* win, float* cost, float* sint, float* fbT) {
+  const int N = c->n_fft, nfreq = N / 2 + 1, nm = c->n_mels;
+  for (int k = 0; k < N; ++k) {
+    win[k] = (float)(0.5 - 0.5 * cos(2.0 * kPi * k / N));
+    if (cost) cost[k] = (float)cos(2.0 * kPi * k / N);
+    if (sint) sint[k] = (float)sin(2.0 * kPi * k / N);
+  }
+  const double mel_min = HostTables::hz2mel((double)c->min_frequency), mel_max = HostTables::hz2mel((double)c->max_frequency);
+  std::vector<double> ff(nm + 2);
+  for (int i = 0; i < nm + 2; ++i) ff[i] = HostTables::mel2hz(mel_min + (mel_max - mel_min) * i / (nm + 1));
+  const double nyq = (double)(c->sampling_rate / 2);   // HF: linspace(0, sampling_rate // 2, n_freq)
+  for (int k = 0; k < nfreq; ++k) {
+    const double fk = nyq * k / (nfreq - 1);
+    for (int m = 0; m < nm; ++m) {
+      const double down = (fk - ff[m]) / (ff[m + 1] - ff[m]);
+      const double up = (ff[m + 2] - fk) / (ff[m + 2] - ff[m + 1]);
+      double v = down < up ? down : up;
+      if (v < 0) v = 0;
+      v *= 2.0 / (ff[m + 2] - ff[m]);
+      fbT[(size_t)k * nm + m] = (float)v;
+    }
+  }
+}
+
+}  // namespace gww
+
+namespace {
+
+// out[0..n) = DFT_n(in[0], in[stride], ...) by decimation in time over the prime factors of n (4 before 2); n divides H,
+// w[k] = exp(-2 pi i k / H); t: scratch for one butterfly (the largest prime factor of H)
+void fft_any(int n, const Cpx* in, long stride, Cpx* out, const Cpx* w, int H, Cpx* t) {
+  if (n == 1) {
+    out[0] = in[0];
+    return;
+  }
+  int p = n;
+  if (n % 4 == 0) p = 4;
+  else if (n % 2 == 0) p = 2;
+  else
+    for (int q = 3; q * q <= n; q += 2)
+      if (n % q == 0) {
+        p = q;
+        break;
+      }
+  const int m = n / p;
+  for (int q = 0; q < p; ++q) fft_any(m, in + (long)q * stride, stride * p, out + q * m, w, H, t);
+  const int tw = H / n, tp = H / p;
+  for (int k = 0; k < m; ++k) {
+    for (int q = 0; q < p; ++q) {
+      const Cpx a = out[q * m + k];
+      const Cpx ww = w[(int)(((long)q * k * tw) % H)];
+      t[q] = {a.re * ww.re - a.im * ww.im, a.re * ww.im + a.im * ww.re};
+    }
+    for (int r = 0; r < p; ++r) {
+      double sr = t[0].re, si = t[0].im;
+      for (int q = 1; q < p; ++q) {
+        const Cpx ww = w[(int)(((long)q * r) % p) * tp];
+        sr += t[q].re * ww.re - t[q].im * ww.im;
+        si += t[q].re * ww.im + t[q].im * ww.re;
+      }
+      out[k + r * m] = {sr, si};
+    }
+  }
+}
+
+bool is_whisper_default(const gww_frontend_cfg* c) {
+  return c->sampling_rate == 16000 && c->n_fft == kNfft && c->hop_length == kHop && c->n_samples == kChunk &&
+         c->min_frequency == 0.0f && c->max_frequency == 8000.0f;
+}
+
+}  // namespace
+
+extern "C" int gww_frontend_validate_cfg(const gww_frontend_cfg* cfg) {
+  return gww::frontend_validate(cfg, "gww_frontend_validate_cfg");
+}
+
+extern "C" int gww_frontend_mel_filters_host_f32(const gww_frontend_cfg* cfg, float* out) {
+  if (int rc = gww::frontend_validate(cfg, "gww_frontend_mel_filters_host_f32")) return rc;
+  if (!out) return gww::fail(GWW_ERR_ARG, "gww_frontend_mel_filters_host_f32: out is NULL");
+  const int N = cfg->n_fft, nfreq = N / 2 + 1, nm = cfg->n_mels;
+  std::vector<float> win(N), fb((size_t)nfreq * nm);
+  gww::frontend_tables(cfg, win.data(), nullptr, nullptr, fb.data());
+  for (int k = 0; k < nfreq; ++k)
+    for (int m = 0; m < nm; ++m) out[(size_t)m * nfreq + k] = fb[(size_t)k * nm + m];
+  return GWW_OK;
+}
+
+extern "C" int gww_logmel_host_cfg_f32(const gww_frontend_cfg* cfg, const float* wave, int n_seg, int n_samples_in,
+                                       long wave_stride, float* out) {
+  const char* who = "gww_logmel_host_cfg_f32";
+  if (int rc = gww::frontend_validate(cfg, who)) return rc;
+  if (!wave || !out) return gww::fail(GWW_ERR_ARG, "%s: NULL argument", who);
+  if (n_seg < 0 || n_samples_in < 0) return gww::fail(GWW_ERR_ARG, "%s: negative size", who);
+  // Whisper's published configuration keeps its own 200-point FFT and tables: one result, bit for bit, by either entry
+  if (is_whisper_default(cfg)) return gww_logmel_host_nmel_f32(wave, n_seg, n_samples_in, wave_stride, cfg->n_mels, out);
+  const int N = cfg->n_fft, H = N / 2, nfreq = H + 1, hop = cfg->hop_length, chunk = cfg->n_samples, nm = cfg->n_mels;
+  const int frames = chunk / hop;
+  const int n_eff = n_samples_in < chunk ? n_samples_in : chunk;   // HF truncates at chunk_length
+  if (wave_stride < n_eff) return gww::fail(GWW_ERR_ARG, "%s: wave_stride %ld < n_samples %d", who, wave_stride, n_samples_in);
+  const int live = gww::frontend_live_frames(cfg, n_eff);
+
+  std::vector<float> win32(N), fb((size_t)nfreq * nm);
+  gww::frontend_tables(cfg, win32.data(), nullptr, nullptr, fb.data());
+  std::vector<int> fb_first(nfreq, 0), fb_count(nfreq, 0);      // the non-zero run of mels per bin
+  for (int k = 0; k < nfreq; ++k) {
+    int first = -1, last = -1;
+    for (int m = 0; m < nm; ++m)
+      if (fb[(size_t)k * nm + m] != 0.0f) {
+        if (first < 0) first = m;
+        last = m;
+      }
+    if (first >= 0) {
+      fb_first[k] = first;
+      fb_count[k] = last - first + 1;
+    }
+  }
+  std::vector<Cpx> wH(H), wN(H + 1), z(H), Z(H), scratch(H);
+  for (int k = 0; k < H; ++k) wH[k] = {cos(2.0 * kPi * k / H), -sin(2.0 * kPi * k / H)};
+  for (int k = 0; k <= H; ++k) wN[k] = {cos(2.0 * kPi * k / N), -sin(2.0 * kPi * k / N)};
+  std::vector<double> frame(N), mel(nm);
+  std::vector<float> raw((size_t)nm * live);
+
+  for (int s = 0; s < n_seg; ++s) {
+    const float* x = wave + (long)s * wave_stride;
+    float* o = out + (size_t)s * nm * frames;
+    auto sample = [&](long j) -> double {        // padded index j <-> buffer index j - n_fft / 2, reflected once
+      long i = j - H;
+      if (i < 0) i = -i;
+      if (i >= chunk) i = 2L * (chunk - 1) - i;
+      return i < n_eff ? (double)x[i] : 0.0;
+    };
+    float seg_max = -INFINITY;
+    for (int t = 0; t < live; ++t) {
+      for (int n = 0; n < N; ++n) frame[n] = sample((long)t * hop + n) * (double)win32[n];
+      for (int n = 0; n < H; ++n) z[n] = {frame[2 * n], frame[2 * n + 1]};
+      fft_any(H, z.data(), 1, Z.data(), wH.data(), H, scratch.data());
+      for (int m = 0; m < nm; ++m) mel[m] = 0.0;
+      for (int k = 0; k <= H; ++k) {
+        const Cpx a = Z[k % H];
+        const Cpx b = {Z[(H - k) % H].re, -Z[(H - k) % H].im};
+        const Cpx e = {0.5 * (a.re + b.re), 0.5 * (a.im + b.im)};
+        const Cpx od = {0.5 * (a.im - b.im), -0.5 * (a.re - b.re)};
+        const Cpx w = wN[k];
+        const double re = e.re + od.re * w.re - od.im * w.im;
+        const double im = e.im + od.re * w.im + od.im * w.re;
+        const float pk = (float)(re * re + im * im);          // HF's magnitudes are fp32
+        const float* v = fb.data() + (size_t)k * nm + fb_first[k];
+        for (int c = 0; c < fb_count[k]; ++c) mel[fb_first[k] + c] += (double)v[c] * (double)pk;
+      }
+      for (int m = 0; m < nm; ++m) {
+        float v = (float)mel[m];
+        if (v < 1e-10f) v = 1e-10f;
+        const float lg = (float)log10((double)v);
+        raw[(size_t)m * live + t] = lg;
+        if (lg > seg_max) seg_max = lg;
+      }
+    }
+    if (live < frames && -10.0f > seg_max) seg_max = -10.0f;   // the dead frames' log10(1e-10) takes part in the max
+    const float floor_v = seg_max - 8.0f;
+    const float dead = ((-10.0f > floor_v ? -10.0f : floor_v) + 4.0f) / 4.0f;
+    for (int m = 0; m < nm; ++m) {
+      float* row = o + (size_t)m * frames;
+      const float* r = raw.data() + (size_t)m * live;
+      for (int t = 0; t < live; ++t) row[t] = ((r[t] > floor_v ? r[t] : floor_v) + 4.0f) / 4.0f;
+      for (int t = live; t < frames; ++t) row[t] = dead;
+    }
+  }
+  return GWW_OK;
+}

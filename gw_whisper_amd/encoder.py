@@ -19,6 +19,10 @@ Mirrors the HuggingFace surface the reference uses:
   (``.hidden_states``: L + 1 tensors ``[B, 1500, d]``, ``.attentions``: L tensors ``[B, H, 1500, 1500]``, eager
   attention's ``attn_weights``), inference only; ``return_dict=False`` returns HF's plain tuple.
 
+The context is HF's ``max_source_positions``: ``WhisperConfig(max_source_positions=T)`` for any ``T`` in [16, 1500] takes
+``[B, num_mel_bins, 2 T]`` features (a ``WhisperFeatureExtractor`` of the matching ``chunk_length`` / ``hop_length`` makes
+them) and returns ``[B, T, d]``; ``with_context(T)`` cuts a longer encoder to it.
+
 The submodules hold parameters only; all arithmetic runs in the HIP library.
 Calling the module with CPU tensors raises -- there is no CPU fallback.
 """
@@ -233,8 +237,14 @@ def _bias(linear):
 class WhisperEncoder(nn.Module):
     """Parameter container + launcher for the HIP encoder forward."""
 
+    MIN_CONTEXT, MAX_CONTEXT = 16, 1500   # supported max_source_positions (DESIGN.md: the route each (d, T) takes)
+
     def __init__(self, config: WhisperConfig, precision: str = "bf16"):
         super().__init__()
+        T = config.max_source_positions
+        if int(T) != T or not self.MIN_CONTEXT <= T <= self.MAX_CONTEXT:
+            raise ValueError(f"WhisperEncoder: max_source_positions={T!r} must be an integer in "
+                             f"[{self.MIN_CONTEXT}, {self.MAX_CONTEXT}]")
         self.config = config
         d = config.d_model
         self.conv1 = nn.Conv1d(config.num_mel_bins, d, kernel_size=3, padding=1)
@@ -278,6 +288,16 @@ class WhisperEncoder(nn.Module):
     def _has_adapters(self) -> bool:
         return bool(self._param_cache().adapters)
 
+    def config_dict(self) -> dict:
+        """The encoder's ``config.json`` with HF WhisperConfig field names (what :meth:`save_pretrained` writes and
+        ``WhisperConfig.from_json_file`` reads)."""
+        c = self.config
+        return {"model_type": "whisper", "architectures": ["WhisperEncoder"], "d_model": c.d_model,
+                "encoder_layers": c.encoder_layers, "encoder_attention_heads": c.encoder_attention_heads,
+                "encoder_ffn_dim": c.encoder_ffn_dim, "num_mel_bins": c.num_mel_bins,
+                "max_source_positions": c.max_source_positions, "dropout": c.dropout, "activation_function": "gelu",
+                "scale_embedding": False, "torch_dtype": "float32"}
+
     def save_pretrained(self, save_directory: str):
         """HF ``WhisperEncoder.save_pretrained`` layout (Signal_vs_Noise/src/train.py:196 saves a fully fine-tuned
         encoder this way): ``config.json`` with WhisperConfig field names and ``model.safetensors`` whose keys are the
@@ -289,12 +309,7 @@ class WhisperEncoder(nn.Module):
         if self._has_adapters():
             raise _lib.GwwError("save_pretrained() of an adapted encoder: save the adapter through the PeftModel")
         os.makedirs(save_directory, exist_ok=True)
-        c = self.config
-        cfg = {"model_type": "whisper", "architectures": ["WhisperEncoder"], "d_model": c.d_model,
-               "encoder_layers": c.encoder_layers, "encoder_attention_heads": c.encoder_attention_heads,
-               "encoder_ffn_dim": c.encoder_ffn_dim, "num_mel_bins": c.num_mel_bins,
-               "max_source_positions": c.max_source_positions, "dropout": c.dropout, "activation_function": "gelu",
-               "scale_embedding": False, "torch_dtype": "float32"}
+        cfg = self.config_dict()
         with open(os.path.join(save_directory, "config.json"), "w") as f:
             json.dump(cfg, f, indent=2, sort_keys=True)
         sd = {k: v.detach().to("cpu", torch.float32).contiguous() for k, v in self.state_dict().items()}
@@ -305,15 +320,52 @@ class WhisperEncoder(nn.Module):
             p.requires_grad = False
 
     @staticmethod
-    def from_pretrained(save_directory: str, **kw) -> "WhisperEncoder":
+    def from_pretrained(save_directory: str, max_source_positions: int | None = None, **kw) -> "WhisperEncoder":
         """Load what :meth:`save_pretrained` wrote: ``config.json`` (geometry and ``num_mel_bins``) and
-        ``model.safetensors``."""
+        ``model.safetensors``.  ``max_source_positions=T`` below the saved context builds the encoder of that context:
+        rows 0 .. T - 1 of the saved position table (what HF users get from ``ignore_mismatched_sizes`` plus a slice)."""
+        import dataclasses
         import os
 
         from safetensors.torch import load_file
-        enc = WhisperEncoder(WhisperConfig.from_json_file(os.path.join(save_directory, "config.json")), **kw)
+        cfg = WhisperConfig.from_json_file(os.path.join(save_directory, "config.json"))
+        if max_source_positions is not None:
+            if max_source_positions > cfg.max_source_positions:
+                raise ValueError(f"WhisperEncoder.from_pretrained: max_source_positions={max_source_positions} exceeds "
+                                 f"the saved position table ({cfg.max_source_positions} rows)")
+            cfg = dataclasses.replace(cfg, max_source_positions=int(max_source_positions))
+        enc = WhisperEncoder(cfg, **kw)
         enc.load_state_dict(load_file(os.path.join(save_directory, "model.safetensors")))
         return enc
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """``nn.Module.load_state_dict``; a position table LONGER than this encoder's context is cut to its rows
+        0 .. T - 1 (the sinusoids of a position do not depend on the table's length).  A shorter one is an error, as ever.
+        The cut is silent, so it also takes a checkpoint loaded into the WRONG encoder -- a 1500-row table into a T = 100
+        encoder built by mistake -- without a word: the context is this encoder's configuration, never the checkpoint's.
+        Where the two are meant to agree, compare ``state_dict["embed_positions.weight"].shape[0]`` with
+        ``config.max_source_positions`` before loading."""
+        key = "embed_positions.weight"
+        pos = state_dict.get(key) if hasattr(state_dict, "get") else None
+        T = self.config.max_source_positions
+        if pos is not None and getattr(pos, "ndim", 0) == 2 and pos.shape[0] > T:
+            state_dict = dict(state_dict)
+            state_dict[key] = pos[:T]
+        return super().load_state_dict(state_dict, *args, **kwargs)
+
+    def with_context(self, max_source_positions: int) -> "WhisperEncoder":
+        """A new encoder of context ``max_source_positions`` <= this one's with the same weights (copies) and rows
+        0 .. T - 1 of ``embed_positions``, on the same device and in the same precision; HF state-dict keys throughout.
+        For an adapted encoder, cut the base first and attach the adapters to the result."""
+        import dataclasses
+        T = int(max_source_positions)
+        if T > self.config.max_source_positions:
+            raise ValueError(f"with_context({T}): this encoder's position table has {self.config.max_source_positions} rows")
+        if self._has_adapters():
+            raise _lib.GwwError("with_context() of an adapted encoder: cut the base encoder, then attach the adapters")
+        enc = WhisperEncoder(dataclasses.replace(self.config, max_source_positions=T), precision=self.precision)
+        enc.load_state_dict(self.state_dict())
+        return enc.to(self.embed_positions.weight.device)
 
     @staticmethod
     def from_numpy_state_dict(sd: dict, config: WhisperConfig, **kw) -> "WhisperEncoder":
@@ -531,6 +583,9 @@ class WhisperEncoder(nn.Module):
         want_a = c.output_attentions if output_attentions is None else bool(output_attentions)
         as_dict = c.return_dict if return_dict is None else bool(return_dict)
         cache = self._enter(input_features)
+        if want_a and c.max_source_positions % 4:
+            raise _lib.GwwError(f"WhisperEncoder: output_attentions needs max_source_positions % 4 == 0 (the attention maps "
+                                f"are stored 16 bytes at a time), got {c.max_source_positions}")
         if self._wants_grad(input_features, cache):
             if want_h or want_a:
                 raise _lib.GwwError("WhisperEncoder: output_hidden_states / output_attentions are inference only (no "

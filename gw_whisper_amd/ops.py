@@ -6,6 +6,8 @@ requires CUDA(HIP) tensors and calls into libgww.so; none has a torch fallback.
 
 from __future__ import annotations
 
+from dataclasses import dataclass
+
 import torch
 
 from . import _lib
@@ -24,21 +26,61 @@ def _dev(t: torch.Tensor, dtype=None, name="tensor") -> torch.Tensor:
     return t.contiguous()
 
 
+@dataclass(frozen=True)
+class FrontendConfig:
+    """One configuration of the log-mel front end (``gww_frontend_cfg`` of include/gww.h): HF's
+    ``WhisperFeatureExtractor(feature_size, sampling_rate, hop_length, chunk_length, n_fft)`` with
+    ``n_samples = chunk_length * sampling_rate``, plus the band of the mel filterbank (HF fixes 0 .. 8000 Hz).  The
+    defaults are Whisper's published configuration.  The library checks the supported set; its message names the field."""
+    n_mels: int = 80
+    sampling_rate: int = 16000
+    n_fft: int = 400
+    hop_length: int = 160
+    n_samples: int = 480000
+    min_frequency: float = 0.0
+    max_frequency: float = 8000.0
+
+    @property
+    def n_frames(self) -> int:
+        return self.n_samples // self.hop_length
+
+    @property
+    def n_freq(self) -> int:
+        return self.n_fft // 2 + 1
+
+    @property
+    def is_published(self) -> bool:
+        return (self.sampling_rate, self.n_fft, self.hop_length, self.n_samples, float(self.min_frequency),
+                float(self.max_frequency)) == (16000, 400, 160, 480000, 0.0, 8000.0)
+
+    def c_struct(self) -> "_lib.FrontendCfg":
+        return _lib.FrontendCfg(int(self.n_mels), int(self.sampling_rate), int(self.n_fft), int(self.hop_length),
+                                int(self.n_samples), float(self.min_frequency), float(self.max_frequency))
+
+
 _frontend = {}
 
 
-def _fe(device, n_mels: int = 80) -> int:
+def _fe(device, n_mels: int = 80, config: FrontendConfig | None = None, general: bool = False) -> int:
+    """The front-end handle of a device: per ``n_mels`` for the published configuration, per configuration otherwise
+    (``general``: the published configuration through the general kernels, a handle of its own -- for tests)."""
     idx = torch.device(device).index or 0
-    if (idx, n_mels) not in _frontend:
+    key = (idx, n_mels) if config is None else (idx, config, bool(general))
+    if key not in _frontend:
         import ctypes as C
         h = C.c_void_p()
         with torch.cuda.device(idx):
-            if n_mels == 80:
+            if config is not None:
+                cfg = config.c_struct()
+                check(lib().gww_frontend_create_cfg(C.byref(cfg), C.byref(h)), "gww_frontend_create_cfg")
+                if general:
+                    check(lib().gww_frontend_set_general(h, 1), "gww_frontend_set_general")
+            elif n_mels == 80:
                 check(lib().gww_frontend_create(C.byref(h)), "gww_frontend_create")
             else:
                 check(lib().gww_frontend_create_nmel(n_mels, C.byref(h)), "gww_frontend_create_nmel")
-        _frontend[(idx, n_mels)] = h
-    return _frontend[(idx, n_mels)]
+        _frontend[key] = h
+    return _frontend[key]
 
 
 def _check_n_mels(n_mels: int) -> None:
@@ -46,47 +88,89 @@ def _check_n_mels(n_mels: int) -> None:
         raise _lib.GwwError(f"n_mels={n_mels}: the Whisper front end has 80 or 128 (large-v3) mel bins")
 
 
-def logmel(wave: torch.Tensor, n_samples: int | None = None, n_mels: int = 80) -> torch.Tensor:
-    """[n, L] fp32 GPU waveform (16 kHz) -> [n, n_mels, 3000] fp32 ``input_features``.
+def logmel(wave: torch.Tensor, n_samples: int | None = None, n_mels: int = 80, config: FrontendConfig | None = None,
+           general: bool = False) -> torch.Tensor:
+    """[n, L] fp32 GPU waveform -> [n, n_mels, n_frames] fp32 ``input_features`` (16 kHz and [n, n_mels, 3000] without
+    ``config``).
 
     Same arithmetic as ``WhisperFeatureExtractor(feature_size=n_mels)(...)`` (reference call site
     Signal_vs_Noise/src/dataset.py:20-21): zero-pad/truncate to 30 s, STFT, mel, log10,
     per-segment dynamic-range clamp, affine.  ``n_mels`` is 80, or 128 for whisper-large-v3.
+    ``config`` (its ``n_mels`` then counts) selects any supported configuration: the published one runs the same kernels
+    as no ``config`` at all, every other one the general kernels of csrc/logmel_any.hip.
     """
+    if config is not None:
+        n_mels = config.n_mels
     _check_n_mels(n_mels)
     if wave.dim() == 1:
         wave = wave[None]
     wave = _dev(wave, torch.float32, "wave")
     n, L = wave.shape
     n_samples = L if n_samples is None else n_samples
-    out = torch.empty((n, n_mels, 3000), dtype=torch.float32, device=wave.device)
+    fe = _fe(wave.device, n_mels, config, general)
+    frames = 3000 if config is None else config.n_frames
+    out = torch.empty((n, n_mels, frames), dtype=torch.float32, device=wave.device)
     seg_max = torch.empty((max(n, 1),), dtype=torch.float32, device=wave.device)
     with torch.cuda.device(wave.device):
         step = 32768   # gridDim.y limit
         for i in range(0, n, step):
             m = min(step, n - i)
-            check(lib().gww_logmel_f32(_fe(wave.device, n_mels), wave[i:].data_ptr(), m, n_samples, wave.stride(0),
+            check(lib().gww_logmel_f32(fe, wave[i:].data_ptr(), m, n_samples, wave.stride(0),
                                        out[i:].data_ptr(), seg_max[i:].data_ptr(), _stream()), "gww_logmel_f32")
     return out
 
 
-def logmel_host(wave, n_samples: int | None = None, n_mels: int = 80) -> torch.Tensor:
-    """CPU twin of :func:`logmel`: [n, L] fp32 host waveform -> [n, n_mels, 3000] fp32 CPU tensor.
+def logmel_host(wave, n_samples: int | None = None, n_mels: int = 80, config: FrontendConfig | None = None) -> torch.Tensor:
+    """CPU twin of :func:`logmel`: [n, L] fp32 host waveform -> [n, n_mels, n_frames] fp32 CPU tensor.
 
-    Runs ``gww_logmel_host_nmel_f32`` (plain C++ inside libgww.so, no HIP call), so it works inside forked DataLoader
+    Runs ``gww_logmel_host_nmel_f32`` (``gww_logmel_host_cfg_f32`` with a ``config``; plain C++ inside libgww.so, no HIP
+    call), so it works inside forked DataLoader
     workers, where the reference calls the extractor (Signal_vs_Noise/src/dataset.py:20-21 under
     src/train.py:224-225).  Not a fallback of the GPU path: callers pick it by handing over host data.
     """
     import numpy as np
+    if config is not None:
+        n_mels = config.n_mels
     _check_n_mels(n_mels)
     w = np.ascontiguousarray(wave.numpy() if isinstance(wave, torch.Tensor) else wave, dtype=np.float32)
     if w.ndim == 1:
         w = w[None]
     n, L = w.shape
     n_samples = L if n_samples is None else n_samples
+    if config is not None:
+        import ctypes as C
+        frontend_validate(config)   # (before anything is allocated: an unsupported n_frames must not size the output)
+        cfg = config.c_struct()
+        out = torch.empty((n, n_mels, config.n_frames), dtype=torch.float32)
+        check(lib().gww_logmel_host_cfg_f32(C.byref(cfg), w.ctypes.data, n, n_samples, max(L, 1) if n else 1,
+                                            out.data_ptr()), "gww_logmel_host_cfg_f32")
+        return out
     out = torch.empty((n, n_mels, 3000), dtype=torch.float32)
     check(lib().gww_logmel_host_nmel_f32(w.ctypes.data, n, n_samples, max(L, 1) if n else 1, n_mels, out.data_ptr()),
           "gww_logmel_host_nmel_f32")
+    return out
+
+
+def frontend_validate(config: FrontendConfig) -> None:
+    """Raise ``GwwError`` (naming the field) unless the library supports ``config``; needs no GPU."""
+    import ctypes as C
+    cfg = config.c_struct()
+    check(lib().gww_frontend_validate_cfg(C.byref(cfg)), "gww_frontend_validate_cfg")
+
+
+def mel_filters(config: FrontendConfig, device=None):
+    """float32 [n_mels, n_fft / 2 + 1]: the filterbank of ``config`` (numpy): the host twin's, or with a CUDA ``device`` the one
+    that device's handle holds."""
+    import ctypes as C
+    import numpy as np
+    frontend_validate(config)
+    out = np.empty((config.n_mels, config.n_freq), np.float32)
+    if device is None or torch.device(device).type == "cpu":
+        cfg = config.c_struct()
+        check(lib().gww_frontend_mel_filters_host_f32(C.byref(cfg), out.ctypes.data), "gww_frontend_mel_filters_host_f32")
+    else:
+        check(lib().gww_frontend_mel_filters_f32(_fe(device, config.n_mels, config), out.ctypes.data),
+              "gww_frontend_mel_filters_f32")
     return out
 
 

@@ -20,7 +20,10 @@ loss and the confusion matrix stay on the device and are read once (``roc.Binary
 the band are computed on the device (``roc.RocEvaluator``) from the resample indices of the host stream the reference
 draws from, so ``--bootstrap_seed S`` gives what the reference gives after ``np.random.seed(S)``; ``--dataset_paths`` are
 the HuggingFace ``datasets`` directories ``run_train.py`` reads, ``--synthetic N`` its seeded synthetic set;
-``--encoder-weights`` / seeded base weights as there.
+``--encoder-weights`` / seeded base weights as there.  Where the adapter directory holds a ``preprocessor_config.json`` and
+a ``config.json`` -- a ``run_train.py`` run with front-end flags writes them -- the features and the encoder's context are
+theirs, ``--synthetic`` segments come at that sampling rate, and the line of ``eval_log.jsonl`` names the context and the
+extractor it used; one of the two files without the other is an error (``saved_front_end``).
 """
 import argparse
 import json
@@ -43,14 +46,45 @@ def load_arrays(path):
             np.asarray(cols["injection_snr"], np.float32))
 
 
+def saved_front_end(model_dir, encoder_name):
+    """(encoder configuration, ``ops.logmel``'s ``config``, sampling rate) of a saved model.  A ``run_train.py`` run with
+    front-end flags left ``preprocessor_config.json`` and the encoder's ``config.json`` beside the adapter: the two are read
+    together or not at all.  A directory that holds one without the other -- a copy that lost a file -- or two that do not
+    fit each other is an error, never a run on Whisper's defaults.  Needs no GPU."""
+    from gw_whisper_amd import synth
+    from gw_whisper_amd.encoder import WhisperConfig
+    from gw_whisper_amd.feature_extraction import WhisperFeatureExtractor
+    config = WhisperConfig.named(encoder_name)
+    pre, cfg_json = (os.path.join(model_dir, n) for n in ("preprocessor_config.json", "config.json"))
+    saved = None
+    if os.path.isfile(cfg_json):
+        saved = WhisperConfig.from_json_file(cfg_json)
+        if (saved.d_model, saved.encoder_layers, saved.encoder_attention_heads, saved.encoder_ffn_dim) != \
+                tuple(synth.ENCODER_SIZES[encoder_name]):
+            raise SystemExit(f"{cfg_json} describes another encoder than --encoder {encoder_name}")
+    if not os.path.isfile(pre):
+        # (a fully fine-tuned encoder of the default context has a config.json and no preprocessor_config.json)
+        if saved is not None and saved.max_source_positions != config.max_source_positions:
+            raise SystemExit(f"{cfg_json} has max_source_positions {saved.max_source_positions} but {pre} is missing: the "
+                             "encoder's front end is unknown")
+        return config, None, 16000
+    if saved is None:
+        raise SystemExit(f"{pre} is there but {cfg_json} is missing: the encoder's context is unknown")
+    extractor = WhisperFeatureExtractor.from_pretrained(model_dir)
+    if extractor.feature_size != saved.num_mel_bins or extractor.nb_max_frames != 2 * saved.max_source_positions:
+        raise SystemExit(f"{pre} gives [{extractor.feature_size}, {extractor.nb_max_frames}] features, {cfg_json} an encoder "
+                         f"of [{saved.num_mel_bins}, {2 * saved.max_source_positions}]")
+    return saved, extractor.frontend_config, extractor.sampling_rate
+
+
 def load_models(args, device):
     """evaluation.py:91-103."""
     from gw_whisper_amd import synth
-    from gw_whisper_amd.encoder import WhisperConfig, WhisperEncoder
+    from gw_whisper_amd.encoder import WhisperEncoder
     from gw_whisper_amd.models import one_channel_ligo_binary_classifier, two_channel_ligo_binary_classifier
     from gw_whisper_amd.peft import PeftModel
     d, L, H, F = synth.ENCODER_SIZES[args.encoder]
-    config = WhisperConfig.named(args.encoder)
+    config, fe_config, rate = saved_front_end(args.lora_weights_path, args.encoder)
     encoder = WhisperEncoder(config, precision=args.precision)
     if args.encoder_weights:
         if args.encoder_weights.endswith(".safetensors"):
@@ -65,10 +99,10 @@ def load_models(args, device):
     head = two_channel_ligo_binary_classifier if args.model_type == "2D" else one_channel_ligo_binary_classifier
     model = head(peft, num_classes=1).to(device)
     model.classifier.load_state_dict(torch.load(args.dense_layers_path, map_location=device))
-    return model.eval(), config.num_mel_bins
+    return model.eval(), config, fe_config, rate
 
 
-def evaluate(model, arrays, args, n_mels, device):
+def evaluate(model, arrays, args, n_mels, device, fe_config=None):
     """One pass in dataset order (evaluation.py:32-64); nothing is read from the device before the pass is over."""
     from gw_whisper_amd import ops, roc
     h1, l1, labels, snr = arrays
@@ -78,11 +112,12 @@ def evaluate(model, arrays, args, n_mels, device):
         for i in range(0, n, args.batch_size):
             sl = slice(i, min(i + args.batch_size, n))
             if args.model_type == "2D":
-                mel = ops.logmel(torch.from_numpy(np.concatenate((h1[sl], l1[sl]))).to(device), n_mels=n_mels)
+                mel = ops.logmel(torch.from_numpy(np.concatenate((h1[sl], l1[sl]))).to(device), n_mels=n_mels,
+                                 config=fe_config)
                 b = sl.stop - sl.start
                 logits = model(mel[:b], mel[b:])
             else:
-                logits = model(ops.logmel(torch.from_numpy(l1[sl]).to(device), n_mels=n_mels))
+                logits = model(ops.logmel(torch.from_numpy(l1[sl]).to(device), n_mels=n_mels, config=fe_config))
             state.add(logits.float(), torch.from_numpy(labels[sl]).to(device), torch.from_numpy(snr[sl]).to(device))
     return state
 
@@ -93,21 +128,22 @@ def main(args):
     device = torch.device("cuda", 0)
     if not args.lora_weights_path or not args.dense_layers_path:
         raise SystemExit("--lora_weights_path and --dense_layers_path are required")
+    if not args.synthetic and not args.dataset_paths:
+        raise SystemExit("--dataset_paths P... is required (or --synthetic N)")
+    model, config, fe_config, rate = load_models(args, device)
+    n_mels = config.num_mel_bins
     if args.synthetic:
         from run_train import synthetic_dataset
-        sets = [synthetic_dataset(args.synthetic, args.seed)]
-    elif args.dataset_paths:
-        sets = [load_arrays(p) for p in args.dataset_paths]
+        sets = [synthetic_dataset(args.synthetic, args.seed, rate)]
     else:
-        raise SystemExit("--dataset_paths P... is required (or --synthetic N)")
-    model, n_mels = load_models(args, device)
+        sets = [load_arrays(p) for p in args.dataset_paths]
     os.makedirs(args.out_dir, exist_ok=True)
     ev = roc.RocEvaluator(num_bootstrap=args.num_bootstrap, seed=args.bootstrap_seed)
     with open(os.path.join(args.out_dir, "eval_log.jsonl"), "a") as log:
         for i, arrays in enumerate(sets):
             if args.model_type == "2D" and arrays[0] is None:
                 raise SystemExit(f"test set {i} has no h1_timeseries column: --model_type 2D needs both detectors")
-            state = evaluate(model, arrays, args, n_mels, device)
+            state = evaluate(model, arrays, args, n_mels, device, fe_config)
             out = ev(state.scores[:state.filled], state.labels[:state.filled])
             res = state.read()
             np.savez(os.path.join(args.out_dir, f"ROC_curve_SNR_{i}_{args.model_type}.npz"), fpr=out["fpr"], tpr=out["tpr"],
@@ -119,6 +155,10 @@ def main(args):
                 f.write(f"\nmacro F1: {f1:.6f}\n")
             rec = {"dataset": i, "n": state.filled, "loss": res["loss"], "auc": out["auc"], "f1": f1,
                    "n_valid": out["n_valid"], "num_bootstrap": args.num_bootstrap}
+            if fe_config is not None:      # the saved front end this run computed its features with
+                rec.update(max_source_positions=config.max_source_positions, sampling_rate=rate, n_fft=fe_config.n_fft,
+                           hop_length=fe_config.hop_length, n_frames=fe_config.n_frames,
+                           max_frequency=fe_config.max_frequency)
             log.write(json.dumps(rec) + "\n")
             log.flush()
             print(f"test set {i}: loss {res['loss']:.4f}, AUC {out['auc']:.4f}, macro F1 {f1:.4f}, "

@@ -70,12 +70,13 @@ DEFAULT_LORA_TARGETS = ("layers.*.self_attn.q_proj", "layers.*.self_attn.k_proj"
                         "layers.*.self_attn.o_proj")
 
 
-def synthetic_dataset(n, seed):
-    """n two-detector 1 s segments at 16 kHz, unit-variance noise; odd indices carry the same chirp in both."""
+def synthetic_dataset(n, seed, rate=16000):
+    """n two-detector 1 s segments at ``rate`` Hz (16 kHz by default), unit-variance noise; odd indices carry the same
+    chirp in both."""
     from gw_whisper_amd import synth
-    h1 = synth.strain_segments(n, seed=seed)
-    l1 = synth.strain_segments(n, seed=seed + 1)
-    t = np.arange(16000, dtype=np.float32) / 16000.0
+    h1 = synth.strain_segments(n, seed=seed, n_samples=rate)
+    l1 = synth.strain_segments(n, seed=seed + 1, n_samples=rate)
+    t = np.arange(rate, dtype=np.float32) / np.float32(rate)
     labels = np.zeros(n, np.float32)
     rng = np.random.default_rng(seed + 2)
     for i in range(1, n, 2):
@@ -90,7 +91,7 @@ def synthetic_dataset(n, seed):
 def load_arrays(args):
     """(h1, l1, labels, snr); h1 is None with --detectors 1 on a dataset directory (sd_train.py never reads it)."""
     if args.synthetic:
-        return synthetic_dataset(args.synthetic, args.seed)
+        return synthetic_dataset(args.synthetic, args.seed, getattr(args, "sampling_rate", 16000))
     from datasets import concatenate_datasets, load_from_disk
     path = args.data_path
     chunks = sorted(p for p in os.listdir(path) if p.startswith("chunk")) if os.path.isdir(path) else []
@@ -109,6 +110,26 @@ def check_args(args):
     if args.head_step == "hip" and args.head == "cnn":
         raise ValueError("--head-step hip --head cnn: the HIP step is the MLP heads' (csrc/binary_head.hip); the CNN decoder "
                          "already runs its own HIP chain")
+
+
+FRONTEND_DEFAULTS = {"sampling_rate": 16000, "n_fft": 400, "hop_length": 160, "chunk_length": 30, "mel_fmax": 8000.0}
+
+
+def frontend_plan(args, n_mels=80):
+    """(extractor keyword arguments, max_source_positions) of the front-end flags, or (None, 1500) when all of them are
+    Whisper's: the run then builds, computes and writes exactly what it did before the flags existed.  The encoder's
+    context is ``chunk_length * sampling_rate // hop_length // 2``; an odd frame count is refused (conv2 halves it), the
+    rest of the supported set is the extractor's to check."""
+    got = {k: getattr(args, k, v) for k, v in FRONTEND_DEFAULTS.items()}
+    if all(float(got[k]) == float(v) for k, v in FRONTEND_DEFAULTS.items()):
+        return None, 1500
+    frames = got["chunk_length"] * got["sampling_rate"] // got["hop_length"] if got["hop_length"] > 0 else 0
+    if frames % 2:
+        raise ValueError(f"--chunk-length {got['chunk_length']} --sampling-rate {got['sampling_rate']} --hop-length "
+                         f"{got['hop_length']}: {frames} frames, an odd count; the encoder's stride-2 conv needs an even one")
+    kw = dict(feature_size=n_mels, sampling_rate=got["sampling_rate"], hop_length=got["hop_length"],
+              chunk_length=got["chunk_length"], n_fft=got["n_fft"], min_frequency=0.0, max_frequency=float(got["mel_fmax"]))
+    return kw, frames // 2
 
 
 def main(args):
@@ -136,6 +157,15 @@ def main(args):
     # src/dataset.py:12 -- the extractor of the same size: 128 mel bins for large-v3 / large-v3-turbo, 80 otherwise
     n_mels = WhisperFeatureExtractor.from_pretrained(f"openai/whisper-{args.encoder}").feature_size
     assert n_mels == config.num_mel_bins
+    # the front-end flags: a configured extractor and an encoder of the matching context (a longer position table of
+    # --encoder-weights, or of the seeded weights, is cut to its first rows by load_state_dict, as with_context does)
+    fe_kw, context = frontend_plan(args, n_mels)
+    extractor, fe_config = None, None
+    if fe_kw is not None:
+        import dataclasses
+        extractor = WhisperFeatureExtractor(**fe_kw)
+        fe_config = extractor.frontend_config
+        config = dataclasses.replace(config, max_source_positions=context)
     encoder = WhisperEncoder(config, precision=args.precision)
     if args.encoder_weights:
         if args.encoder_weights.endswith(".safetensors"):
@@ -197,9 +227,9 @@ def main(args):
 
     def features(idx):
         if args.detectors == 1:    # one_channel_LigoBinaryData: the L1 strain alone
-            return (ops.logmel(torch.from_numpy(l1[idx]).to(device), n_mels=n_mels),)
+            return (ops.logmel(torch.from_numpy(l1[idx]).to(device), n_mels=n_mels, config=fe_config),)
         w = torch.from_numpy(np.concatenate((h1[idx], l1[idx]))).to(device)
-        mel = ops.logmel(w, n_mels=n_mels)
+        mel = ops.logmel(w, n_mels=n_mels, config=fe_config)
         return mel[: len(idx)], mel[len(idx):]
 
     def evaluate_hip():
@@ -241,7 +271,13 @@ def main(args):
     def save(prefix):
         if rank != 0:
             return
-        model.encoder.save_pretrained(os.path.join(args.models_path, f"{prefix}lora_weights_{tag}"))
+        out_dir = os.path.join(args.models_path, f"{prefix}lora_weights_{tag}")
+        model.encoder.save_pretrained(out_dir)
+        if extractor is not None:
+            # a non-default front end travels with the model: run_evaluation.py reads both files
+            extractor.save_pretrained(out_dir)
+            with open(os.path.join(out_dir, "config.json"), "w") as f:
+                json.dump(encoder.config_dict(), f, indent=2, sort_keys=True)
         torch.save(model.classifier.state_dict(), os.path.join(args.models_path, f"{prefix}dense_layers_{tag}.pth"))
 
     stopper, best = EarlyStopper(patience=15), float("inf")
@@ -329,6 +365,14 @@ def build_parser():
                              "keeps the targets it was saved with")
     parser.add_argument("--synthetic", type=int, default=0, help="use N seeded synthetic segments instead of --data-path")
     parser.add_argument("--encoder-weights", type=str, default=None, help="HF WhisperEncoder state_dict (.pth / .safetensors)")
+    # the front end (defaults: Whisper's); any other value builds a WhisperFeatureExtractor of that configuration and an
+    # encoder of max_source_positions = chunk_length * sampling_rate // hop_length // 2
+    parser.add_argument("--sampling-rate", type=int, default=FRONTEND_DEFAULTS["sampling_rate"], help="Hz of the strain segments")
+    parser.add_argument("--n-fft", type=int, default=FRONTEND_DEFAULTS["n_fft"])
+    parser.add_argument("--hop-length", type=int, default=FRONTEND_DEFAULTS["hop_length"])
+    parser.add_argument("--chunk-length", type=int, default=FRONTEND_DEFAULTS["chunk_length"], help="seconds a segment is padded to")
+    parser.add_argument("--mel-fmax", type=float, default=FRONTEND_DEFAULTS["mel_fmax"],
+                        help="upper edge of the mel filterbank in Hz (HF fixes 8000; pass sampling_rate / 2 for strain)")
     parser.add_argument("--precision", choices=("bf16", "fp32"), default="bf16",
                         help="encoder arithmetic: bf16 (default) or exact fp32, the reference's own training arithmetic "
                              "(DoRA / LoRA only: full fine-tuning is bf16)")

@@ -54,6 +54,8 @@ const char* gww_last_error(void);
  * seg_max[n_seg] fp32 scratch (per-segment max of the raw log10 mel)
  * Exact shortcut: frames that only see zero padding are filled with the one
  * constant HF would produce; only ceil((n_samples+200)/160) frames run a DFT.
+ * (The sizes above are those of Whisper's published configuration; a handle from
+ * gww_frontend_create_cfg, below, brings its own: out is [n_seg, n_mels, n_frames].)
  * -------------------------------------------------------------------------- */
 typedef struct gww_frontend gww_frontend;
 int gww_frontend_create(gww_frontend** out);          /* uploads window / twiddle / filterbank tables; 80 mels */
@@ -69,6 +71,34 @@ int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, int n_samples
 int gww_logmel_host_f32(const float* wave, int n_seg, int n_samples, long wave_stride, float* out);   /* 80 mels */
 /* the same with n_mels 80 or 128; out [n_seg, n_mels, 3000] */
 int gww_logmel_host_nmel_f32(const float* wave, int n_seg, int n_samples, long wave_stride, int n_mels, float* out);
+
+/* Any configuration of HF's WhisperFeatureExtractor(feature_size, sampling_rate, hop_length, chunk_length, n_fft):
+ * zero-pad / truncate to n_samples = chunk_length * sampling_rate -> reflect-pad n_fft / 2 -> periodic-Hann n_fft-point
+ * DFT every hop_length -> |X|^2 of frames 0 .. n_samples / hop_length - 1 -> slaney mel [n_mels, n_fft / 2 + 1] ->
+ * log10(max(., 1e-10)) -> per-segment max -> max(x, max - 8) -> (x + 4) / 4.
+ * Supported (anything else: GWW_ERR_ARG, the message names the field): n_fft even in [16, 1024]; 1 <= hop_length <= n_fft;
+ * n_mels 80 or 128; n_samples > n_fft / 2; 1 <= n_frames = n_samples / hop_length <= 3000; 0 <= min_frequency <
+ * max_frequency.  max_frequency is the one extension over HF, which fixes 8000 Hz.
+ * A handle of Whisper's published configuration (16 kHz, 400, 160, 480000, 0 .. 8000 Hz) runs the same kernels as one
+ * from gww_frontend_create_nmel; every other one runs the general kernels (csrc/logmel_any.hip).  gww_logmel_f32 then
+ * writes out [n_seg, n_mels, n_frames]. */
+typedef struct {
+    int   n_mels, sampling_rate, n_fft, hop_length, n_samples;
+    float min_frequency, max_frequency;
+} gww_frontend_cfg;
+/* GWW_OK if cfg is in the supported set, else GWW_ERR_ARG and a message naming the field; plain C++, no GPU, no data */
+int gww_frontend_validate_cfg(const gww_frontend_cfg* cfg);
+int gww_frontend_create_cfg(const gww_frontend_cfg* cfg, gww_frontend** out);
+int gww_frontend_frames(const gww_frontend* fe);                       /* n_frames of the handle */
+int gww_frontend_mel_filters_f32(const gww_frontend* fe, float* out);  /* HOST out [n_mels, n_fft / 2 + 1]; for tests */
+/* the same filterbank without a handle or a GPU (plain C++, as the host twin below) */
+int gww_frontend_mel_filters_host_f32(const gww_frontend_cfg* cfg, float* out);
+/* for tests: on != 0 sends a handle of the published configuration through the general kernels too */
+int gww_frontend_set_general(gww_frontend* fe, int on);
+/* the host twin (see gww_logmel_host_f32: no HIP call, fork-safe); wave [n_seg] rows of n_samples_in samples, wave_stride
+ * apart; out [n_seg, n_mels, n_frames].  The published configuration gives gww_logmel_host_nmel_f32's result bit for bit. */
+int gww_logmel_host_cfg_f32(const gww_frontend_cfg* cfg, const float* wave, int n_seg, int n_samples_in, long wave_stride,
+                            float* out);
 
 /* --------------------------------------------------------------------------
  * Encoder.  Replaces WhisperEncoder.forward as built at
