@@ -62,6 +62,14 @@ class FrontendCfg(C.Structure):
                 ("n_samples", C.c_int), ("min_frequency", C.c_float), ("max_frequency", C.c_float)]
 
 
+class WindowsPlan(C.Structure):
+    _fields_ = [("route", C.c_int), ("edge_lo", C.c_int), ("edge_hi", C.c_int), ("interior", C.c_int),
+                ("stream_frames", C.c_long), ("dft_frames_shared", C.c_long), ("dft_frames_per_window", C.c_long),
+                ("workspace_bytes", C.c_long)]
+
+
+WINDOWS_PER_WINDOW, WINDOWS_SHARED = 0, 1
+
 # name -> (restype, argtypes); every symbol include/gww.h declares
 SIGNATURES = {
     "gww_version": (C.c_int, []),
@@ -80,6 +88,9 @@ SIGNATURES = {
     "gww_frontend_mel_filters_host_f32": (C.c_int, [C.POINTER(FrontendCfg), C.c_void_p]),
     "gww_frontend_set_general": (C.c_int, [C.c_void_p, C.c_int]),
     "gww_logmel_host_cfg_f32": (C.c_int, [C.POINTER(FrontendCfg), C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_void_p]),
+    "gww_logmel_windows_plan": (C.c_int, [C.POINTER(FrontendCfg), C.c_int, C.c_int, C.POINTER(WindowsPlan)]),
+    "gww_logmel_windows_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_long, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_int, C.c_void_p, C.c_long, C.c_int, C.c_void_p]),
     "gww_encoder_create": (C.c_int, [C.POINTER(EncCfg), C.POINTER(C.c_void_p)]),
     "gww_encoder_destroy": (None, [C.c_void_p]),
     "gww_encoder_set_weights": (C.c_int, [C.c_void_p, C.POINTER(EncGlobals), C.POINTER(EncLayer),

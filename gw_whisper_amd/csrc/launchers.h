@@ -27,8 +27,15 @@ struct LogmelAnyPlan {
 };
 int logmel_any_plan(const gww_frontend_cfg* c, LogmelAnyPlan* p);
 // tables: win | cost | sint [n_fft] each, then fbT [n_fft / 2 + 1][n_mels] (device)
+// n_outer x n_seg segments: segment o n_seg + i starts at wave + o outer_stride + i wave_stride
 int launch_logmel_any(const LogmelAnyPlan& p, const float* tables, const float* wave, int n_seg, int n_eff, int live,
-                      long wave_stride, float* out, float* seg_max, hipStream_t s);
+                      long wave_stride, float* out, float* seg_max, hipStream_t s, int n_outer = 1, long outer_stride = 0);
+// ---- the windows of a series: logmel_host.cpp (the route and the frame counts: plain C++), logmel_windows.hip
+int logmel_windows_plan(const gww_frontend_cfg* c, int step, int n_windows, gww_windows_plan* out, const char* who);
+// wp: the plan of (cfg, step, n_windows); workspace: n_rows * wp.workspace_bytes bytes, 16-byte aligned
+int launch_logmel_windows(const LogmelAnyPlan& p, const gww_windows_plan& wp, const float* tables, const float* series,
+                          int n_rows, int n_series, long row_stride, int step, int w0, int n_windows, float* out,
+                          int out_rows_major, void* workspace, hipStream_t s);
 
 // ---- the conv stem: conv1_mel.hip, stem_tail.hip, gemm_bf16.hip
 bool conv1_mel_supported(int n_mels, int d, int kpad);

@@ -538,3 +538,32 @@ extern "C" int gww_logmel_f32(gww_frontend* fe, const float* wave, int n_seg, in
   return fe->n_mels == 128 ? launch_logmel<128>(fe, wave, n_seg, n_eff, live, wave_stride, out, seg_max, s)
                            : launch_logmel<80>(fe, wave, n_seg, n_eff, live, wave_stride, out, seg_max, s);
 }
+
+// The windows of a series (logmel_windows.hip).  Every check that needs no device runs before the first HIP call.
+extern "C" int gww_logmel_windows_f32(gww_frontend* fe, const float* series, int n_rows, int n_series, long row_stride,
+                                      int step, int w0, int n_windows, float* out, int out_rows_major, void* workspace,
+                                      long workspace_bytes, int force_route, void* stream) {
+  const char* who = "gww_logmel_windows_f32";
+  GWW_REQUIRE(fe && series && out && workspace, "%s: NULL argument", who);
+  GWW_REQUIRE(n_rows >= 1, "%s: n_rows=%d must be at least 1", who, n_rows);
+  GWW_REQUIRE(w0 >= 0, "%s: w0=%d must not be negative", who, w0);
+  gww_windows_plan wp;
+  GWW_TRY(logmel_windows_plan(&fe->cfg, step, n_windows, &wp, who));
+  const long last = ((long)w0 + n_windows - 1) * step + fe->cfg.n_samples;
+  GWW_REQUIRE(last <= (long)n_series, "%s: n_series=%d is too short for window w0 + n_windows - 1 = %ld (step %d, window %d: %ld samples)",
+              who, n_series, (long)w0 + n_windows - 1, step, fe->cfg.n_samples, last);
+  GWW_REQUIRE(row_stride >= 0 && (n_rows == 1 || row_stride > 0), "%s: row_stride=%ld", who, row_stride);
+  GWW_REQUIRE(force_route >= -1 && force_route <= GWW_WINDOWS_SHARED, "%s: force_route=%d (-1, 0 or 1)", who, force_route);
+  GWW_REQUIRE(force_route != GWW_WINDOWS_SHARED || wp.route == GWW_WINDOWS_SHARED,
+              "%s: force_route: the plan refuses the shared route for step=%d, n_windows=%d (hop_length %d, %ld shared against %ld "
+              "per-window frames)", who, step, n_windows, fe->cfg.hop_length, wp.dft_frames_shared, wp.dft_frames_per_window);
+  if (force_route == GWW_WINDOWS_PER_WINDOW && wp.route != GWW_WINDOWS_PER_WINDOW) {
+    wp.route = GWW_WINDOWS_PER_WINDOW;
+    wp.workspace_bytes = ((long)n_windows * 4 + 15) / 16 * 16;
+  }
+  if (workspace_bytes < (long)n_rows * wp.workspace_bytes)
+    return fail(GWW_ERR_WORKSPACE, "%s: workspace_bytes=%ld, need %ld", who, workspace_bytes, (long)n_rows * wp.workspace_bytes);
+  GWW_REQUIRE(aligned(workspace, 16), "%s: workspace must be 16-byte aligned", who);
+  return launch_logmel_windows(fe->plan, wp, fe->blob, series, n_rows, n_series, row_stride, step, w0, n_windows, out,
+                               out_rows_major, workspace, (hipStream_t)stream);
+}

@@ -21,6 +21,8 @@
 //                          by atomicMax on the ordered key
 //   k_logmel_any_finalize  one [n_frames] row per workgroup: clamp to max - 8, affine, the constant of the dead frames
 //                          (bitwise the same in every dead frame of a row: what k_stem_detect looks for)
+// The per-frame arithmetic -- fold, DFT, power, mel, log10 -- lives in logmel_tile.h, which logmel_windows.hip (the windows of
+// a series, each frame once) includes too: one body, so a frame's value does not depend on the kernel that computes it.
 // The DFT folds the real input, x[n] +- x[n_fft - n] (half the multiply-adds), against the n_fft-entry twiddle table; the
 // windowed even / odd frames and the twiddles sit in LDS; fp32 throughout.  A workgroup of 256 threads owns FT x G frames:
 // G = 1, 2 or 4 thread groups (as many as 256 threads hold copies of the n_fft / 2 + 1 bins, in whole waves), each thread
@@ -34,17 +36,12 @@
 // holds), where the ev / od reads are wave-uniform broadcasts.  Taking bin n_fft / 2 out of the loop (its "twiddles" are
 // +-1: an alternating sum) and walking each lane's twiddle in registers by a rotation recurrence would remove both; the
 // step after that is the one DESIGN.md names, the two contractions on the fp32 matrix cores.
-#include "common.h"
+#include "logmel_tile.h"
 #include "device_sort.h"
-
-#include <math.h>
 
 namespace gww {
 
-constexpr int kAnyThreads = 256;
-constexpr size_t kAnyLdsMax = 64 * 1024;
-
-// The LDS tile in floats: xs [span4] | ev [ftw][S] | od [ftw][S] | ct [n_fft] | st [n_fft] | pw [ftw][S + 1] | red [4]
+// The LDS tile (logmel_tile.h: AnyTile) in floats
 static size_t any_lds_floats(int n_fft, int hop, int S, int ftw) {
   const size_t span4 = ((size_t)hop * (ftw - 1) + n_fft + 3) / 4 * 4;
   return span4 + 2 * (size_t)ftw * S + 2 * (size_t)n_fft + (size_t)ftw * (S + 1) + 4;
@@ -72,102 +69,39 @@ int logmel_any_plan(const gww_frontend_cfg* c, LogmelAnyPlan* p) {
   return fail(GWW_ERR_ARG, "logmel_any_plan: n_fft=%d hop_length=%d: no tile fits the LDS", c->n_fft, c->hop_length);
 }
 
-struct AnyTables {
-  const float *win, *cost, *sint, *fbT;   // [n_fft] x 3, [n_fft / 2 + 1][n_mels]
-};
-
-// grid (cdiv(live, FT G), n_seg), 256 threads, p.lds_bytes of dynamic LDS
+// grid (cdiv(live, FT G), n_seg, n_outer), 256 threads, p.lds_bytes of dynamic LDS.  Segment blockIdx.z * n_seg + blockIdx.y
+// starts at wave + blockIdx.z * outer_stride + blockIdx.y * stride: one stride for a batch of segments, two for the
+// windows of a multi-row series read in place (logmel_windows.hip)
 template <int FT>
-__global__ __launch_bounds__(kAnyThreads) void k_logmel_any_frames(const float* __restrict__ wave, long stride, int n_eff,
+__global__ __launch_bounds__(kAnyThreads, kAnyWaves) void k_logmel_any_frames(const float* __restrict__ wave, long stride, int n_eff,
                                                                    int live, LogmelAnyPlan p, AnyTables tb,
                                                                    float* __restrict__ out,
-                                                                   unsigned int* __restrict__ seg_max) {
+                                                                   unsigned int* __restrict__ seg_max,
+                                                                   long outer_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int N = p.n_fft, H = N / 2, nfreq = H + 1, S = p.S, hop = p.hop, nm = p.n_mels;
-  const int ftw = FT * p.groups, PS = S + 1;
-  const int span = hop * (ftw - 1) + N, span4 = (span + 3) / 4 * 4;
-  float* xs = lds;
-  float* ev = xs + span4;
-  float* od = ev + ftw * S;
-  float* ct = od + ftw * S;
-  float* st = ct + N;
-  float* pw = st + N;
-  float* red = pw + ftw * PS;
+  const int H = p.n_fft / 2, hop = p.hop, nm = p.n_mels;
+  const AnyTile T = any_tile(lds, p, FT);
+  const int ftw = T.ftw;
 
   const int tid = threadIdx.x;
-  const int seg = blockIdx.y;
+  const int seg = blockIdx.z * gridDim.y + blockIdx.y;
   const int t0 = blockIdx.x * ftw;
-  const float* x = wave + (long)seg * stride;
+  const float* x = wave + (long)blockIdx.z * outer_stride + (long)blockIdx.y * stride;
 
   // the samples of this tile: reflected once at either end of the n_samples buffer, zero from n_eff on (and wherever a
   // frame past the last one would reach: those frames are never stored)
-  for (int i = tid; i < span; i += kAnyThreads) {
+  for (int i = tid; i < T.span; i += kAnyThreads) {
     long q = (long)t0 * hop - H + i;
     if (q < 0) q = -q;
     if (q >= p.chunk) q = 2L * (p.chunk - 1) - q;
-    xs[i] = (q >= 0 && q < n_eff) ? x[q] : 0.0f;
+    T.xs[i] = (q >= 0 && q < n_eff) ? x[q] : 0.0f;
   }
-  for (int i = tid; i < N; i += kAnyThreads) {
-    ct[i] = tb.cost[i];
-    st[i] = tb.sint[i];
-  }
+  any_load_twiddles(T, p, tb);
   __syncthreads();
-  // windowed even / odd parts; columns H + 1 .. S - 1 are zero
-  for (int i = tid; i < ftw * S; i += kAnyThreads) {
-    const int f = i / S, n = i - f * S;
-    float e = 0.f, o = 0.f;
-    if (n <= H) {
-      const float a = xs[f * hop + n] * tb.win[n];
-      if (n == 0 || n == H) {
-        e = a;
-      } else {
-        const float b = xs[f * hop + N - n] * tb.win[N - n];
-        e = a + b;
-        o = a - b;
-      }
-    }
-    ev[i] = e;
-    od[i] = o;
-  }
+  const float* xs = T.xs;
+  any_fold(T, p, tb, [xs, hop](int f, int n) { return xs[f * hop + n]; });
   __syncthreads();
-
-  {
-    const int gsz = kAnyThreads / p.groups;          // a multiple of 64: a wave serves one group
-    const int g = tid / gsz, b = tid - g * gsz;
-    const float* evg = ev + g * FT * S;
-    const float* odg = od + g * FT * S;
-    for (int k = b; k < nfreq; k += gsz) {
-      float re[FT], im[FT];
-#pragma unroll
-      for (int f = 0; f < FT; ++f) re[f] = im[f] = 0.f;
-      int idx = 0;   // (k n) mod n_fft
-      for (int n = 0; n < S; n += 4) {
-        float c[4], s[4];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          c[j] = ct[idx];
-          s[j] = st[idx];
-          idx += k;
-          if (idx >= N) idx -= N;
-        }
-#pragma unroll
-        for (int f = 0; f < FT; ++f) {
-          const float4 e4 = *reinterpret_cast<const float4*>(&evg[f * S + n]);
-          const float4 o4 = *reinterpret_cast<const float4*>(&odg[f * S + n]);
-          re[f] = fmaf(e4.x, c[0], re[f]);
-          re[f] = fmaf(e4.y, c[1], re[f]);
-          re[f] = fmaf(e4.z, c[2], re[f]);
-          re[f] = fmaf(e4.w, c[3], re[f]);
-          im[f] = fmaf(o4.x, s[0], im[f]);
-          im[f] = fmaf(o4.y, s[1], im[f]);
-          im[f] = fmaf(o4.z, s[2], im[f]);
-          im[f] = fmaf(o4.w, s[3], im[f]);
-        }
-      }
-#pragma unroll
-      for (int f = 0; f < FT; ++f) pw[(g * FT + f) * PS + k] = re[f] * re[f] + im[f] * im[f];
-    }
-  }
+  any_dft_power<FT>(T, p);
   __syncthreads();
 
   // mel projection + log10; thread -> (mel, frame), frame fastest: a store instruction writes runs of one mel row
@@ -176,30 +110,24 @@ __global__ __launch_bounds__(kAnyThreads) void k_logmel_any_frames(const float* 
     const int m = i / ftw, f = i - m * ftw;
     const int t = t0 + f;
     if (t >= live) continue;
-    const float* pf = pw + f * PS;
-    float acc = 0.f;
-    for (int k = 0; k < nfreq; ++k) acc = fmaf(tb.fbT[k * nm + m], pf[k], acc);
-    // log10 in fp64, rounded once (see logmel.hip: the dead frames' -10.0 must be what a live 1e-10 gives)
-    const float lg = (float)log10((double)fmaxf(acc, 1e-10f));
+    const float lg = any_mel_log10(T, p, tb, f, m);
     out[((long)seg * nm + m) * p.n_frames + t] = lg;
     lmax = fmaxf(lmax, lg);
   }
   lmax = wave_max(lmax);
-  if ((tid & 63) == 0) red[tid >> 6] = lmax;
+  if ((tid & 63) == 0) T.red[tid >> 6] = lmax;
   __syncthreads();
   if (tid == 0) {
-    const float m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    const float m = fmaxf(fmaxf(T.red[0], T.red[1]), fmaxf(T.red[2], T.red[3]));
     if (m > -INFINITY) atomicMax(&seg_max[seg], ordered_u32(m));
   }
 }
-
-__device__ __forceinline__ float any_affine(float v, float floor_v) { return (fmaxf(v, floor_v) + 4.0f) * 0.25f; }
 
 // grid (n_mels, n_seg), 256 threads: one [n_frames] row per workgroup.  VEC: n_frames % 4 == 0 and out 16-byte aligned
 template <bool VEC>
 __global__ __launch_bounds__(kAnyThreads) void k_logmel_any_finalize(float* __restrict__ out, int live, int n_frames,
                                                                      const unsigned int* __restrict__ seg_max) {
-  const int seg = blockIdx.y, m = blockIdx.x;
+  const int seg = blockIdx.z * gridDim.y + blockIdx.y, m = blockIdx.x;
   float mx = from_ordered_u32(seg_max[seg]);
   mx = fmaxf(mx, live < n_frames ? -10.0f : mx);     // dead frames contribute log10(1e-10) = -10
   const float floor_v = mx - 8.0f;
@@ -227,26 +155,23 @@ __global__ __launch_bounds__(kAnyThreads) void k_logmel_any_finalize(float* __re
 }
 
 int launch_logmel_any(const LogmelAnyPlan& p, const float* tables, const float* wave, int n_seg, int n_eff, int live,
-                      long wave_stride, float* out, float* seg_max, hipStream_t s) {
+                      long wave_stride, float* out, float* seg_max, hipStream_t s, int n_outer, long outer_stride) {
   GWW_REQUIRE(live >= 1 && live <= p.n_frames && n_eff >= 0 && n_eff <= p.chunk, "logmel_any: live=%d n_eff=%d out of range",
               live, n_eff);
   GWW_REQUIRE(n_seg >= 1 && n_seg <= 65535, "logmel_any: n_seg=%d (1 .. 65535 per call)", n_seg);
+  GWW_REQUIRE(n_outer >= 1 && n_outer <= 65535, "logmel_any: n_outer=%d (1 .. 65535 per call)", n_outer);
   GWW_REQUIRE((p.ft == 8 || p.ft == 4) && p.lds_bytes <= kAnyLdsMax, "logmel_any: bad plan");
-  AnyTables tb;
-  tb.win = tables;
-  tb.cost = tables + p.n_fft;
-  tb.sint = tables + 2 * p.n_fft;
-  tb.fbT = tables + 3 * p.n_fft;
+  const AnyTables tb = any_tables(tables, p.n_fft);
   unsigned int* mx = reinterpret_cast<unsigned int*>(seg_max);
-  const dim3 g1((unsigned)cdiv(live, p.ft * p.groups), (unsigned)n_seg);
+  const dim3 g1((unsigned)cdiv(live, p.ft * p.groups), (unsigned)n_seg, (unsigned)n_outer);
   if (p.ft == 8)
     hipLaunchKernelGGL(k_logmel_any_frames<8>, g1, dim3(kAnyThreads), p.lds_bytes, s, wave, wave_stride, n_eff, live, p, tb,
-                       out, mx);
+                       out, mx, outer_stride);
   else
     hipLaunchKernelGGL(k_logmel_any_frames<4>, g1, dim3(kAnyThreads), p.lds_bytes, s, wave, wave_stride, n_eff, live, p, tb,
-                       out, mx);
+                       out, mx, outer_stride);
   GWW_LAUNCH_CHECK();
-  const dim3 g2((unsigned)p.n_mels, (unsigned)n_seg);
+  const dim3 g2((unsigned)p.n_mels, (unsigned)n_seg, (unsigned)n_outer);
   if (p.n_frames % 4 == 0 && aligned(out, 16))
     hipLaunchKernelGGL(k_logmel_any_finalize<true>, g2, dim3(kAnyThreads), 0, s, out, live, p.n_frames, mx);
   else

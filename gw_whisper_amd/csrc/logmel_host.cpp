@@ -262,7 +262,46 @@ void frontend_tables(const gww_frontend_cfg* c, float* win, float* cost, float* 
   }
 }
 
+// The windows of a series (include/gww.h: gww_windows_plan): which frames of a window see its reflect padding, how many
+// distinct interior frames n windows hold, and the route that follows.  No GPU call.
+//   edge at the start:  t hop < n_fft / 2            <=>  t < ceil((n_fft / 2) / hop)
+//   edge at the end:    t hop + n_fft / 2 > L        <=>  t > (L - n_fft / 2) / hop
+// With step = s hop, interior frame t of window w is frame w s + t of one hop-spaced stream: n windows hold
+// (n - 1) min(s, interior) + interior distinct ones.
+int logmel_windows_plan(const gww_frontend_cfg* c, int step, int n_windows, gww_windows_plan* out, const char* who) {
+  if (int rc = frontend_validate(c, who)) return rc;
+  if (!out) return fail(GWW_ERR_ARG, "%s: out is NULL", who);
+  if (step < 1) return fail(GWW_ERR_ARG, "%s: step=%d must be at least 1", who, step);
+  if (n_windows < 1) return fail(GWW_ERR_ARG, "%s: n_windows=%d must be at least 1", who, n_windows);
+  const int H = c->n_fft / 2, hop = c->hop_length, L = c->n_samples, F = L / hop;
+  const long n = n_windows;
+  int lo = (H + hop - 1) / hop;
+  if (lo > F) lo = F;
+  int hi0 = (L - H) / hop + 1;            // the first frame that reaches past the window's last sample
+  if (hi0 > F) hi0 = F;
+  if (hi0 < lo) hi0 = lo;                 // (a frame that is an edge at both ends counts once)
+  out->edge_lo = lo;
+  out->edge_hi = F - hi0;
+  out->interior = hi0 - lo;
+  const bool aligned_step = step % hop == 0;
+  const long s = step / hop;
+  out->stream_frames = aligned_step && out->interior > 0 ? (n - 1) * (s < out->interior ? s : out->interior) + out->interior
+                                                         : n * out->interior;
+  out->dft_frames_shared = out->stream_frames + n * (out->edge_lo + out->edge_hi);
+  out->dft_frames_per_window = n * F;
+  const bool shared = aligned_step && out->dft_frames_shared < out->dft_frames_per_window;
+  out->route = shared ? GWW_WINDOWS_SHARED : GWW_WINDOWS_PER_WINDOW;
+  // shared: raw stream [n_mels, stream_frames] + raw edges [n_windows, n_mels, edges]; per window: one maximum each
+  const long floats = shared ? (long)c->n_mels * (out->stream_frames + n * (out->edge_lo + out->edge_hi)) : n;
+  out->workspace_bytes = (floats * 4 + 15) / 16 * 16;
+  return GWW_OK;
+}
+
 }  // namespace gww
+
+extern "C" int gww_logmel_windows_plan(const gww_frontend_cfg* cfg, int step, int n_windows, gww_windows_plan* out) {
+  return gww::logmel_windows_plan(cfg, step, n_windows, out, "gww_logmel_windows_plan");
+}
 
 namespace {
 

@@ -2,12 +2,14 @@
 // -fsanitize=address,undefined and run on the CPU, outside pytest.  It runs the configurations of
 // tests/test_frontend_config_host.py -- ragged and over-long inputs included -- and every refusal, and checks what needs
 // no reference: finite values, the constant of the dead frames, and the published configuration bit for bit against
-// gww_logmel_host_nmel_f32.  Exit status 0 when all of it holds.
+// gww_logmel_host_nmel_f32; and gww_logmel_windows_plan over the configurations and refusals of
+// tests/test_logmel_windows_host.py against a brute-force count.  Exit status 0 when all of it holds.
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "../../include/gww.h"
@@ -76,7 +78,74 @@ static void refuse(gww_frontend_cfg c, const char* field) {
         gww::g_msg);
 }
 
+// gww_logmel_windows_plan against a brute-force count: loop over windows and frames, classify each by the two
+// inequalities of include/gww.h, put the centres of the interior ones into a set (a sorted vector here)
+static void plan_case(int n_fft, int hop, int L, int step, int n) {
+  const gww_frontend_cfg c = {80, 2048, n_fft, hop, L, 0.f, 1024.f};
+  gww_windows_plan p;
+  memset(&p, 0xEE, sizeof p);
+  const int rc = gww_logmel_windows_plan(&c, step, n, &p);
+  CHECK(rc == GWW_OK, "windows plan n_fft %d hop %d L %d step %d n %d: rc %d (%s)", n_fft, hop, L, step, n, rc, gww::g_msg);
+  if (rc != GWW_OK) return;
+  const int H = n_fft / 2, F = L / hop;
+  long lo = 0, hi = 0;
+  std::vector<long> centres;
+  for (int w = 0; w < n; ++w)
+    for (int t = 0; t < F; ++t) {
+      if (t * hop < H) ++lo;
+      else if (t * hop + H > L) ++hi;
+      else centres.push_back((long)w * step + (long)t * hop);
+    }
+  std::sort(centres.begin(), centres.end());
+  // (a step that is no multiple of the hop: the plan models no sharing at all -- the kernels share none -- although every
+  // few windows line up again)
+  const long distinct = step % hop ? (long)centres.size() : (long)(std::unique(centres.begin(), centres.end()) - centres.begin());
+  const long shared_frames = distinct + lo + hi, per_window = (long)n * F;
+  const bool shared = step % hop == 0 && shared_frames < per_window;
+  CHECK(p.edge_lo == lo / n && p.edge_hi == hi / n && p.interior == F - lo / n - hi / n, "windows plan: edges %d + %d + %d, want "
+        "%ld + %ld", p.edge_lo, p.interior, p.edge_hi, lo / n, hi / n);
+  CHECK(p.stream_frames == distinct && p.dft_frames_shared == shared_frames && p.dft_frames_per_window == per_window,
+        "windows plan n_fft %d hop %d L %d step %d n %d: %ld stream / %ld shared / %ld per window, want %ld / %ld / %ld", n_fft,
+        hop, L, step, n, p.stream_frames, p.dft_frames_shared, p.dft_frames_per_window, distinct, shared_frames, per_window);
+  CHECK(p.route == (shared ? GWW_WINDOWS_SHARED : GWW_WINDOWS_PER_WINDOW), "windows plan: route %d", p.route);
+  const long floats = shared ? 80 * (distinct + lo + hi) : n;
+  CHECK(p.workspace_bytes == (floats * 4 + 15) / 16 * 16, "windows plan: workspace %ld", p.workspace_bytes);
+  printf("ok  windows n_fft %4d hop %3d L %5d step %4d n %4d: %d + %d + %d frames, %ld shared / %ld per window -> %s\n", n_fft,
+         hop, L, step, n, p.edge_lo, p.interior, p.edge_hi, p.dft_frames_shared, p.dft_frames_per_window,
+         p.route == GWW_WINDOWS_SHARED ? "shared" : "per window");
+}
+
+static void plan_refuse(gww_frontend_cfg c, int step, int n, const char* name) {
+  gww_windows_plan p;
+  const int rc = gww_logmel_windows_plan(&c, step, n, &p);
+  CHECK(rc == GWW_ERR_ARG && strstr(gww::g_msg, name), "windows plan: expected a refusal naming %s, got rc %d (%s)", name, rc,
+        gww::g_msg);
+  if (rc == GWW_ERR_ARG) printf("ok  refused: %s\n", gww::g_msg);
+}
+
 int main() {
+  // the windows of a series: tests/test_logmel_windows_host.py
+  const int plans[][4] = {{16, 4, 128, 8},  {18, 6, 132, 12}, {16, 16, 256, 32}, {128, 12, 2048, 204}, {16, 4, 128, 4},
+                          {16, 4, 128, 128}, {16, 4, 128, 10}, {16, 4, 128, 512}, {64, 8, 40, 8},       {64, 8, 2048, 200}};
+  for (const auto& q : plans)
+    for (int n : {1, 2, 7, 256}) plan_case(q[0], q[1], q[2], q[3], n);
+  {
+    const gww_frontend_cfg w = {80, 2048, 128, 12, 2048, 0.f, 1024.f};
+    gww_windows_plan p;
+    CHECK(gww_logmel_windows_plan(&w, 204, 256, &p) == GWW_OK && p.edge_lo == 6 && p.edge_hi == 4 && p.interior == 160 &&
+              p.stream_frames == 17 * 255 + 160 && p.route == GWW_WINDOWS_SHARED,
+          "windows plan: the workload's counts");
+    plan_refuse(w, 0, 4, "step");
+    plan_refuse(w, -204, 4, "step");
+    plan_refuse(w, 204, 0, "n_windows");
+    plan_refuse(w, 204, -3, "n_windows");
+    gww_frontend_cfg b = w;
+    b.n_fft = 127;
+    plan_refuse(b, 204, 4, "n_fft");
+    CHECK(gww_logmel_windows_plan(&w, 204, 4, nullptr) == GWW_ERR_ARG && strstr(gww::g_msg, "out"), "NULL plan accepted");
+    CHECK(gww_logmel_windows_plan(nullptr, 204, 4, &p) == GWW_ERR_ARG, "NULL cfg accepted by the windows plan");
+  }
+
   // (mels, rate, n_fft, hop, chunk samples, fmin, fmax) and the input length: tests/test_frontend_config_host.py
   const struct { gww_frontend_cfg c; int n_in; } cases[] = {
       {{80, 2048, 128, 16, 4096, 0.f, 8000.f}, 2048},

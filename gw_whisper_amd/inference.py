@@ -16,6 +16,9 @@ step), the threshold is applied on the device and triggers leave the GPU in one 
     RegBCELoss               <->  train.py:358-370
     ResampleMelAdapter            the reference's OTHER front end (Signal_vs_Noise/utils/preprocess.py:44-51 +
                                   WhisperFeatureExtractor): FFT resampling 2048 -> 16000 Hz and log-mel, on device
+    NativeMelAdapter              a front end at the strain's own rate (``ops.FrontendConfig``): no resampling, no 30 s pad;
+                                  under ``evaluate_slices`` the features come straight from the series, every STFT frame of
+                                  a batch computed once (``ops.logmel_windows``)
 
 Whitening (PyCBC, :56-137): ``whiten.py``.  The HDF5 reader stays host-side reference code.
 The Q-transform adapter of the reference (``QTransformAdapter``, both the train.py and the inference.py variant) is
@@ -87,6 +90,37 @@ class ResampleMelAdapter(nn.Module):
         return ops.logmel(wave).reshape(B, D, 80, 3000)
 
 
+class NativeMelAdapter(nn.Module):
+    """``[B, D, L]`` strain at the model's own rate -> ``[B, D, n_mels, n_frames]`` features of ``config`` (``ops.logmel`` with
+    ``config``: no resampling, no padding to 30 s; ``L`` must be ``config.n_samples``).  ``from_series`` computes the same
+    features for the windows of a series without cutting them (``ops.logmel_windows``): ``evaluate_slices`` takes that path
+    for a network whose adapter has it.  ``route``: passed on to ``ops.logmel_windows`` (tests, timing)."""
+
+    def __init__(self, config, n_detectors: int = 2, route: Optional[str] = None):
+        super().__init__()
+        self.config = config
+        self.n_detectors = n_detectors
+        self.route = route
+
+    def _check(self, length: int) -> None:
+        if length != self.config.n_samples:
+            raise _lib.GwwError(f"NativeMelAdapter: windows of {length} samples but config.n_samples is "
+                                f"{self.config.n_samples}: the front end's chunk must be the window")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        from . import ops
+        B, D, n = x.shape
+        self._check(n)
+        return ops.logmel(x.reshape(B * D, n), config=self.config).reshape(B, D, self.config.n_mels, self.config.n_frames)
+
+    def from_series(self, dss: torch.Tensor, step: int, w0: int, n: int, window: Optional[int] = None) -> torch.Tensor:
+        """Windows ``w0 .. w0 + n - 1`` (``config.n_samples`` samples every ``step``) of ``dss [D, N]`` -> ``[n, D, n_mels,
+        n_frames]``, bit for bit what ``forward`` gives for the cut windows."""
+        from . import ops
+        self._check(self.config.n_samples if window is None else window)
+        return ops.logmel_windows(dss, self.config, step, w0=w0, n_windows=n, route=self.route)
+
+
 # --------------------------------------------------------------------------------------- model shell
 class GWWhisperClassifier(nn.Module):
     """Reference ``MLGWSC-1/inference.py:353-392``: adapter -> encoder per detector -> token -> MLP (+ Softmax).
@@ -107,7 +141,10 @@ class GWWhisperClassifier(nn.Module):
     def embed(self, x: torch.Tensor) -> torch.Tensor:
         """The pooled token of every detector, ``[B, D, d]``: everything in front of the head.  Adapter and encoder run
         per detector, so these tokens are also what a time slide pairs up (``time_slides.py``)."""
-        feats = self.adapter(x)                                   # [B, D, 80, 3000]
+        return self.embed_features(self.adapter(x))               # [B, D, 80, 3000]
+
+    def embed_features(self, feats: torch.Tensor) -> torch.Tensor:
+        """``embed`` behind the adapter: features ``[B, D, n_mels, n_frames]`` -> pooled tokens ``[B, D, d]``."""
         B, D = feats.shape[:2]
         flat = feats.reshape(B * D, *feats.shape[2:])
         if self.use_last_token and not torch.is_grad_enabled():
@@ -203,22 +240,34 @@ def evaluate_slices(slicer: DeviceSegmentSlicer, network: nn.Module, device: str
     device (``cluster_triggers_device``) and return ``(triggers, scores per batch, (times, values, variances))``.
     ``return_tokens``: the network is a ``GWWhisperClassifier``; also return, as the last element, the pooled tokens of
     these windows ``[n, D, d]`` fp32 on the device (what ``time_slides`` pairs up) -- the network runs as the same two
-    steps ``classifier(embed(x))`` its ``forward`` is, so every other result is what it is without the flag."""
+    steps ``classifier(embed(x))`` its ``forward`` is, so every other result is what it is without the flag.
+    A network whose adapter has ``from_series`` (``NativeMelAdapter``) gets its features straight from the series,
+    ``classifier(embed_features(adapter.from_series(...)))``, without materialising the windows; STFT frames are shared
+    within a batch, not across batches.  Every other network takes the materialising path."""
     w0, w1 = (0, len(slicer)) if window_range is None else window_range      # one rank's shard (shard_windows)
     n = w1 - w0
     scores = torch.empty((n,), dtype=torch.float32, device=slicer.dss.device)
     if return_tokens and not (hasattr(network, "embed") and hasattr(network, "classifier")):
         raise _lib.GwwError("evaluate_slices: return_tokens needs a network with embed() and classifier (GWWhisperClassifier)")
     tokens = None
+    from_series = getattr(getattr(network, "adapter", None), "from_series", None)
+    if from_series is not None and not (hasattr(network, "embed_features") and hasattr(network, "classifier")):
+        from_series = None
     with torch.no_grad():
         for i0 in range(0, n, batch_size):
             i1 = min(n, i0 + batch_size)
-            x = slicer.windows(w0 + i0, w0 + i1).contiguous()
-            if return_tokens:
-                tok = network.embed(x)
-                if tokens is None:
-                    tokens = torch.empty((n, *tok.shape[1:]), dtype=torch.float32, device=slicer.dss.device)
-                tokens[i0:i1] = tok
+            if from_series is not None:
+                # a native-rate front end: the features of the windows straight from the series, each STFT frame once
+                tok = network.embed_features(from_series(slicer.dss, slicer.index_step_size, w0 + i0, i1 - i0,
+                                                         window=slicer.slice_length))
+            else:
+                x = slicer.windows(w0 + i0, w0 + i1).contiguous()
+                tok = network.embed(x) if return_tokens else None
+            if tok is not None:
+                if return_tokens:
+                    if tokens is None:
+                        tokens = torch.empty((n, *tok.shape[1:]), dtype=torch.float32, device=slicer.dss.device)
+                    tokens[i0:i1] = tok
                 out = network.classifier(tok.reshape(tok.shape[0], -1))
             else:
                 out = network(x)

@@ -120,6 +120,83 @@ def logmel(wave: torch.Tensor, n_samples: int | None = None, n_mels: int = 80, c
     return out
 
 
+_WINDOW_ROUTES = {_lib.WINDOWS_PER_WINDOW: "per_window", _lib.WINDOWS_SHARED: "shared"}
+_last_windows_route = None
+
+
+def logmel_windows_plan(config: FrontendConfig, step: int, n_windows: int) -> dict:
+    """What ``logmel_windows`` does for ``n_windows`` windows of ``config.n_samples`` samples every ``step`` (include/gww.h:
+    ``gww_windows_plan``): ``route`` ("shared" or "per_window"), ``edge_lo`` / ``edge_hi`` / ``interior`` frames per window,
+    ``stream_frames``, ``dft_frames_shared`` / ``dft_frames_per_window`` and ``workspace_bytes``, the last four per row.
+    Plain C++, needs no GPU; ``step < 1`` and ``n_windows < 1`` raise ``GwwError`` naming the argument."""
+    import ctypes as C
+    cfg, plan = config.c_struct(), _lib.WindowsPlan()
+    check(lib().gww_logmel_windows_plan(C.byref(cfg), int(step), int(n_windows), C.byref(plan)), "gww_logmel_windows_plan")
+    out = {name: int(getattr(plan, name)) for name, _ in _lib.WindowsPlan._fields_}
+    out["route"] = _WINDOW_ROUTES[plan.route]
+    return out
+
+
+def last_logmel_windows_route():
+    """"shared" or "per_window": the route the last ``logmel_windows`` call ran (None before the first)."""
+    return _last_windows_route
+
+
+def logmel_windows(series: torch.Tensor, config: FrontendConfig, step: int, w0: int = 0, n_windows: int | None = None,
+                   rows_major: bool = False, route: str | None = None) -> torch.Tensor:
+    """[R, N] fp32 GPU series (any row stride) -> [n, R, n_mels, n_frames] (``rows_major``: [R, n, ...]) fp32: the
+    features of windows ``w0 .. w0 + n - 1``, window ``w`` being samples ``[w step, w step + config.n_samples)`` of every
+    row -- bit for bit ``logmel(window, config=config)`` of the materialised window (for Whisper's published configuration:
+    ``general=True``, the general kernels), without materialising it.
+    ``n_windows=None``: every window from ``w0`` on that fits.  Where ``step`` is a multiple of the hop and windows overlap,
+    an STFT frame several windows hold is computed once per call (csrc/logmel_windows.hip, ``logmel_windows_plan``);
+    ``route="per_window"`` forces the general kernels on every window, ``route="shared"`` raises where the plan refuses."""
+    global _last_windows_route
+    if route not in (None, "shared", "per_window"):
+        raise _lib.GwwError(f"logmel_windows: route={route!r} (None, 'shared' or 'per_window')")
+    if series.dim() == 1:
+        series = series[None]
+    if series.dim() != 2:
+        raise _lib.GwwError(f"logmel_windows: series {tuple(series.shape)} is not [rows, samples]")
+    R, N = series.shape
+    step, w0, L = int(step), int(w0), int(config.n_samples)
+    if step < 1:
+        raise _lib.GwwError(f"logmel_windows: step={step} must be at least 1")
+    if w0 < 0:
+        raise _lib.GwwError(f"logmel_windows: w0={w0} must not be negative")
+    fit = 0 if N < w0 * step + L else (N - L - w0 * step) // step + 1
+    n = fit if n_windows is None else int(n_windows)
+    if n < 1 or n > fit:
+        raise _lib.GwwError(f"logmel_windows: n_windows={n}: a series of {N} samples holds {fit} window(s) of {L} every {step} "
+                            f"from w0={w0} on")
+    if R < 1:
+        raise _lib.GwwError("logmel_windows: series has no rows")
+    plan = logmel_windows_plan(config, step, n)
+    if route == "shared" and plan["route"] != "shared":
+        raise _lib.GwwError(f"logmel_windows: route='shared' is refused for step={step}, n_windows={n} (hop_length "
+                            f"{config.hop_length}: {plan['dft_frames_shared']} shared against {plan['dft_frames_per_window']} "
+                            f"per-window frames)")
+    if not series.is_cuda:
+        raise _lib.GwwError(f"series must live on the GPU (got {series.device}); gw_whisper_amd has no CPU path")
+    if series.dtype != torch.float32:
+        raise _lib.GwwError(f"series must be torch.float32, got {series.dtype}")
+    if series.stride(1) != 1 or (R > 1 and series.stride(0) < 1):
+        series = series.contiguous()
+    per_window = route == "per_window" or plan["route"] == "per_window"
+    ws_bytes = R * ((4 * n + 15) // 16 * 16 if per_window else plan["workspace_bytes"])
+    shape = (R, n) if rows_major else (n, R)
+    out = torch.empty((*shape, config.n_mels, config.n_frames), dtype=torch.float32, device=series.device)
+    ws = torch.empty((ws_bytes // 4,), dtype=torch.float32, device=series.device)
+    fe = _fe(series.device, config.n_mels, config, general=config.is_published)
+    with torch.cuda.device(series.device):
+        check(lib().gww_logmel_windows_f32(fe, series.data_ptr(), R, N, series.stride(0) if R > 1 else N, step, w0, n,
+                                           out.data_ptr(), int(rows_major), ws.data_ptr(), ws_bytes,
+                                           _lib.WINDOWS_PER_WINDOW if route == "per_window" else -1, _stream()),
+              "gww_logmel_windows_f32")
+    _last_windows_route = "per_window" if per_window else "shared"
+    return out
+
+
 def logmel_host(wave, n_samples: int | None = None, n_mels: int = 80, config: FrontendConfig | None = None) -> torch.Tensor:
     """CPU twin of :func:`logmel`: [n, L] fp32 host waveform -> [n, n_mels, n_frames] fp32 CPU tensor.
 

@@ -108,10 +108,14 @@ def stack_events(keys, rows) -> np.ndarray:
 
 
 def scan_events(model, strain, batch_size: int = 256, window_size: int = WINDOW_SIZE, step_size: int = STEP_SIZE,
-                n_mels: int = 80, device="cuda") -> np.ndarray:
+                n_mels: int = 80, device="cuda", frontend=None) -> np.ndarray:
     """``sigmoid(model(mel_h1, mel_l1))`` of every window of every event: strain [E, 2, N] at 2048 Hz (H1 = detector 0,
     L1 = detector 1), one upload; result [E, n_windows] float32, one copy back.  ``model``: a two-detector model on the
-    device (``two_channel_ligo_binary_classifier`` or ``TwoChannelLIGOBinaryClassifierCNN``, num_classes = 1)."""
+    device (``two_channel_ligo_binary_classifier`` or ``TwoChannelLIGOBinaryClassifierCNN``, num_classes = 1).
+    ``frontend``: an ``ops.FrontendConfig`` whose ``n_samples`` is ``window_size`` -- the features of a model trained at the
+    strain's own rate, through ``ops.logmel_windows`` on the [E * 2, N] rows (no resampling, no window is cut, an STFT
+    frame shared by several windows of a batch is computed once); ``None``: resample to 16 kHz + Whisper's published
+    log-mel, as the reference does."""
     from . import ops
     from .inference import resample
     if isinstance(strain, (list, tuple)):
@@ -127,6 +131,8 @@ def scan_events(model, strain, batch_size: int = 256, window_size: int = WINDOW_
     if W == 0:
         raise GwwError(f"scan_events: {N} samples hold no window of {window_size}")
     dss = t.to(device=device, dtype=torch.float32).contiguous()      # the one host-to-device copy
+    if frontend is not None:
+        return _scan_native(model, dss, W, batch_size, window_size, step_size, frontend)
     # window (e, j), detector k as a view: no bytes move
     win = dss.as_strided((E, W, 2, window_size), (dss.stride(0), step_size, dss.stride(1), 1))
     out = torch.empty((E * W,), dtype=torch.float32, device=dss.device)
@@ -141,3 +147,31 @@ def scan_events(model, strain, batch_size: int = 256, window_size: int = WINDOW_
             logits = model(mel[:b], mel[b:])
             out[i0:i0 + b] = torch.sigmoid(logits.float().reshape(b))
     return out.reshape(E, W).cpu().numpy()
+
+
+def _scan_native(model, dss, W: int, batch_size: int, window_size: int, step_size: int, frontend) -> np.ndarray:
+    """``scan_events`` on a native-rate front end: batches of ``batch_size`` windows as before, now window-major -- windows
+    j0 .. j1 - 1 of as many events as fill the batch -- so that one ``ops.logmel_windows`` call serves a batch; rows-major
+    output [E' * 2, n, ...] viewed as [E', 2, n, ...] gives ``mel_h1`` and ``mel_l1`` as slices (views, where a batch holds the
+    windows of one event -- the catalogue's case of long events)."""
+    from . import ops
+    if frontend.n_samples != window_size:
+        raise GwwError(f"scan_events: frontend.n_samples is {frontend.n_samples} but window_size is {window_size}: the front "
+                       f"end's chunk must be the window")
+    E, _, N = dss.shape
+    rows = dss.reshape(E * 2, N)
+    out = torch.empty((E, W), dtype=torch.float32, device=dss.device)
+    nm, F = frontend.n_mels, frontend.n_frames
+    with torch.no_grad():
+        if W >= batch_size:                                           # one event at a time, its windows in batches
+            groups = [(e, e + 1, j0, min(j0 + batch_size, W)) for e in range(E) for j0 in range(0, W, batch_size)]
+        else:                                                         # whole events, as many as fit a batch
+            per = max(1, batch_size // W)
+            groups = [(e0, min(e0 + per, E), 0, W) for e0 in range(0, E, per)]
+        for e0, e1, j0, j1 in groups:
+            b, n = e1 - e0, j1 - j0
+            mel = ops.logmel_windows(rows[2 * e0:2 * e1], frontend, step_size, w0=j0, n_windows=n, rows_major=True)
+            mel = mel.reshape(b, 2, n, nm, F)
+            logits = model(mel[:, 0].reshape(b * n, nm, F), mel[:, 1].reshape(b * n, nm, F))
+            out[e0:e1, j0:j1] = torch.sigmoid(logits.float().reshape(b, n))
+    return out.cpu().numpy()

@@ -100,6 +100,37 @@ int gww_frontend_set_general(gww_frontend* fe, int on);
 int gww_logmel_host_cfg_f32(const gww_frontend_cfg* cfg, const float* wave, int n_seg, int n_samples_in, long wave_stride,
                             float* out);
 
+/* The windows of a series: window w covers samples [w * step, w * step + cfg.n_samples) of every row of series
+ * [n_rows, n_series] (rows row_stride apart); out [n_windows, n_rows, n_mels, n_frames], or [n_rows, n_windows, ...] with
+ * out_rows_major, holds for windows w0 .. w0 + n_windows - 1 what gww_logmel_f32 gives for the materialised window, bit
+ * for bit (csrc/logmel_windows.hip).  Frame t of a window is an EDGE frame when t * hop_length < n_fft / 2 or
+ * t * hop_length + n_fft / 2 > n_samples (it sees the reflect padding), else INTERIOR.  On the shared route
+ * (step % hop_length == 0 and dft_frames_shared < dft_frames_per_window) an interior frame that several windows hold is
+ * computed once per call; the per-window route runs the general kernels on the windows in place.
+ * gww_logmel_windows_plan: plain C++, no GPU; step < 1 and n_windows < 1 are GWW_ERR_ARG naming the argument. */
+#define GWW_WINDOWS_PER_WINDOW 0
+#define GWW_WINDOWS_SHARED 1
+typedef struct {
+    int  route;                  /* GWW_WINDOWS_SHARED / GWW_WINDOWS_PER_WINDOW: what gww_logmel_windows_f32 runs */
+    int  edge_lo, edge_hi;       /* edge frames per window at its start and at its end */
+    int  interior;               /* n_frames - edge_lo - edge_hi */
+    long stream_frames;          /* distinct interior frames of the n_windows windows (per-window count when step is no
+                                    multiple of hop_length: nothing is shared then) */
+    long dft_frames_shared;      /* stream_frames + n_windows * (edge_lo + edge_hi), per row */
+    long dft_frames_per_window;  /* n_windows * n_frames, per row */
+    long workspace_bytes;        /* of the chosen route, PER ROW (a multiple of 16): the call needs n_rows times this */
+} gww_windows_plan;
+int gww_logmel_windows_plan(const gww_frontend_cfg* cfg, int step, int n_windows, gww_windows_plan* out);
+/* fe: a handle whose n_samples is the window length; series, out, workspace: device pointers, workspace 16-byte aligned
+ * and at least n_rows * plan.workspace_bytes long (its contents before the call do not matter; nothing is allocated per
+ * call).  A series too short for window w0 + n_windows - 1 is GWW_ERR_ARG.  n_windows * n_rows up to 2^31 - 1: the launcher
+ * loops over the output's outer index where a grid dimension is 16 bits; more than 65535 rows (per-window route, rows
+ * major: windows) per call are refused with a message, never truncated.  force_route: -1 the plan's route,
+ * GWW_WINDOWS_PER_WINDOW to force the fallback, GWW_WINDOWS_SHARED is refused where the plan does not choose it. */
+int gww_logmel_windows_f32(gww_frontend* fe, const float* series, int n_rows, int n_series, long row_stride, int step,
+                           int w0, int n_windows, float* out, int out_rows_major, void* workspace, long workspace_bytes,
+                           int force_route, void* stream);
+
 /* --------------------------------------------------------------------------
  * Encoder.  Replaces WhisperEncoder.forward as built at
  *   Signal_vs_Noise/src/train.py:227-228,240 ; Glitch_classification/src/train.py:159 ;
