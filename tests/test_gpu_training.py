@@ -9,6 +9,7 @@ from gw_whisper_amd import synth
 from oracle import dora as odora
 from oracle import encoder as oenc
 from oracle import logmel as olm
+from tests.stem_like import c_step as _c_step
 
 pytestmark = pytest.mark.gpu
 
@@ -574,33 +575,6 @@ def test_input_gradient_through_the_conv_stem(T, gww):
         an = float((g * v).sum())
         print(f"d loss / d mel, direction {trial}: analytic(HIP, bf16) {an:.5f}  finite-difference(fp64 oracle) {fd:.5f}")
         assert abs(an - fd) < 0.06 * abs(fd) + 2e-3, (an, fd)
-
-
-def _c_step(T, enc, mel, pooled, d_hidden, want_x0, want_mel):
-    """gww_encoder_train_forward + _backward (their _f32 twins for an fp32 encoder) straight through ctypes, no targets:
-    (d_x0 | None, d_mel | None).  The outputs start as NaN, so an element the backward leaves unwritten shows."""
-    from gw_whisper_amd import _lib
-    lib = _lib.lib()
-    sfx = "_f32" if enc.precision == "fp32" else ""
-    B, d, Tn = mel.shape[0], enc.config.d_model, enc.config.max_source_positions
-    with T.cuda.device(mel.device):
-        enc._sync_weights()
-        h = enc._ensure_handle()
-        ws = T.empty((getattr(lib, "gww_train_workspace_bytes" + sfx)(h, B),), dtype=T.uint8, device=mel.device)
-        saved = T.empty((getattr(lib, "gww_train_saved_bytes" + sfx)(h, B),), dtype=T.uint8, device=mel.device)
-        hidden = T.empty((B, d) if pooled else (B, Tn, d), dtype=T.float32, device=mel.device)
-        stream = T.cuda.current_stream().cuda_stream
-        _lib.check(getattr(lib, "gww_encoder_train_forward" + sfx)(
-            h, mel.data_ptr(), B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), hidden.data_ptr(), int(pooled),
-            stream), "train_forward" + sfx)
-        d_x0 = T.full((B, Tn, d), float("nan"), dtype=T.float32, device=mel.device) if want_x0 else None
-        d_mel = T.full(mel.shape, float("nan"), dtype=T.float32, device=mel.device) if want_mel else None
-        _lib.check(getattr(lib, "gww_encoder_train_backward" + sfx)(
-            h, B, ws.data_ptr(), ws.numel(), saved.data_ptr(), saved.numel(), d_hidden.data_ptr(), None, 0,
-            d_x0.data_ptr() if want_x0 else None, d_mel.data_ptr() if want_mel else None, int(pooled), stream),
-            "train_backward" + sfx)
-        T.cuda.synchronize()
-    return d_x0, d_mel
 
 
 @pytest.mark.parametrize("pooled", [False, True], ids=["dense", "pooled"])
