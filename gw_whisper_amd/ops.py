@@ -919,7 +919,9 @@ def adapter_grads_f32(x, dy, y, bias_st, yscale, scaling, A, B, mag, nrm):
 
 def info_nce_forward(z1, z2, temperature: float):
     """InfoNCE of the reference's ContrastivePretrainer (``gww_info_nce_forward_f32``): z1, z2 fp32 [B, P] (P <= 1024) ->
-    (loss [1] device scalar, saved = (n [2B, P], nrm [2B], lse [2B], term [2B]) for ``info_nce_backward``)."""
+    (loss [1] device scalar, saved = (n [2B, P], nrm [2B], lse [2B], term [2B]) for ``info_nce_backward``).
+    A row's norm is the square root of an fp32 sum of squares, as in the fp32 reference: rows with |z| above about
+    1.8e19 overflow that sum (inf norm, zero direction) and are outside what this computes."""
     z1 = _dev(z1, torch.float32, "z1")
     z2 = _dev(z2, torch.float32, "z2")
     if z1.dim() != 2 or z1.shape != z2.shape:
