@@ -70,6 +70,23 @@ class WindowsPlan(C.Structure):
 
 WINDOWS_PER_WINDOW, WINDOWS_SHARED = 0, 1
 
+MLP_MAX_LAYERS = 5      # include/gww.h GWW_MLP_MAX_LAYERS
+
+
+class MlpParams(C.Structure):
+    _fields_ = [("n_layers", C.c_int), ("w", C.c_void_p * MLP_MAX_LAYERS), ("b", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+class MlpActs(C.Structure):
+    _fields_ = [("h", C.c_void_p * (MLP_MAX_LAYERS - 1)), ("logits", C.c_void_p)]
+
+
+class MlpGrads(C.Structure):
+    _fields_ = [("dw", C.c_void_p * MLP_MAX_LAYERS), ("db", C.c_void_p * MLP_MAX_LAYERS)]
+
+
+_MLP_P, _MLP_A, _MLP_G = C.POINTER(MlpParams), C.POINTER(MlpActs), C.POINTER(MlpGrads)
+
 # name -> (restype, argtypes); every symbol include/gww.h declares
 SIGNATURES = {
     "gww_version": (C.c_int, []),
@@ -238,11 +255,11 @@ SIGNATURES = {
                                                 + [C.c_void_p] * 5),
     "gww_assemble_batch_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_long, C.c_long, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
-    "gww_head_forward_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_ulonglong,
-                                       C.c_ulonglong] + [C.c_void_p] * 9),
+    "gww_head_forward_f32": (C.c_int, [C.c_void_p, _MLP_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                       C.c_ulonglong, C.c_ulonglong, _MLP_A] + [C.c_void_p] * 5),
     "gww_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "gww_head_backward_f32": (C.c_int, [C.c_void_p] * 10 + [C.c_int, C.c_int, C.c_int, C.c_float, C.c_int]
-                              + [C.c_void_p] * 11),
+    "gww_head_backward_f32": (C.c_int, [C.c_void_p, _MLP_P, _MLP_A, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float,
+                                        C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, _MLP_G, C.c_void_p]),
     "gww_head_dropout_mask_f32": (C.c_int, [C.c_ulonglong, C.c_ulonglong, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                             C.c_void_p]),
     "gww_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
@@ -252,12 +269,12 @@ SIGNATURES = {
     "gww_cnn_head_forward_f32": (C.c_int, [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 3),
     "gww_cnn_head_backward_f32": (C.c_int, [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10
                                   + [C.c_size_t, C.c_void_p]),
-    "gww_det_head_forward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_void_p] * 10),
+    "gww_det_head_forward_f32": (C.c_int, [C.c_void_p, _MLP_P, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, _MLP_A]
+                                 + [C.c_void_p] * 5),
     "gww_det_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int]),
-    "gww_det_head_backward_f32": (C.c_int, [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-                                  + [C.c_void_p] * 12),
-    "gww_det_head_scores_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
-                                          C.c_void_p]),
+    "gww_det_head_backward_f32": (C.c_int, [C.c_void_p, _MLP_P, _MLP_A, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, _MLP_G, C.c_void_p]),
+    "gww_det_head_scores_f32": (C.c_int, [C.c_void_p, _MLP_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]),
     "gww_det_eval_accumulate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5),
     "gww_score_thresholds_workspace_bytes": (C.c_size_t, []),
     "gww_score_thresholds_f32": (C.c_int, [C.c_void_p, C.c_long, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
@@ -296,16 +313,16 @@ SIGNATURES = {
     "gww_trig_steps_workspace_bytes": (C.c_size_t, [C.c_long]),
     "gww_trig_steps_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_long, C.c_double, C.c_double,
                                      C.c_double] + [C.c_void_p] * 7 + [C.c_size_t, C.c_void_p]),
-    "gww_det_head_scores2_f32": (C.c_int, [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long,
-                                           C.c_void_p]),
-    "gww_bin_head_forward_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 10),
+    "gww_det_head_scores2_f32": (C.c_int, [C.c_void_p, _MLP_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_long, C.c_void_p]),
+    "gww_bin_head_forward_f32": (C.c_int, [C.c_int, C.c_void_p, _MLP_P, C.c_void_p, C.c_int, C.c_int, C.c_int, _MLP_A]
+                                 + [C.c_void_p] * 5),
     "gww_bin_head_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
-    "gww_bin_head_backward_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 12 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t]
-                                  + [C.c_void_p] * 12),
-    "gww_bin_head_scores_f32": (C.c_int, [C.c_int] + [C.c_void_p] * 11 + [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gww_bin_head_backward_f32": (C.c_int, [C.c_int, C.c_void_p, _MLP_P, _MLP_A, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_size_t, C.c_void_p, _MLP_G, C.c_void_p]),
+    "gww_bin_head_scores_f32": (C.c_int, [C.c_int, C.c_void_p, _MLP_P, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
 }
 
-ABI_VERSION = 107   # include/gww.h GWW_VERSION this binding was written against
+ABI_VERSION = 108   # include/gww.h GWW_VERSION this binding was written against
 
 _lib = None
 

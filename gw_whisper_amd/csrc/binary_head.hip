@@ -5,13 +5,11 @@
 // identical bits), plain launches, nothing here synchronises.
 //   k_bh_fwd         one workgroup per 16 rows walks the layers through LDS; tail (fp64 on the fp32 logits, rounded once):
 //                    sigmoid, the row's BCE-with-logits sum, dz = d loss / d logits.  TRAIN false: the logits only
-//   k_bh_mean        one workgroup: loss = sum(row_loss) / (B C), fp64 partial sums in a fixed tree
-//   k_bh_bwd_in      the same row blocks backwards, every layer's dz left in a workspace, the pooled-token gradient out
-//   k_bh_bwd_w       ONE launch for all the layers' dW = dz^T h and db
-// Layout 1 is the detection head's chain, walked by the same chain_fwd / chain_bwd: at equal weights its logits are the
-// bits of k_det_fwd's.  Layout 2 keeps a 1024-wide row in LDS, next to which x fits only up to d_in = 1280: its first
-// layer walks x in 512-column chunks (chain_fwd_chunked, the k order of chain_fwd) at every d_in, and its backward takes its
-// 98 816 bytes of LDS from the launch (chain_bwd_at).
+//   k_chain_mean, k_chain_bwd_in<BinTwo, false, true>, k_chain_bwd_w<4>: head_chain.h
+// Layout 1 is the detection head's chain, walked by the same chain_fwd: at equal weights its logits are the bits of
+// k_det_fwd's, and its backward IS the detection head's (det_chain_backward, detect.hip).  Layout 2 keeps a 1024-wide row in
+// LDS, next to which x fits only up to d_in = 1280: its first layer walks x in 512-column chunks (chain_fwd_chunked, the k
+// order of chain_fwd) at every d_in, and its backward takes its 98 816 bytes of LDS from the launch.
 #include "head_chain.h"
 
 namespace gww {
@@ -20,7 +18,7 @@ template <int LAYOUT>
 struct BinHead;
 template <>
 struct BinHead<GWW_BIN_HEAD_ONE> {
-  using CH = Chain<512, 256, 128, 64>;
+  using CH = DetChain;
 };
 template <>
 struct BinHead<GWW_BIN_HEAD_TWO> {
@@ -31,7 +29,6 @@ using BinTwo = BinHead<GWW_BIN_HEAD_TWO>::CH;
 static_assert(BinOne::L == 5 && BinOne::bwd_lds_bytes() == 49664, "layout 1 is the detection head's chain");
 static_assert(BinTwo::L == 4 && BinTwo::fwd_w(0) == 512 && BinTwo::fwd_w(1) == 1024 && BinTwo::bwd_lds_bytes() == 98816,
               "LDS layout of the two-detector head");
-constexpr int BH_LMAX = 5;
 
 struct BinTail {
   const float* targets;
@@ -77,29 +74,6 @@ __global__ __launch_bounds__(CH_THREADS) void k_bh_fwd(const float* __restrict__
   }
 }
 
-__global__ __launch_bounds__(256) void k_bh_mean(const float* __restrict__ row_loss, int B, int C, float* __restrict__ loss) {
-  const double s = block_sum_f64(row_loss, B);
-  if (threadIdx.x == 0) loss[0] = (float)(s / ((double)B * (double)C));
-}
-
-// ---- backward ----------------------------------------------------------------------------------------------------------
-template <int LAYOUT>
-__global__ __launch_bounds__(CH_THREADS) void k_bh_bwd_in(const float* __restrict__ dz_in, const float* __restrict__ gscale,
-                                                          ChainBwdArgs<BinHead<LAYOUT>::CH::L> A, int B, int d_in, int C) {
-  using CH = typename BinHead<LAYOUT>::CH;
-  if constexpr (LAYOUT == GWW_BIN_HEAD_ONE) {
-    chain_bwd<CH, false>(dz_in, gscale, A, B, d_in, C, 1.f);
-  } else {
-    extern __shared__ __attribute__((aligned(16))) float sm_bh[];
-    chain_bwd_at<CH>(sm_bh, dz_in, gscale, A, B, d_in, C);
-  }
-}
-
-template <int L>
-__global__ __launch_bounds__(256) void k_bh_bwd_w(ChainWgradArgs<L> A, int B) {
-  chain_bwd_w(A, B);
-}
-
 // ---- host side -------------------------------------------------------------------------------------------------------
 static int bh_check_shape(const char* who, int layout, int B, int d_in, int C) {
   GWW_REQUIRE(layout == GWW_BIN_HEAD_ONE || layout == GWW_BIN_HEAD_TWO, "%s: layout=%d must be %d (d_in -> 512 -> 256 -> 128 "
@@ -111,89 +85,30 @@ static int bh_check_shape(const char* who, int layout, int B, int d_in, int C) {
   return GWW_OK;
 }
 
-// the pointers of the layers a layout has (w, b, h of the others are ignored): non-NULL and 16-byte aligned; the last
-// layer's bias is read by elements and needs no alignment
-static bool bh_layers_ok(int L, const float* const* w, const float* const* b, const float* const* h) {
-  for (int i = 0; i < L; ++i) {
-    if (!w[i] || (((uintptr_t)w[i]) & 15)) return false;
-    if (b && (!b[i] || (i < L - 1 && (((uintptr_t)b[i]) & 15)))) return false;
-    if (h && i < L - 1 && (!h[i] || (((uintptr_t)h[i]) & 15))) return false;
-  }
-  return true;
-}
-
+// forward (TRAIN: H and the loss) or scores (H == NULL, loss == NULL, S empty) of one layout
 template <int LAYOUT, bool TRAIN>
-static int bh_launch_fwd(const float* x, const float* const* w, const float* const* b, float* const* h, float* logits, int B,
-                         int d_in, int C, const BinTail& S, hipStream_t s) {
+static int bh_forward(const char* who, const float* x, const gww_mlp_params* P, const gww_mlp_acts* H, float* logits, int B,
+                      int d_in, int C, const BinTail& S, float* loss, void* stream) {
   using CH = typename BinHead<LAYOUT>::CH;
+  GWW_TRY(chain_check_operands(who, CH::L, x, P, H, nullptr));
   const size_t lds = LAYOUT == GWW_BIN_HEAD_ONE ? chain_lds_bytes<CH>(d_in) : chain_chunked_lds_bytes<CH>();
-  ChainFwdArgs<CH::L> P;
-  for (int i = 0; i < CH::L; ++i) {
-    P.W[i] = w[i];
-    P.b[i] = b[i];
-    P.save[i] = i < CH::L - 1 ? (TRAIN ? h[i] : nullptr) : logits;
-  }
-  GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bh_fwd<LAYOUT, TRAIN>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                              (int)lds));
-  hipLaunchKernelGGL((k_bh_fwd<LAYOUT, TRAIN>), dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, x, P, B, d_in, C, S);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
-}
-
-template <int LAYOUT>
-static int bh_launch_bwd(const float* x, const float* const* w, const float* const* h, const float* dz, const float* dloss, int B,
-                         int d_in, int C, float* ws, float* dx, float* const* dw, float* const* db, hipStream_t s) {
-  using CH = typename BinHead<LAYOUT>::CH;
-  ChainBwdArgs<CH::L> A;
-  for (int i = 0; i < CH::L; ++i) A.W[i] = w[i];
-  for (int i = 0; i < CH::L - 1; ++i) A.h[i] = h[i];
-  A.dx = dx;
-  chain_carve<CH>(ws, B, A.dz);
-  const size_t lds = LAYOUT == GWW_BIN_HEAD_ONE ? 0 : CH::bwd_lds_bytes();
-  if (lds)
-    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_bh_bwd_in<LAYOUT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds));
-  hipLaunchKernelGGL(k_bh_bwd_in<LAYOUT>, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, dz, dloss, A, B, d_in, C);
-  GWW_LAUNCH_CHECK();
-  ChainWgradArgs<CH::L> T;
-  float* gw[CH::L];
-  float* gb[CH::L];
-  for (int i = 0; i < CH::L; ++i) {
-    gw[i] = dw[i];
-    gb[i] = db[i];
-  }
-  const int grid = chain_wgrad_table<CH>(T, x, A, gw, gb, d_in, C);
-  hipLaunchKernelGGL(k_bh_bwd_w<CH::L>, dim3((unsigned)grid), dim3(256), 0, s, T, B);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return chain_launch_fwd(k_bh_fwd<LAYOUT, TRAIN>, lds, B, S.row_loss, (double)B * (double)C, loss, (hipStream_t)stream, x,
+                          chain_fwd_args<CH::L>(P, H ? H->h : nullptr, logits), B, d_in, C, S);
 }
 
 }  // namespace gww
 
 using namespace gww;
 
-extern "C" int gww_bin_head_forward_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2,
-                                        const float* b2, const float* w3, const float* b3, const float* w4, const float* b4,
-                                        const float* w5, const float* b5, const float* targets, int B, int d_in, int C,
-                                        float* h1, float* h2, float* h3, float* h4, float* logits, float* probs,
-                                        float* row_loss, float* dz, float* loss, void* stream) {
-  GWW_TRY(bh_check_shape("gww_bin_head_forward_f32", layout, B, d_in, C));
-  const int L = layout == GWW_BIN_HEAD_ONE ? BinOne::L : BinTwo::L;
-  const float* const w[BH_LMAX] = {w1, w2, w3, w4, w5};
-  const float* const b[BH_LMAX] = {b1, b2, b3, b4, b5};
-  float* const h[BH_LMAX - 1] = {h1, h2, h3, h4};
-  GWW_REQUIRE(x && targets && logits && probs && row_loss && dz && loss, "gww_bin_head_forward_f32: NULL argument");
-  GWW_REQUIRE(bh_layers_ok(L, w, b, h) && aligned16({x}),
-              "gww_bin_head_forward_f32: x and the %d layers' w, b and h must be non-NULL and 16-byte aligned", L);
-  hipStream_t s = (hipStream_t)stream;
+extern "C" int gww_bin_head_forward_f32(int layout, const float* x, const gww_mlp_params* params, const float* targets, int B,
+                                        int d_in, int C, const gww_mlp_acts* acts, float* probs, float* row_loss, float* dz,
+                                        float* loss, void* stream) {
+  const char* who = "gww_bin_head_forward_f32";
+  GWW_TRY(bh_check_shape(who, layout, B, d_in, C));
+  GWW_REQUIRE(targets && acts && probs && row_loss && dz && loss, "%s: NULL argument", who);
   const BinTail S{targets, probs, row_loss, dz};
-  if (layout == GWW_BIN_HEAD_ONE)
-    GWW_TRY((bh_launch_fwd<GWW_BIN_HEAD_ONE, true>(x, w, b, h, logits, B, d_in, C, S, s)));
-  else
-    GWW_TRY((bh_launch_fwd<GWW_BIN_HEAD_TWO, true>(x, w, b, h, logits, B, d_in, C, S, s)));
-  hipLaunchKernelGGL(k_bh_mean, dim3(1), dim3(256), 0, s, (const float*)row_loss, B, C, loss);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  if (layout == GWW_BIN_HEAD_ONE) return bh_forward<GWW_BIN_HEAD_ONE, true>(who, x, params, acts, acts->logits, B, d_in, C, S, loss, stream);
+  return bh_forward<GWW_BIN_HEAD_TWO, true>(who, x, params, acts, acts->logits, B, d_in, C, S, loss, stream);
 }
 
 extern "C" size_t gww_bin_head_workspace_bytes(int layout, int B, int C) {
@@ -202,40 +117,22 @@ extern "C" size_t gww_bin_head_workspace_bytes(int layout, int B, int C) {
   return 0;
 }
 
-extern "C" int gww_bin_head_backward_f32(int layout, const float* x, const float* w1, const float* w2, const float* w3,
-                                         const float* w4, const float* w5, const float* h1, const float* h2, const float* h3,
-                                         const float* h4, const float* dz, const float* dloss, int B, int d_in, int C, float* ws,
-                                         size_t ws_bytes, float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
-                                         float* db3, float* dw4, float* db4, float* dw5, float* db5, void* stream) {
-  GWW_TRY(bh_check_shape("gww_bin_head_backward_f32", layout, B, d_in, C));
-  const int L = layout == GWW_BIN_HEAD_ONE ? BinOne::L : BinTwo::L;
-  const float* const w[BH_LMAX] = {w1, w2, w3, w4, w5};
-  const float* const h[BH_LMAX - 1] = {h1, h2, h3, h4};
-  float* const dw[BH_LMAX] = {dw1, dw2, dw3, dw4, dw5};
-  float* const db[BH_LMAX] = {db1, db2, db3, db4, db5};
-  GWW_REQUIRE(x && dz && ws && dx, "gww_bin_head_backward_f32: NULL argument");
-  GWW_REQUIRE(bh_layers_ok(L, w, nullptr, h) && bh_layers_ok(L, dw, nullptr, nullptr) && aligned16({x, ws, dx}),
-              "gww_bin_head_backward_f32: x, ws, dx and the %d layers' w, h and dw must be non-NULL and 16-byte aligned", L);
-  for (int i = 0; i < L; ++i) GWW_REQUIRE(db[i], "gww_bin_head_backward_f32: NULL bias gradient of layer %d", i + 1);
-  GWW_REQUIRE(ws_bytes >= gww_bin_head_workspace_bytes(layout, B, C), "gww_bin_head_backward_f32: workspace of %zu bytes, %zu needed",
-              ws_bytes, gww_bin_head_workspace_bytes(layout, B, C));
+extern "C" int gww_bin_head_backward_f32(int layout, const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts,
+                                         const float* dz, const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes,
+                                         float* dx, const gww_mlp_grads* grads, void* stream) {
+  const char* who = "gww_bin_head_backward_f32";
+  GWW_TRY(bh_check_shape(who, layout, B, d_in, C));
   hipStream_t s = (hipStream_t)stream;
-  if (layout == GWW_BIN_HEAD_ONE) return bh_launch_bwd<GWW_BIN_HEAD_ONE>(x, w, h, dz, dloss, B, d_in, C, ws, dx, dw, db, s);
-  return bh_launch_bwd<GWW_BIN_HEAD_TWO>(x, w, h, dz, dloss, B, d_in, C, ws, dx, dw, db, s);
+  if (layout == GWW_BIN_HEAD_ONE) return det_chain_backward(who, x, params, acts, dz, dloss, B, d_in, C, ws, ws_bytes, dx, grads, s);
+  return chain_backward<BinTwo, false, true>(who, x, params, acts, dz, dloss, B, d_in, C, 1.f, ws, ws_bytes, dx, grads, s);
 }
 
-extern "C" int gww_bin_head_scores_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2,
-                                       const float* b2, const float* w3, const float* b3, const float* w4, const float* b4,
-                                       const float* w5, const float* b5, int B, int d_in, int C, float* logits, void* stream) {
-  GWW_TRY(bh_check_shape("gww_bin_head_scores_f32", layout, B, d_in, C));
-  const int L = layout == GWW_BIN_HEAD_ONE ? BinOne::L : BinTwo::L;
-  const float* const w[BH_LMAX] = {w1, w2, w3, w4, w5};
-  const float* const b[BH_LMAX] = {b1, b2, b3, b4, b5};
-  GWW_REQUIRE(x && logits, "gww_bin_head_scores_f32: NULL argument");
-  GWW_REQUIRE(bh_layers_ok(L, w, b, nullptr) && aligned16({x}),
-              "gww_bin_head_scores_f32: x and the %d layers' w and b must be non-NULL and 16-byte aligned", L);
-  hipStream_t s = (hipStream_t)stream;
-  const BinTail S{};
-  if (layout == GWW_BIN_HEAD_ONE) return bh_launch_fwd<GWW_BIN_HEAD_ONE, false>(x, w, b, nullptr, logits, B, d_in, C, S, s);
-  return bh_launch_fwd<GWW_BIN_HEAD_TWO, false>(x, w, b, nullptr, logits, B, d_in, C, S, s);
+extern "C" int gww_bin_head_scores_f32(int layout, const float* x, const gww_mlp_params* params, int B, int d_in, int C,
+                                       float* logits, void* stream) {
+  const char* who = "gww_bin_head_scores_f32";
+  GWW_TRY(bh_check_shape(who, layout, B, d_in, C));
+  GWW_REQUIRE(logits, "%s: NULL argument", who);
+  if (layout == GWW_BIN_HEAD_ONE)
+    return bh_forward<GWW_BIN_HEAD_ONE, false>(who, x, params, nullptr, logits, B, d_in, C, BinTail{}, nullptr, stream);
+  return bh_forward<GWW_BIN_HEAD_TWO, false>(who, x, params, nullptr, logits, B, d_in, C, BinTail{}, nullptr, stream);
 }

@@ -4,11 +4,8 @@
 // so two identical calls give identical bits.  Plain launches only:
 //   k_head_fwd    one workgroup per 16 rows walks the whole chain, activations in LDS, weights streamed from L2;
 //                 tail: lse, row loss, argmax, dz = (softmax - onehot) / B
-//   k_head_mean   one workgroup: the batch mean of the row losses (fixed order, fp64 partial sums)
-//   k_head_bwd_in the same row blocks backwards: dh = dz W masked by the stored post-dropout activation, every layer's dz
-//                 left in a workspace, the pooled-token gradient out
-//   k_head_bwd_w  ONE launch for the four layers: a workgroup owns a 64 x 64 tile of one layer's dW = dz^T h (and the
-//                 bias column sums of the same dz tile), reducing over the B rows inside the workgroup
+//   k_chain_mean, k_chain_bwd_in<HeadChain, true, false>, k_chain_bwd_w<4>: head_chain.h.  The backward masks dh = dz W by
+//                 the stored post-dropout activation
 // Dropout is Philox4x32-10 keyed by (seed, step offset, layer, element index): the mask depends on neither the launch
 // geometry nor the row blocking.  The backward does not need to regenerate it: the saved activation is the POST-dropout
 // one, which is positive exactly where the unit was kept AND the ReLU was open (x > 0 => x / (1 - p) > 0 in fp32).
@@ -94,21 +91,6 @@ __global__ __launch_bounds__(CH_THREADS) void k_head_fwd(const float* __restrict
   }
 }
 
-// mean of the row losses (fp64 partial sums in a fixed order)
-__global__ __launch_bounds__(256) void k_head_mean(const float* __restrict__ row_loss, int B, float* __restrict__ loss) {
-  const double s = block_sum_f64(row_loss, B);
-  if (threadIdx.x == 0) loss[0] = (float)(s / (double)B);
-}
-
-// ---- backward, input side -------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(CH_THREADS) void k_head_bwd_in(const float* __restrict__ dz_in, const float* __restrict__ gscale,
-                                                            ChainBwdArgs<HeadChain::L> A, int B, int d_in, int C, float scale) {
-  chain_bwd<HeadChain, true>(dz_in, gscale, A, B, d_in, C, scale);
-}
-
-// ---- backward, weight side ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_head_bwd_w(ChainWgradArgs<HeadChain::L> A, int B) { chain_bwd_w(A, B); }
-
 // ---- dropout mask (for tests: rebuild the step in fp64) -------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_head_mask(unsigned long long seed, unsigned long long offset, int layer, long n4,
                                                    unsigned thr, float* __restrict__ mask) {
@@ -155,55 +137,34 @@ __global__ __launch_bounds__(256) void k_eval_accumulate(const float* __restrict
 
 using namespace gww;
 
-extern "C" int gww_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                    const float* w3, const float* b3, const float* w4, const float* b4,
-                                    const long long* labels, int B, int d_in, int C, float p, int train,
-                                    unsigned long long seed, unsigned long long offset, float* h1, float* h2, float* h3,
-                                    float* logits, float* row_loss, long long* pred, float* dz, float* loss, void* stream) {
-  GWW_TRY(chain_check_shape("gww_head_forward_f32", B, 1024, d_in, C, 1));
-  GWW_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && labels, "gww_head_forward_f32: NULL input");
-  GWW_REQUIRE(h1 && h2 && h3 && logits && row_loss && pred && dz && loss, "gww_head_forward_f32: NULL output");
-  GWW_REQUIRE(p >= 0.f && p < 1.f, "gww_head_forward_f32: dropout p=%g must be in [0, 1)", (double)p);
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, b1, b2, b3, h1, h2, h3}), "gww_head_forward_f32: operands must be 16-byte aligned");
+extern "C" int gww_head_forward_f32(const float* x, const gww_mlp_params* params, const long long* labels, int B, int d_in,
+                                    int C, float p, int train, unsigned long long seed, unsigned long long offset,
+                                    const gww_mlp_acts* acts, float* row_loss, long long* pred, float* dz, float* loss,
+                                    void* stream) {
+  const char* who = "gww_head_forward_f32";
+  GWW_TRY(chain_check_shape(who, B, 1024, d_in, C, 1));
+  GWW_REQUIRE(labels && acts && row_loss && pred && dz && loss, "%s: NULL argument", who);
+  GWW_TRY(chain_check_operands(who, HeadChain::L, x, params, acts, nullptr));
+  GWW_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout p=%g must be in [0, 1)", who, (double)p);
   HeadDrop dr;
   dr.seed = seed;
   dr.offset = offset;
   dr.on = train && p > 0.f;
   dr.thr = (unsigned)((double)p * 4294967296.0);
   dr.scale = dr.on ? 1.f / (1.f - p) : 1.f;
-  const size_t lds = chain_lds_bytes<HeadChain>(d_in);
-  hipStream_t s = (hipStream_t)stream;
-  GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_head_fwd), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const ChainFwdArgs<HeadChain::L> P{{w1, w2, w3, w4}, {b1, b2, b3, b4}, {h1, h2, h3, logits}};
-  hipLaunchKernelGGL(k_head_fwd, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, x, P, labels, B, d_in, C, dr, row_loss,
-                     pred, dz);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_head_mean, dim3(1), dim3(256), 0, s, (const float*)row_loss, B, loss);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return chain_launch_fwd(k_head_fwd, chain_lds_bytes<HeadChain>(d_in), B, row_loss, (double)B, loss, (hipStream_t)stream, x,
+                          chain_fwd_args<HeadChain::L>(params, acts->h, acts->logits), labels, B, d_in, C, dr, row_loss, pred, dz);
 }
 
-extern "C" int gww_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
-                                     const float* h1, const float* h2, const float* h3, const float* dz, const float* dloss,
-                                     int B, int d_in, int C, float p, int train, float* ws, float* dx, float* dw1, float* db1,
-                                     float* dw2, float* db2, float* dw3, float* db3, float* dw4, float* db4, void* stream) {
-  GWW_TRY(chain_check_shape("gww_head_backward_f32", B, 1024, d_in, C, 1));
-  GWW_REQUIRE(x && w1 && w2 && w3 && w4 && h1 && h2 && h3 && dz, "gww_head_backward_f32: NULL input");
-  GWW_REQUIRE(ws && dx && dw1 && db1 && dw2 && db2 && dw3 && db3 && dw4 && db4, "gww_head_backward_f32: NULL output");
-  GWW_REQUIRE(p >= 0.f && p < 1.f, "gww_head_backward_f32: dropout p=%g must be in [0, 1)", (double)p);
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, h1, h2, h3, ws, dx, dw1, dw2, dw3, dw4}),
-              "gww_head_backward_f32: operands must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  ChainBwdArgs<HeadChain::L> A{{w1, w2, w3, w4}, {h1, h2, h3}, {}, dx};
-  chain_carve<HeadChain>(ws, B, A.dz);       // gww_head_workspace_bytes
+extern "C" int gww_head_backward_f32(const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts, const float* dz,
+                                     const float* dloss, int B, int d_in, int C, float p, int train, float* ws, size_t ws_bytes,
+                                     float* dx, const gww_mlp_grads* grads, void* stream) {
+  const char* who = "gww_head_backward_f32";
+  GWW_TRY(chain_check_shape(who, B, 1024, d_in, C, 1));
+  GWW_REQUIRE(p >= 0.f && p < 1.f, "%s: dropout p=%g must be in [0, 1)", who, (double)p);
   const float scale = (train && p > 0.f) ? 1.f / (1.f - p) : 1.f;
-  hipLaunchKernelGGL(k_head_bwd_in, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, s, dz, dloss, A, B, d_in, C, scale);
-  GWW_LAUNCH_CHECK();
-  ChainWgradArgs<HeadChain::L> T;
-  const int grid = chain_wgrad_table<HeadChain>(T, x, A, {dw1, dw2, dw3, dw4}, {db1, db2, db3, db4}, d_in, C);
-  hipLaunchKernelGGL(k_head_bwd_w, dim3((unsigned)grid), dim3(256), 0, s, T, B);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return chain_backward<HeadChain, true, false>(who, x, params, acts, dz, dloss, B, d_in, C, scale, ws, ws_bytes, dx, grads,
+                                                (hipStream_t)stream);
 }
 
 extern "C" size_t gww_head_workspace_bytes(int B, int C) { return chain_workspace_bytes<HeadChain>(B, C); }

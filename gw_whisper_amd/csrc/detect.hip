@@ -6,9 +6,7 @@
 //   k_det_fwd        one workgroup per 16 rows walks the five layers through LDS; tail (fp64 on the fp32 logits, rounded
 //                    once): softmax, q = eps + (1 - C eps) p, the row's BCE sum, dz = d loss / d logits.  MODE >= 0: no
 //                    saves, one score per row (inference)
-//   k_det_mean       one workgroup: loss = sum(row_loss) / (B C), fp64 partial sums in a fixed tree
-//   k_det_bwd_in     the same row blocks backwards, every layer's dz left in a workspace, the pooled-token gradient out
-//   k_det_bwd_w      ONE launch for the five layers' dW = dz^T h and db
+//   k_chain_mean, k_chain_bwd_in<DetChain, false, false>, k_chain_bwd_w<5>: head_chain.h
 //   k_det_eval       one workgroup: correct += #(argmax targets == argmax probs), loss_sum += the batch's mean loss
 //   k_sel_*          radix select over the order-preserving integer image of fp32: four 8-bit histogram passes for all
 //                    F ranks together (integer atomics only: they commute)
@@ -18,7 +16,6 @@
 
 namespace gww {
 
-using DetChain = Chain<512, 256, 128, 64>;
 static_assert(DetChain::fwd_w(0) == 256 && DetChain::fwd_w(1) == 512 && DetChain::bwd_lds_bytes() == 49664,
               "LDS layout of the detection head (DESIGN.md section 21)");
 constexpr int DT_FMAX = 8;                  // false-alarm ranks of one selection
@@ -102,23 +99,17 @@ __global__ __launch_bounds__(CH_THREADS) void k_det_fwd(const float* __restrict_
   }
 }
 
-__global__ __launch_bounds__(256) void k_det_mean(const float* __restrict__ row_loss, int B, int C, float* __restrict__ loss) {
-  const double s = block_sum_f64(row_loss, B);
-  if (threadIdx.x == 0) loss[0] = (float)(s / ((double)B * (double)C));
-}
-
 // ---- backward ----------------------------------------------------------------------------------------------------------
 // LDS: buffer 0 dz5 [16][C16], then dz3 [16][128], then dz1 [16][512]; buffer 1 dz4 [16][64], then dz2 [16][256]
-__global__ __launch_bounds__(CH_THREADS) void k_det_bwd_in(const float* __restrict__ dz_in, const float* __restrict__ gscale,
-                                                           ChainBwdArgs<DetChain::L> A, int B, int d_in, int C) {
-  chain_bwd<DetChain, false>(dz_in, gscale, A, B, d_in, C, 1.f);
+int det_chain_backward(const char* who, const float* x, const gww_mlp_params* P, const gww_mlp_acts* H, const float* dz,
+                       const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes, float* dx, const gww_mlp_grads* G,
+                       hipStream_t s) {
+  return chain_backward<DetChain, false, false>(who, x, P, H, dz, dloss, B, d_in, C, 1.f, ws, ws_bytes, dx, G, s);
 }
-
-__global__ __launch_bounds__(256) void k_det_bwd_w(ChainWgradArgs<DetChain::L> A, int B) { chain_bwd_w(A, B); }
 
 // ---- evaluation accumulate ------------------------------------------------------------------------------------------
 // one workgroup: correct += #(argmax targets == argmax probs) (integer LDS atomics: they commute), loss_sum += the batch's
-// mean loss as k_det_mean rounds it to fp32 (the reference sums loss.item() over batches and divides by their number),
+// mean loss as k_chain_mean rounds it to fp32 (the reference sums loss.item() over batches and divides by their number),
 // n += B, batches += 1; one writer.
 __global__ __launch_bounds__(256) void k_det_eval(const float* __restrict__ probs, const float* __restrict__ targets,
                                                   const float* __restrict__ row_loss, int B, int C,
@@ -255,107 +246,62 @@ __global__ __launch_bounds__(256) void k_det_counts(const float* __restrict__ sc
 
 using namespace gww;
 
-extern "C" int gww_det_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                        const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                                        const float* b5, const float* targets, int B, int d_in, int C, float epsilon,
-                                        float* h1, float* h2, float* h3, float* h4, float* logits, float* probs,
-                                        float* row_loss, float* dz, float* loss, void* stream) {
-  GWW_TRY(chain_check_shape("gww_det_head_forward_f32", B, 65536, d_in, C, 2));
-  GWW_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && w5 && b5 && targets, "gww_det_head_forward_f32: NULL input");
-  GWW_REQUIRE(h1 && h2 && h3 && h4 && logits && probs && row_loss && dz && loss, "gww_det_head_forward_f32: NULL output");
-  GWW_REQUIRE(epsilon >= 0.f && epsilon * (float)C < 1.f, "gww_det_head_forward_f32: epsilon=%g must be in [0, 1/C)", (double)epsilon);
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, w5, b1, b2, b3, b4, h1, h2, h3, h4}),
-              "gww_det_head_forward_f32: operands must be 16-byte aligned");
-  const size_t lds = chain_lds_bytes<DetChain>(d_in);
-  hipStream_t s = (hipStream_t)stream;
-  GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<-1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  const ChainFwdArgs<DetChain::L> P{{w1, w2, w3, w4, w5}, {b1, b2, b3, b4, b5}, {h1, h2, h3, h4, logits}};
-  const DetTail S{probs, row_loss, dz};
-  hipLaunchKernelGGL(k_det_fwd<-1>, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, x, P, targets, B, d_in, C, epsilon,
-                     S, (float*)nullptr, 0L);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_det_mean, dim3(1), dim3(256), 0, s, (const float*)row_loss, B, C, loss);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+extern "C" int gww_det_head_forward_f32(const float* x, const gww_mlp_params* params, const float* targets, int B, int d_in,
+                                        int C, float epsilon, const gww_mlp_acts* acts, float* probs, float* row_loss, float* dz,
+                                        float* loss, void* stream) {
+  const char* who = "gww_det_head_forward_f32";
+  GWW_TRY(chain_check_shape(who, B, 65536, d_in, C, 2));
+  GWW_REQUIRE(targets && acts && probs && row_loss && dz && loss, "%s: NULL argument", who);
+  GWW_TRY(chain_check_operands(who, DetChain::L, x, params, acts, nullptr));
+  GWW_REQUIRE(epsilon >= 0.f && epsilon * (float)C < 1.f, "%s: epsilon=%g must be in [0, 1/C)", who, (double)epsilon);
+  return chain_launch_fwd(k_det_fwd<-1>, chain_lds_bytes<DetChain>(d_in), B, row_loss, (double)B * (double)C, loss,
+                          (hipStream_t)stream, x, chain_fwd_args<DetChain::L>(params, acts->h, acts->logits), targets, B, d_in, C,
+                          epsilon, DetTail{probs, row_loss, dz}, (float*)nullptr, 0L);
 }
 
 extern "C" size_t gww_det_head_workspace_bytes(int B, int C) { return chain_workspace_bytes<DetChain>(B, C); }
 
-extern "C" int gww_det_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
-                                         const float* w5, const float* h1, const float* h2, const float* h3, const float* h4,
-                                         const float* dz, const float* dloss, int B, int d_in, int C, float* ws,
-                                         size_t ws_bytes, float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
-                                         float* db3, float* dw4, float* db4, float* dw5, float* db5, void* stream) {
+extern "C" int gww_det_head_backward_f32(const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts, const float* dz,
+                                         const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes, float* dx,
+                                         const gww_mlp_grads* grads, void* stream) {
   GWW_TRY(chain_check_shape("gww_det_head_backward_f32", B, 65536, d_in, C, 2));
-  GWW_REQUIRE(x && w1 && w2 && w3 && w4 && w5 && h1 && h2 && h3 && h4 && dz, "gww_det_head_backward_f32: NULL input");
-  GWW_REQUIRE(ws && dx && dw1 && db1 && dw2 && db2 && dw3 && db3 && dw4 && db4 && dw5 && db5,
-              "gww_det_head_backward_f32: NULL output");
-  GWW_REQUIRE(ws_bytes >= gww_det_head_workspace_bytes(B, C), "gww_det_head_backward_f32: workspace of %zu bytes, %zu needed",
-              ws_bytes, gww_det_head_workspace_bytes(B, C));
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, w5, h1, h2, h3, h4, ws, dx, dw1, dw2, dw3, dw4, dw5}),
-              "gww_det_head_backward_f32: operands must be 16-byte aligned");
-  hipStream_t s = (hipStream_t)stream;
-  ChainBwdArgs<DetChain::L> A{{w1, w2, w3, w4, w5}, {h1, h2, h3, h4}, {}, dx};
-  chain_carve<DetChain>(ws, B, A.dz);
-  hipLaunchKernelGGL(k_det_bwd_in, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), 0, s, dz, dloss, A, B, d_in, C);
-  GWW_LAUNCH_CHECK();
-  ChainWgradArgs<DetChain::L> T;
-  const int grid = chain_wgrad_table<DetChain>(T, x, A, {dw1, dw2, dw3, dw4, dw5}, {db1, db2, db3, db4, db5}, d_in, C);
-  hipLaunchKernelGGL(k_det_bwd_w, dim3((unsigned)grid), dim3(256), 0, s, T, B);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return det_chain_backward("gww_det_head_backward_f32", x, params, acts, dz, dloss, B, d_in, C, ws, ws_bytes, dx, grads,
+                            (hipStream_t)stream);
 }
 
-extern "C" int gww_det_head_scores_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                       const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                                       const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride,
-                                       void* stream) {
-  GWW_TRY(chain_check_shape("gww_det_head_scores_f32", B, 65536, d_in, C, 2));
-  GWW_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && w5 && b5 && out, "gww_det_head_scores_f32: NULL argument");
-  GWW_REQUIRE(mode == 0 || mode == 1, "gww_det_head_scores_f32: mode=%d must be 0 (probs[:, 0]) or 1 (z0 - z1)", mode);
-  GWW_REQUIRE(mode == 0 || C == 2, "gww_det_head_scores_f32: mode 1 (z0 - z1) needs C = 2, not %d", C);
-  GWW_REQUIRE(out_stride >= 1, "gww_det_head_scores_f32: out_stride=%ld must be >= 1", out_stride);
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, w5, b1, b2, b3, b4}), "gww_det_head_scores_f32: operands must be 16-byte aligned");
-  const size_t lds = chain_lds_bytes<DetChain>(d_in);
-  hipStream_t s = (hipStream_t)stream;
-  const ChainFwdArgs<DetChain::L> P{{w1, w2, w3, w4, w5}, {b1, b2, b3, b4, b5}, {}};
-  const DetTail S{};
-  const dim3 grid((unsigned)cdiv(B, CH_ROWS));
-  if (mode == 0) {
-    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_det_fwd<0>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
-  } else {
-    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_det_fwd<1>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
+// The two score entries: one value per row (k_det_fwd<0 / 1>) or all C of them (`both`, k_det_fwd<2 / 3>).
+template <int MODE>
+static int det_launch_scores(const float* x, const gww_mlp_params* P, int B, int d_in, int C, float* out, long out_stride,
+                             void* stream) {
+  return chain_launch_fwd(k_det_fwd<MODE>, chain_lds_bytes<DetChain>(d_in), B, nullptr, 0.0, nullptr, (hipStream_t)stream, x,
+                          chain_fwd_args<DetChain::L>(P, nullptr, nullptr), (const float*)nullptr, B, d_in, C, 0.f, DetTail{}, out,
+                          out_stride);
+}
+static int det_scores(const char* who, bool both, const float* x, const gww_mlp_params* P, int B, int d_in, int C, int mode,
+                      float* out, long out_stride, void* stream) {
+  GWW_TRY(chain_check_shape(who, B, 65536, d_in, C, 2));
+  GWW_REQUIRE(out, "%s: NULL argument", who);
+  GWW_TRY(chain_check_operands(who, DetChain::L, x, P, nullptr, nullptr));
+  GWW_REQUIRE(mode == 0 || mode == 1, "%s: mode=%d must be 0 (%s) or 1 (%s)", who, mode, both ? "probs" : "probs[:, 0]",
+              both ? "z0 - z1, z1 - z0" : "z0 - z1");
+  GWW_REQUIRE(mode == 0 || C == 2, "%s: mode 1 (%s) needs C = 2, not %d", who, both ? "z0 - z1, z1 - z0" : "z0 - z1", C);
+  GWW_REQUIRE(out_stride >= (both ? C : 1), "%s: out_stride=%ld must be >= %d", who, out_stride, both ? C : 1);
+  switch (2 * both + mode) {
+    case 0: return det_launch_scores<0>(x, P, B, d_in, C, out, out_stride, stream);
+    case 1: return det_launch_scores<1>(x, P, B, d_in, C, out, out_stride, stream);
+    case 2: return det_launch_scores<2>(x, P, B, d_in, C, out, out_stride, stream);
+    default: return det_launch_scores<3>(x, P, B, d_in, C, out, out_stride, stream);
   }
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
 }
 
-extern "C" int gww_det_head_scores2_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                                        const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                                        const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride,
-                                        void* stream) {
-  GWW_TRY(chain_check_shape("gww_det_head_scores2_f32", B, 65536, d_in, C, 2));
-  GWW_REQUIRE(x && w1 && b1 && w2 && b2 && w3 && b3 && w4 && b4 && w5 && b5 && out, "gww_det_head_scores2_f32: NULL argument");
-  GWW_REQUIRE(mode == 0 || mode == 1, "gww_det_head_scores2_f32: mode=%d must be 0 (probs) or 1 (z0 - z1, z1 - z0)", mode);
-  GWW_REQUIRE(mode == 0 || C == 2, "gww_det_head_scores2_f32: mode 1 (z0 - z1, z1 - z0) needs C = 2, not %d", C);
-  GWW_REQUIRE(out_stride >= C, "gww_det_head_scores2_f32: out_stride=%ld must be >= C = %d", out_stride, C);
-  GWW_REQUIRE(aligned16({x, w1, w2, w3, w4, w5, b1, b2, b3, b4}), "gww_det_head_scores2_f32: operands must be 16-byte aligned");
-  const size_t lds = chain_lds_bytes<DetChain>(d_in);
-  hipStream_t s = (hipStream_t)stream;
-  const ChainFwdArgs<DetChain::L> P{{w1, w2, w3, w4, w5}, {b1, b2, b3, b4, b5}, {}};
-  const DetTail S{};
-  const dim3 grid((unsigned)cdiv(B, CH_ROWS));
-  if (mode == 0) {
-    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_det_fwd<2>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
-  } else {
-    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_det_fwd<3>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(k_det_fwd<3>, grid, dim3(CH_THREADS), lds, s, x, P, (const float*)nullptr, B, d_in, C, 0.f, S, out, out_stride);
-  }
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+extern "C" int gww_det_head_scores_f32(const float* x, const gww_mlp_params* params, int B, int d_in, int C, int mode, float* out,
+                                       long out_stride, void* stream) {
+  return det_scores("gww_det_head_scores_f32", false, x, params, B, d_in, C, mode, out, out_stride, stream);
+}
+
+extern "C" int gww_det_head_scores2_f32(const float* x, const gww_mlp_params* params, int B, int d_in, int C, int mode,
+                                        float* out, long out_stride, void* stream) {
+  return det_scores("gww_det_head_scores2_f32", true, x, params, B, d_in, C, mode, out, out_stride, stream);
 }
 
 extern "C" int gww_det_eval_accumulate(const float* probs, const float* targets, const float* row_loss, int B, int C,

@@ -1,8 +1,10 @@
-// The exact-fp32 MLP chain behind the glitch head (classify.hip) and the detection head (detect.hip): d_in -> hidden widths
-// -> C, ReLU (and optionally dropout) between the layers.  Every contraction is a v_mfma_f32_16x16x4_f32 chain (bit for
-// bit a k-ordered fmaf chain), no float atomics, every reduction in a fixed order: two identical calls give identical bits,
-// and two heads give identical bits wherever their layers agree.  One workgroup of CH_THREADS owns CH_ROWS rows and walks
-// the whole chain with the activations in two LDS buffers that take turns; the weights stream from L2.
+// The exact-fp32 MLP chain behind the glitch head (classify.hip), the detection head (detect.hip) and the binary heads
+// (binary_head.hip): d_in -> hidden widths -> C, ReLU (and optionally dropout) between the layers.  Every contraction is a
+// v_mfma_f32_16x16x4_f32 chain (bit for bit a k-ordered fmaf chain), no float atomics, every reduction in a fixed order: two
+// identical calls give identical bits, and two heads give identical bits wherever their layers agree.  One workgroup of
+// CH_THREADS owns CH_ROWS rows and walks the whole chain with the activations in two LDS buffers that take turns; the
+// weights stream from L2.  A head is a Chain<...>, a forward kernel with its tail and its C entries; the backward kernels,
+// the loss mean, the operand check and the two host paths (chain_launch_fwd, chain_backward) are here, once.
 #pragma once
 #include <initializer_list>
 
@@ -300,13 +302,13 @@ struct ChainBwdArgs {
   float* dx;
 };
 
-// dz_L (times the device scalar gscale, if given) -> ... -> dx for the workgroup's rows, every layer's dz left in A.dz
+// dz_L (times the device scalar gscale, if given) -> ... -> dx for the workgroup's rows, every layer's dz left in A.dz.
+// buf0 / buf1: the two LDS buffers, [CH_ROWS][CH::bwd_w(b) + CH_PAD] floats, 16-byte aligned.
 template <class CH, bool SCALED>
-__device__ __forceinline__ void chain_bwd(const float* __restrict__ dz_in, const float* __restrict__ gscale,
-                                          const ChainBwdArgs<CH::L>& A, int B, int d_in, int C, float scale) {
+__device__ __forceinline__ void chain_bwd(float* buf0, float* buf1, const float* __restrict__ dz_in,
+                                          const float* __restrict__ gscale, const ChainBwdArgs<CH::L>& A, int B, int d_in, int C,
+                                          float scale) {
   constexpr int L = CH::L, ld[2] = {CH::bwd_w(0) + CH_PAD, CH::bwd_w(1) + CH_PAD};
-  __shared__ __attribute__((aligned(16))) float buf0[CH_ROWS * ld[0]];
-  __shared__ __attribute__((aligned(16))) float buf1[CH_ROWS * ld[1]];
   float* const buf[2] = {buf0, buf1};
   const long row0 = (long)blockIdx.x * CH_ROWS;
   const float g = gscale ? gscale[0] : 1.f;
@@ -332,35 +334,20 @@ __device__ __forceinline__ void chain_bwd(const float* __restrict__ dz_in, const
   chain_layer_bwd<false, false>(buf[s], ld[s], nullptr, 0, A.W[0], CH::out(0), d_in, nullptr, 1.f, A.dx, row0, B);
 }
 
-// chain_bwd over the caller's LDS (sm: CH::bwd_lds_bytes(), 16-byte aligned): a chain whose two buffers pass the 64 KiB of
-// static LDS takes them from the launch.  Same layer walk, same bits.
-template <class CH>
-__device__ __forceinline__ void chain_bwd_at(float* sm, const float* __restrict__ dz_in, const float* __restrict__ gscale,
-                                             const ChainBwdArgs<CH::L>& A, int B, int d_in, int C) {
-  constexpr int L = CH::L, ld[2] = {CH::bwd_w(0) + CH_PAD, CH::bwd_w(1) + CH_PAD};
-  float* const buf[2] = {sm, sm + CH_ROWS * ld[0]};
-  const long row0 = (long)blockIdx.x * CH_ROWS;
-  const float g = gscale ? gscale[0] : 1.f;
-  const int C16 = (C + 15) & ~15;
-  for (int i = threadIdx.x; i < CH_ROWS * C16; i += CH_THREADS) {
-    const int m = i / C16, n = i - m * C16;
-    float v = 0.f;
-    if (row0 + m < B && n < C) {
-      v = g * dz_in[(row0 + m) * C + n];
-      A.dz[L - 1][(row0 + m) * C + n] = v;
-    }
-    buf[0][m * ld[0] + n] = v;
+// The backward-input kernel of a chain.  SCALED: the head has dropout, `scale` = 1 / (1 - p).  DYN_LDS: a chain whose two
+// buffers pass the 64 KiB of static LDS takes its CH::bwd_lds_bytes() from the launch.  Same layer walk, same bits.
+template <class CH, bool SCALED, bool DYN_LDS>
+__global__ __launch_bounds__(CH_THREADS) void k_chain_bwd_in(const float* __restrict__ dz_in, const float* __restrict__ gscale,
+                                                             ChainBwdArgs<CH::L> A, int B, int d_in, int C, float scale) {
+  constexpr int n0 = CH_ROWS * (CH::bwd_w(0) + CH_PAD), n1 = CH_ROWS * (CH::bwd_w(1) + CH_PAD);
+  if constexpr (DYN_LDS) {
+    extern __shared__ __attribute__((aligned(16))) float sm_chain[];
+    chain_bwd<CH, SCALED>(sm_chain, sm_chain + n0, dz_in, gscale, A, B, d_in, C, scale);
+  } else {
+    __shared__ __attribute__((aligned(16))) float buf0[n0];
+    __shared__ __attribute__((aligned(16))) float buf1[n1];
+    chain_bwd<CH, SCALED>(buf0, buf1, dz_in, gscale, A, B, d_in, C, scale);
   }
-  __syncthreads();
-#pragma unroll
-  for (int i = L - 1; i > 0; --i) {
-    const int s = (L - 1 - i) & 1;
-    chain_layer_bwd<true, false>(buf[s], ld[s], buf[s ^ 1], ld[s ^ 1], A.W[i], CH::out(i, C), CH::out(i - 1), A.h[i - 1], 1.f,
-                                 A.dz[i - 1], row0, B);
-    __syncthreads();
-  }
-  constexpr int s = (L - 1) & 1;
-  chain_layer_bwd<false, false>(buf[s], ld[s], nullptr, 0, A.W[0], CH::out(0), d_in, nullptr, 1.f, A.dx, row0, B);
 }
 
 // ---- backward, weight side ------------------------------------------------------------------------------------------
@@ -434,6 +421,22 @@ __device__ __forceinline__ void chain_bwd_w(const ChainWgradArgs<L>& A, int B) {
   }
 }
 
+template <int L>
+__global__ __launch_bounds__(256) void k_chain_bwd_w(ChainWgradArgs<L> A, int B) {
+  chain_bwd_w(A, B);
+}
+
+// loss = sum(row_loss) / div, one workgroup, fp64 partial sums in a fixed tree, rounded to fp32 once.  div: B, or
+// (double)B * (double)C (exact for every admitted B and C).  A template, as the other two, so that only a file that launches
+// it carries it; block_sum_f64 is a tree of 256 threads.
+template <int THREADS>
+__global__ __launch_bounds__(THREADS) void k_chain_mean(const float* __restrict__ row_loss, int B, double div,
+                                                        float* __restrict__ loss) {
+  static_assert(THREADS == 256, "block_sum_f64");
+  const double s = block_sum_f64(row_loss, B);
+  if (threadIdx.x == 0) loss[0] = (float)(s / div);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------
 static int chain_check_shape(const char* who, int B, int Bmax, int d_in, int C, int Cmin) {
   GWW_REQUIRE(B >= 1 && B <= Bmax, "%s: B=%d must be 1..%d", who, B, Bmax);
@@ -445,6 +448,30 @@ static bool aligned16(std::initializer_list<const void*> ps) {
   for (const void* p : ps)
     if (((uintptr_t)p) & 15) return false;
   return true;
+}
+// The one check of a chain's operands (include/gww.h: gww_mlp_params / _acts / _grads).  P->n_layers is the chain's L; x and
+// every pointer of the L layers are non-NULL and 16-byte aligned, except the last layer's bias, the logits and the bias
+// gradients, which are accessed by elements and only have to be there.  G == NULL: a forward, which reads the biases and,
+// with H, writes the activations and the logits.  G != NULL: a backward, which reads w and H->h only.
+static int chain_check_operands(const char* who, int L, const float* x, const gww_mlp_params* P, const gww_mlp_acts* H,
+                                const gww_mlp_grads* G) {
+  GWW_REQUIRE(x && P && (H || !G), "%s: NULL x or parameter block", who);
+  GWW_REQUIRE(P->n_layers == L, "%s: n_layers=%d, but the chain has %d layers", who, P->n_layers, L);
+  bool there = true, al = aligned16({x});
+  auto see = [&](const void* p, bool align) {
+    there = there && p;
+    al = al && !(align && (((uintptr_t)p) & 15));
+  };
+  for (int i = 0; i < L; ++i) {
+    see(P->w[i], true);
+    if (!G) see(P->b[i], i < L - 1);
+    if (H && i < L - 1) see(H->h[i], true);
+    if (G) see(G->dw[i], true), see(G->db[i], false);
+  }
+  if (H && !G) see(H->logits, false);
+  GWW_REQUIRE(there, "%s: NULL pointer among the %d layers' operands", who, L);
+  GWW_REQUIRE(al, "%s: x and the %d layers' operands must be 16-byte aligned", who, L);
+  return GWW_OK;
 }
 // dynamic LDS of the forward walk
 template <class CH>
@@ -466,15 +493,79 @@ static void chain_carve(float* ws, int B, float* (&dz)[CH::L]) {
 }
 // the weight-gradient table of one step (h[0] = x); returns the grid size
 template <class CH>
-static int chain_wgrad_table(ChainWgradArgs<CH::L>& T, const float* x, const ChainBwdArgs<CH::L>& A, float* const (&dW)[CH::L],
-                             float* const (&db)[CH::L], int d_in, int C) {
+static int chain_wgrad_table(ChainWgradArgs<CH::L>& T, const float* x, const ChainBwdArgs<CH::L>& A, const gww_mlp_grads& G,
+                             int d_in, int C) {
   int first = 0;
   for (int i = 0; i < CH::L; ++i) {
     const int N = CH::out(i, C), K = CH::in(i, d_in);
-    T.l[i] = ChainWgradLayer{A.dz[i], i ? A.h[i - 1] : x, dW[i], db[i], N, K, K / 64, first};
+    T.l[i] = ChainWgradLayer{A.dz[i], i ? A.h[i - 1] : x, G.dw[i], G.db[i], N, K, K / 64, first};
     first += (int)cdiv(N, 64) * (K / 64);
   }
   return first;
 }
+
+// The forward kernel's arguments from the blocks.  h == NULL: no hidden activation leaves LDS (the score forms).
+template <int L>
+static ChainFwdArgs<L> chain_fwd_args(const gww_mlp_params* P, float* const* h, float* logits) {
+  ChainFwdArgs<L> A;
+  for (int i = 0; i < L; ++i) {
+    A.W[i] = P->w[i];
+    A.b[i] = P->b[i];
+    A.save[i] = i == L - 1 ? logits : h ? h[i] : nullptr;
+  }
+  return A;
+}
+
+// The forward of every head: the caller's kernel (its chain walk and its tail) over ceil(B / 16) workgroups with `lds`
+// bytes of dynamic LDS, then loss = sum(row_loss) / div.  loss == NULL: no loss, one launch (the score forms).
+template <class... KA, class... A>
+static int chain_launch_fwd(void (*kernel)(KA...), size_t lds, int B, const float* row_loss, double div, float* loss,
+                            hipStream_t s, A... args) {
+  GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL(kernel, dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, args...);
+  GWW_LAUNCH_CHECK();
+  if (!loss) return GWW_OK;
+  hipLaunchKernelGGL(k_chain_mean<256>, dim3(1), dim3(256), 0, s, row_loss, B, div, loss);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// The backward of every head, checks included: k_chain_bwd_in over the same row blocks, then ONE k_chain_bwd_w launch for
+// all the layers.  scale: 1 / (1 - p) of a head with dropout (SCALED), else 1.
+template <class CH, bool SCALED, bool DYN_LDS>
+static int chain_backward(const char* who, const float* x, const gww_mlp_params* P, const gww_mlp_acts* H, const float* dz,
+                          const float* dloss, int B, int d_in, int C, float scale, float* ws, size_t ws_bytes, float* dx,
+                          const gww_mlp_grads* G, hipStream_t s) {
+  constexpr int L = CH::L;
+  GWW_REQUIRE(dz && ws && dx && G, "%s: NULL dz, ws, dx or gradient block", who);
+  GWW_TRY(chain_check_operands(who, L, x, P, H, G));
+  GWW_REQUIRE(aligned16({ws, dx}), "%s: ws and dx must be 16-byte aligned", who);
+  GWW_REQUIRE(ws_bytes >= chain_workspace_bytes<CH>(B, C), "%s: workspace of %zu bytes, %zu needed", who, ws_bytes,
+              chain_workspace_bytes<CH>(B, C));
+  ChainBwdArgs<L> A;
+  for (int i = 0; i < L; ++i) A.W[i] = P->w[i];
+  for (int i = 0; i < L - 1; ++i) A.h[i] = H->h[i];
+  A.dx = dx;
+  chain_carve<CH>(ws, B, A.dz);
+  const size_t lds = DYN_LDS ? CH::bwd_lds_bytes() : 0;
+  if (DYN_LDS)
+    GWW_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_chain_bwd_in<CH, SCALED, DYN_LDS>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((k_chain_bwd_in<CH, SCALED, DYN_LDS>), dim3((unsigned)cdiv(B, CH_ROWS)), dim3(CH_THREADS), lds, s, dz, dloss,
+                     A, B, d_in, C, scale);
+  GWW_LAUNCH_CHECK();
+  ChainWgradArgs<L> T;
+  const int grid = chain_wgrad_table<CH>(T, x, A, *G, d_in, C);
+  hipLaunchKernelGGL(k_chain_bwd_w<L>, dim3((unsigned)grid), dim3(256), 0, s, T, B);
+  GWW_LAUNCH_CHECK();
+  return GWW_OK;
+}
+
+// The backward of Chain<512, 256, 128, 64> without dropout, instantiated once, in detect.hip: the detection head's and the
+// one-detector binary head's.
+using DetChain = Chain<512, 256, 128, 64>;
+int det_chain_backward(const char* who, const float* x, const gww_mlp_params* P, const gww_mlp_acts* H, const float* dz,
+                       const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes, float* dx, const gww_mlp_grads* G,
+                       hipStream_t s);
 
 }  // namespace gww

@@ -1044,6 +1044,18 @@ def _mlp_grads(x, ps, dloss, ws, ws_bytes):
     return dloss, _dev(ws, torch.float32, "ws"), torch.empty_like(x), [torch.empty_like(t) for t in ps]
 
 
+def _mlp_blocks(ps, h=None, logits=None, grads=None):
+    """The blocks the C entries of the heads take (``gww_mlp_params``, ``gww_mlp_acts``, ``gww_mlp_grads``, by reference; None
+    for a list that is not given) from the checked tensors: ps = [w1, b1, ...], the activations h, grads = [dw1, db1, ...]."""
+    def ptrs(ts, n):
+        return (_lib.C.c_void_p * n)(*[t.data_ptr() for t in ts])
+    n = _lib.MLP_MAX_LAYERS
+    blocks = (_lib.MlpParams(len(ps) // 2, ptrs(ps[0::2], n), ptrs(ps[1::2], n)),
+              None if h is None else _lib.MlpActs(ptrs(h, n - 1), None if logits is None else logits.data_ptr()),
+              None if grads is None else _lib.MlpGrads(ptrs(grads[0::2], n), ptrs(grads[1::2], n)))
+    return [b if b is None else _lib.C.byref(b) for b in blocks]
+
+
 def _state(t, dt, shape, who, name):
     if not t.is_cuda or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
         raise _lib.GwwError(f"{who}: {name} must be a contiguous GPU {dt} tensor of shape {shape}")
@@ -1061,10 +1073,10 @@ def head_forward(x, params, labels, p: float = 0.3, train: bool = False, seed: i
     B, dev = x.shape[0], x.device
     h, (logits, dz), row_loss, loss = _mlp_outputs(x, HEAD_WIDTHS, C, 2)
     pred = torch.empty((B,), dtype=torch.int64, device=dev)
+    P, A, _ = _mlp_blocks(ps, h, logits)
     with torch.cuda.device(dev):
-        check(lib().gww_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], labels.data_ptr(), B, d_in, C, float(p),
-                                         int(bool(train)), int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1),
-                                         *[t.data_ptr() for t in h], logits.data_ptr(), row_loss.data_ptr(),
+        check(lib().gww_head_forward_f32(x.data_ptr(), P, labels.data_ptr(), B, d_in, C, float(p), int(bool(train)),
+                                         int(seed) & (2 ** 64 - 1), int(offset) & (2 ** 64 - 1), A, row_loss.data_ptr(),
                                          pred.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()), "gww_head_forward_f32")
     return loss, logits, row_loss, pred, (x, ps, h, dz, float(p), bool(train))
 
@@ -1075,10 +1087,10 @@ def head_backward(saved, dloss=None):
     x, ps, h, dz, p, train = saved
     B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
     dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, None, lib().gww_head_workspace_bytes(B, C))
+    P, A, G = _mlp_blocks(ps, h, None, grads)
     with torch.cuda.device(dev):
-        check(lib().gww_head_backward_f32(x.data_ptr(), *[t.data_ptr() for t in ps[0::2]], *[t.data_ptr() for t in h],
-                                          dz.data_ptr(), dloss, B, d_in, C, p, int(train), ws.data_ptr(), dx.data_ptr(),
-                                          *[g.data_ptr() for g in grads], _stream()), "gww_head_backward_f32")
+        check(lib().gww_head_backward_f32(x.data_ptr(), P, A, dz.data_ptr(), dloss, B, d_in, C, p, int(train), ws.data_ptr(),
+                                          ws.numel() * 4, dx.data_ptr(), G, _stream()), "gww_head_backward_f32")
     return dx, grads
 
 
@@ -1189,9 +1201,9 @@ def det_head_forward(x, params, targets, epsilon: float = 1e-6):
         raise _lib.GwwError(f"det_head_forward: x {tuple(x.shape)} / targets {tuple(targets.shape)} do not fit d_in = {d_in}, "
                             f"C = {C}")
     h, (logits, probs, dz), row_loss, loss = _mlp_outputs(x, DET_WIDTHS, C, 3)
+    P, A, _ = _mlp_blocks(ps, h, logits)
     with torch.cuda.device(x.device):
-        check(lib().gww_det_head_forward_f32(x.data_ptr(), *[t.data_ptr() for t in ps], targets.data_ptr(), x.shape[0], d_in,
-                                             C, float(epsilon), *[t.data_ptr() for t in h], logits.data_ptr(),
+        check(lib().gww_det_head_forward_f32(x.data_ptr(), P, targets.data_ptr(), x.shape[0], d_in, C, float(epsilon), A,
                                              probs.data_ptr(), row_loss.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
               "gww_det_head_forward_f32")
     return loss, logits, probs, row_loss, (x, ps, h, dz)
@@ -1204,10 +1216,10 @@ def det_head_backward(saved, dloss=None, ws=None):
     x, ps, h, dz = saved
     B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
     dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, ws, lib().gww_det_head_workspace_bytes(B, C))
+    P, A, G = _mlp_blocks(ps, h, None, grads)
     with torch.cuda.device(dev):
-        check(lib().gww_det_head_backward_f32(x.data_ptr(), *[t.data_ptr() for t in ps[0::2]], *[t.data_ptr() for t in h],
-                                              dz.data_ptr(), dloss, B, d_in, C, ws.data_ptr(), ws.numel() * 4, dx.data_ptr(),
-                                              *[g.data_ptr() for g in grads], _stream()), "gww_det_head_backward_f32")
+        check(lib().gww_det_head_backward_f32(x.data_ptr(), P, A, dz.data_ptr(), dloss, B, d_in, C, ws.data_ptr(), ws.numel() * 4,
+                                              dx.data_ptr(), G, _stream()), "gww_det_head_backward_f32")
     return dx, grads
 
 
@@ -1223,7 +1235,7 @@ def det_head_scores(x, params, out, mode: int = SCORE_PROB0):
     if not out.is_cuda or out.dtype != torch.float32 or out.dim() != 1 or out.shape[0] != B or (B > 1 and out.stride(0) < 1):
         raise _lib.GwwError(f"det_head_scores: out must be a 1-d fp32 GPU view of {B} elements with a positive stride")
     with torch.cuda.device(x.device):
-        check(lib().gww_det_head_scores_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d_in, C, int(mode), out.data_ptr(),
+        check(lib().gww_det_head_scores_f32(x.data_ptr(), _mlp_blocks(ps)[0], B, d_in, C, int(mode), out.data_ptr(),
                                             max(out.stride(0), 1), _stream()), "gww_det_head_scores_f32")
     return out
 
@@ -1244,7 +1256,7 @@ def det_head_scores2(x, params, out=None, remove_softmax: bool = False):
             or (B > 1 and out.stride(0) < C)):
         raise _lib.GwwError(f"det_head_scores2: out must be an fp32 GPU view [{B}, {C}] with unit column stride")
     with torch.cuda.device(x.device):
-        check(lib().gww_det_head_scores2_f32(x.data_ptr(), *[t.data_ptr() for t in ps], B, d_in, C, 1 if remove_softmax else 0,
+        check(lib().gww_det_head_scores2_f32(x.data_ptr(), _mlp_blocks(ps)[0], B, d_in, C, 1 if remove_softmax else 0,
                                              out.data_ptr(), max(out.stride(0), C), _stream()), "gww_det_head_scores2_f32")
     return out
 
@@ -1262,11 +1274,6 @@ def _bin_layout(layout, params, who):
                                  else "two-detector binary head"))
 
 
-def _ptrs(ts, n):
-    """data pointers of ``ts`` padded with NULL to the ``n`` slots of the C entry"""
-    return [t.data_ptr() for t in ts] + [None] * (n - len(ts))
-
-
 def bin_head_forward(layout: int, x, params, targets):
     """Binary head + BCEWithLogitsLoss forward (``gww_bin_head_forward_f32``, 2 launches): x fp32 [B, d_in], params the
     ``nn.Linear`` tensors of the classifier in order (ten for BIN_HEAD_ONE, eight for BIN_HEAD_TWO), targets fp32 [B, C] in
@@ -1279,10 +1286,11 @@ def bin_head_forward(layout: int, x, params, targets):
         raise _lib.GwwError(f"bin_head_forward: x {tuple(x.shape)} / targets {tuple(targets.shape)} do not fit d_in = {d_in}, "
                             f"C = {C}")
     h, (logits, probs, dz), row_loss, loss = _mlp_outputs(x, widths, C, 3)
+    P, A, _ = _mlp_blocks(ps, h, logits)
     with torch.cuda.device(x.device):
-        check(lib().gww_bin_head_forward_f32(int(layout), x.data_ptr(), *_ptrs(ps, 10), targets.data_ptr(), x.shape[0], d_in, C,
-                                             *_ptrs(h, 4), logits.data_ptr(), probs.data_ptr(), row_loss.data_ptr(),
-                                             dz.data_ptr(), loss.data_ptr(), _stream()), "gww_bin_head_forward_f32")
+        check(lib().gww_bin_head_forward_f32(int(layout), x.data_ptr(), P, targets.data_ptr(), x.shape[0], d_in, C, A,
+                                             probs.data_ptr(), row_loss.data_ptr(), dz.data_ptr(), loss.data_ptr(), _stream()),
+              "gww_bin_head_forward_f32")
     return loss, logits, probs, row_loss, (int(layout), x, ps, h, dz)
 
 
@@ -1293,10 +1301,10 @@ def bin_head_backward(saved, dloss=None, ws=None):
     layout, x, ps, h, dz = saved
     B, d_in, C, dev = x.shape[0], x.shape[1], dz.shape[1], x.device
     dloss, ws, dx, grads = _mlp_grads(x, ps, dloss, ws, lib().gww_bin_head_workspace_bytes(layout, B, C))
+    P, A, G = _mlp_blocks(ps, h, None, grads)
     with torch.cuda.device(dev):
-        check(lib().gww_bin_head_backward_f32(layout, x.data_ptr(), *_ptrs(ps[0::2], 5), *_ptrs(h, 4), dz.data_ptr(), dloss, B,
-                                              d_in, C, ws.data_ptr(), ws.numel() * 4, dx.data_ptr(), *_ptrs(grads, 10),
-                                              _stream()), "gww_bin_head_backward_f32")
+        check(lib().gww_bin_head_backward_f32(layout, x.data_ptr(), P, A, dz.data_ptr(), dloss, B, d_in, C, ws.data_ptr(),
+                                              ws.numel() * 4, dx.data_ptr(), G, _stream()), "gww_bin_head_backward_f32")
     return dx, grads
 
 
@@ -1309,8 +1317,8 @@ def bin_head_scores(layout: int, x, params):
         raise _lib.GwwError(f"bin_head_scores: x {tuple(x.shape)} does not fit d_in = {d_in}")
     logits = torch.empty((x.shape[0], C), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
-        check(lib().gww_bin_head_scores_f32(int(layout), x.data_ptr(), *_ptrs(ps, 10), x.shape[0], d_in, C, logits.data_ptr(),
-                                            _stream()), "gww_bin_head_scores_f32")
+        check(lib().gww_bin_head_scores_f32(int(layout), x.data_ptr(), _mlp_blocks(ps)[0], x.shape[0], d_in, C,
+                                            logits.data_ptr(), _stream()), "gww_bin_head_scores_f32")
     return logits
 
 

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GWW_VERSION 107  /* 0.1.7 (number unchanged; additions are symbols only): + gww_encoder_train_forward_f32 / _backward_f32, gww_train_saved_bytes_f32 / gww_train_workspace_bytes_f32, gww_attention_lse_f32, gww_attention_bwd_f32 / _scratch_bytes, gww_adapter_grads_f32 / _scratch_bytes (exact-fp32 DoRA / LoRA training step); + gww_adapter_grads / _scratch_bytes, gww_train_workspace_bytes_adapters (adapter gradients of fc1 / fc2 and of ranks 1..64; gww_dora_target.proj 4 / 5); + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
+#define GWW_VERSION 108  /* 0.1.8: the glitch, detection and binary heads take their layers in gww_mlp_params / _acts / _grads, every head backward takes ws_bytes; 0.1.7 (additions are symbols only): + gww_encoder_train_forward_f32 / _backward_f32, gww_train_saved_bytes_f32 / gww_train_workspace_bytes_f32, gww_attention_lse_f32, gww_attention_bwd_f32 / _scratch_bytes, gww_adapter_grads_f32 / _scratch_bytes (exact-fp32 DoRA / LoRA training step); + gww_adapter_grads / _scratch_bytes, gww_train_workspace_bytes_adapters (adapter gradients of fc1 / fc2 and of ranks 1..64; gww_dora_target.proj 4 / 5); + gww_encoder_forward_outputs, gww_attention_probs_bf16 / _f32 (per-layer hidden states and attention maps); + gww_info_nce_forward_f32 / _backward_f32, gww_qadapter_tail_backward_f32 / _workspace_bytes, gww_assemble_batch_f32 (MLGWSC-1 training program); + gww_gemm_wgrad_bf16 / _workspace_bytes, gww_layernorm_param_grads / _workspace_bytes, gww_encoder_train_backward_full, gww_train_workspace_bytes_full (full fine-tuning: base-weight gradients); + gww_dora_merge_batch_f32 (all adapted projections of a step in one launch), gww_conv1_gelu_bf16 (conv1 read from the [B, 80, T] feature layout); + gww_frontend_create_nmel, gww_logmel_host_nmel_f32 (128-bin front end of whisper-large-v3), gww_encoder_create takes n_mels 128; 0.1.6: + gww_qadapter_cnn_backward_f32 / _workspace_bytes (the Q-adapter CNN's backward as HIP kernels); 0.1.5: + gww_gemm_bf16_v4_split (explicit column split; no environment switch is read by the library any more); 0.1.4: gww_mlp_fused_bf16 / gww_attn_out_mlp_fused_bf16 with the q / k / v tail return x_next over x (x_out keeps x_new); 0.1.3: + gww_logmel_host_f32 (fork-safe CPU twin of the front end); 0.1.2: + whitening kernels, gww_qadapter_tail_f32, gww_attention_bwd_log2q_bf16, gww_lnqkv_fused_bf16, gww_attn_out_mlp_fused_bf16, gww_mlp_pack_op_bf16; the gww_mlp_pack_bf16 stream carries W1 / 8 and 8 W2 */
 
 #define GWW_OK 0
 #define GWW_ERR_ARG (-1)      /* bad argument (shape, null pointer, unsupported size) */
@@ -699,29 +699,49 @@ int gww_qadapter_tail_backward_f32(const float* g, long g_batch_stride, const fl
  * and snr (fp32) are device arrays of R entries.  A row with an index outside its array is written NaN. */
 int gww_assemble_batch_f32(const float* noise, long n_noise, const float* wave, long n_wave, long row_len,
                            const int* idx_noise, const int* idx_wave, const float* snr, int R, float* out, void* stream);
+/* The layers of an MLP head (head_chain.h): x [B, d_in] -> Linear -> ReLU -> ... -> Linear C.  The glitch, detection and
+ * binary heads take them in these blocks, by pointer; the blocks are host memory, the pointers in them device memory.
+ * n_layers is the number of nn.Linear layers of the head the entry runs (4 or 5; any other count is refused, the text
+ * names both); layer i (0-based) has w[i] [out_i, in_i] and b[i] [out_i] as nn.Linear stores them, writes its activation
+ * h[i] [B, out_i] (the last one: logits [B, C]) and has the gradients dw[i], db[i] of those shapes.  Slots past n_layers
+ * are ignored.  x, every w[i], h[i] and dw[i] and the hidden layers' b[i] are 16-byte aligned; the last bias, the logits
+ * and db[i] need no alignment.  A forward reads params and writes acts, a scores entry reads params, a backward reads
+ * params->w and acts->h (not b, not logits) and writes grads. */
+#define GWW_MLP_MAX_LAYERS 5
+typedef struct gww_mlp_params {
+  int n_layers;
+  const float* w[GWW_MLP_MAX_LAYERS];
+  const float* b[GWW_MLP_MAX_LAYERS];
+} gww_mlp_params;
+typedef struct gww_mlp_acts {
+  float* h[GWW_MLP_MAX_LAYERS - 1];
+  float* logits;
+} gww_mlp_acts;
+typedef struct gww_mlp_grads {
+  float* dw[GWW_MLP_MAX_LAYERS];
+  float* db[GWW_MLP_MAX_LAYERS];
+} gww_mlp_grads;
 /* Glitch-classification head step (classify.hip; fp32 on the exact fp32 MFMA, no float atomics: two identical calls give
  * identical bits).  The head is models.glitch_classifier's nn.Sequential (Glitch_classification/src/model.py:4-39):
  * x [B, d_in] -> Linear 512 -> ReLU -> Dropout(p) -> Linear 256 -> ReLU -> Dropout -> Linear 128 -> ReLU -> Dropout ->
  * Linear C, CrossEntropyLoss (mean) against labels [B] (int64).  d_in a multiple of 128 in 128..1280, C 1..64, B 1..1024;
- * w_i [out, in] and b_i [out] as nn.Linear stores them, every float pointer 16-byte aligned.
- * Forward (2 launches): writes the post-dropout activations h1 [B, 512], h2 [B, 256], h3 [B, 128], logits [B, C],
+ * four layers in the blocks above.
+ * Forward (2 launches): writes the post-dropout activations h[0] [B, 512], h[1] [B, 256], h[2] [B, 128], logits [B, C],
  * row_loss [B] (lse - z[y]; NaN for a label outside [0, C)), pred [B] (int64 argmax: a NaN logit is the maximum, ties go
  * to the lowest index), dz [B, C] = (softmax - onehot) / B and the device scalar loss = mean(row_loss).  train != 0
  * applies dropout: element e = row * width + col of layer l (0..2) is dropped when word e % 4 of
  * Philox4x32-10(counter = (e / 4, l, offset lo, offset hi), key = (seed lo, seed hi)) is below p * 2^32, kept values are
  * scaled by 1 / (1 - p); gww_head_dropout_mask_f32 returns that mask (1 kept / 0 dropped) for a [B, width] activation.
  * Backward (2 launches): reads the upstream gradient of the loss from the device scalar dloss (NULL: 1), writes
- * dx [B, d_in] and the eight parameter gradients (not accumulated); ws: gww_head_workspace_bytes(B, C) bytes. */
-int gww_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                         const float* w3, const float* b3, const float* w4, const float* b4, const long long* labels,
-                         int B, int d_in, int C, float p, int train, unsigned long long seed, unsigned long long offset,
-                         float* h1, float* h2, float* h3, float* logits, float* row_loss, long long* pred, float* dz,
-                         float* loss, void* stream);
+ * dx [B, d_in] and the eight parameter gradients (not accumulated); ws: gww_head_workspace_bytes(B, C) bytes, refused
+ * before any launch when ws_bytes is smaller. */
+int gww_head_forward_f32(const float* x, const gww_mlp_params* params, const long long* labels, int B, int d_in, int C,
+                         float p, int train, unsigned long long seed, unsigned long long offset, const gww_mlp_acts* acts,
+                         float* row_loss, long long* pred, float* dz, float* loss, void* stream);
 size_t gww_head_workspace_bytes(int B, int C);
-int gww_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
-                          const float* h1, const float* h2, const float* h3, const float* dz, const float* dloss, int B,
-                          int d_in, int C, float p, int train, float* ws, float* dx, float* dw1, float* db1, float* dw2,
-                          float* db2, float* dw3, float* db3, float* dw4, float* db4, void* stream);
+int gww_head_backward_f32(const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts, const float* dz,
+                          const float* dloss, int B, int d_in, int C, float p, int train, float* ws, size_t ws_bytes,
+                          float* dx, const gww_mlp_grads* grads, void* stream);
 int gww_head_dropout_mask_f32(unsigned long long seed, unsigned long long offset, int layer, int B, int width, float p,
                               float* mask, void* stream);
 /* Evaluation accumulate, one one-workgroup launch per batch: confusion [C, C] (int64, rows = true class) += 1 at
@@ -734,9 +754,9 @@ int gww_eval_accumulate(const float* logits, const long long* labels, const floa
  * nn.Sequential (Signal_vs_Noise/Efficiency_test/src/network.py:69-90; GWWhisperClassifier has the same stack):
  * x [B, d_in] -> Linear 512 -> ReLU -> Linear 256 -> ReLU -> Linear 128 -> ReLU -> Linear 64 -> ReLU -> Linear C ->
  * Softmax(dim=1), reg_BCELoss(dim=C, epsilon) (tools.py:181-191) against targets [B, C] (float in [0, 1]).
- * d_in a multiple of 128 in 128..1280, C 2..64, B 1..65536, 0 <= epsilon < 1 / C; w_i [out, in] and b_i [out] as nn.Linear
- * stores them; x, w_i, b1..b4, h_i, ws, dx and dw_i 16-byte aligned.
- * Forward (2 launches): writes h1 [B, 512], h2 [B, 256], h3 [B, 128], h4 [B, 64] (post-ReLU), logits [B, C], probs [B, C],
+ * d_in a multiple of 128 in 128..1280, C 2..64, B 1..65536, 0 <= epsilon < 1 / C; five layers in the blocks above; ws and
+ * dx 16-byte aligned.
+ * Forward (2 launches): writes h[0] [B, 512] .. h[3] [B, 64] (post-ReLU), logits [B, C], probs [B, C],
  * row_loss [B] = sum over c of -[t log q + (1 - t) log(1 - q)] with q = epsilon + (1 - C epsilon) p and both logs clamped
  * at -100 as nn.BCELoss clamps them, the device scalar loss = sum(row_loss) / (B C) (fp64 partial sums in a fixed tree),
  * and dz [B, C] = d loss / d logits through the softmax, with torch's (q - t) / max((1 - q) q, 1e-12) / (B C) as the q
@@ -747,20 +767,15 @@ int gww_eval_accumulate(const float* logits, const long long* labels, const floa
  * before any launch when ws_bytes is smaller.
  * Scores (1 launch, inference only): out[r * out_stride] = probs[r, 0] (mode 0) or z0 - z1 (mode 1, C = 2 only: column 0
  * of the reference's remove_softmax layer [[1, -1], [-1, 1]]), bit for bit what the forward gives. */
-int gww_det_head_forward_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                             const float* b5, const float* targets, int B, int d_in, int C, float epsilon, float* h1,
-                             float* h2, float* h3, float* h4, float* logits, float* probs, float* row_loss, float* dz,
-                             float* loss, void* stream);
+int gww_det_head_forward_f32(const float* x, const gww_mlp_params* params, const float* targets, int B, int d_in, int C,
+                             float epsilon, const gww_mlp_acts* acts, float* probs, float* row_loss, float* dz, float* loss,
+                             void* stream);
 size_t gww_det_head_workspace_bytes(int B, int C);
-int gww_det_head_backward_f32(const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
-                              const float* w5, const float* h1, const float* h2, const float* h3, const float* h4,
-                              const float* dz, const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes,
-                              float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dw4,
-                              float* db4, float* dw5, float* db5, void* stream);
-int gww_det_head_scores_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                            const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                            const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride, void* stream);
+int gww_det_head_backward_f32(const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts, const float* dz,
+                              const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes, float* dx,
+                              const gww_mlp_grads* grads, void* stream);
+int gww_det_head_scores_f32(const float* x, const gww_mlp_params* params, int B, int d_in, int C, int mode, float* out,
+                            long out_stride, void* stream);
 /* Evaluation accumulate, one one-workgroup launch per batch: correct (int64) += the rows with argmax(targets) ==
  * argmax(probs) (a NaN is the maximum, ties go to the lowest index), loss_sum (fp64) += the batch's mean loss
  * (float)(sum(row_loss) / (B C)), one writer, n (int64) += B, batches (int64) += 1: the reference's validation loss is
@@ -899,9 +914,8 @@ int gww_trig_steps_f64(const double* fp_sorted, const int* n_fp, long cap, const
 /* Both outputs of the detection head per row, inference only, one launch (test_network.py): out [B, C] fp32 with row
  * pitch out_stride >= C.  mode 0: the softmax, the bits of gww_det_head_forward_f32's probs; mode 1 (C = 2): (z0 - z1,
  * z1 - z0), the reference's --remove-softmax layer.  Operands as gww_det_head_scores_f32. */
-int gww_det_head_scores2_f32(const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                             const float* b5, int B, int d_in, int C, int mode, float* out, long out_stride, void* stream);
+int gww_det_head_scores2_f32(const float* x, const gww_mlp_params* params, int B, int d_in, int C, int mode, float* out,
+                             long out_stride, void* stream);
 /* CNN decoder head of the two-detector model (cnn_head.hip; models.TwoChannelLIGOBinaryClassifierCNN, the reference's
  * Signal_vs_Noise/src/model.py:57-85): per sample x [2, d] -> Conv1d(2, 64, 3, pad 1) -> ReLU -> Conv1d(64, 128, 3, pad 1)
  * -> ReLU -> Conv1d(128, 256, 3, pad 1) -> ReLU -> mean over d -> Linear(256, C).  Exact fp32 (the wide convolutions are
@@ -933,34 +947,29 @@ int gww_cast_f32_bf16(const float* x, void* y, long n, void* stream);
  *   GWW_BIN_HEAD_ONE  one_channel_ligo_binary_classifier: x [B, d_in] -> 512 -> 256 -> 128 -> 64 -> C, five layers,
  *                     d_in a multiple of 128 in 128..1280
  *   GWW_BIN_HEAD_TWO  two_channel_ligo_binary_classifier: x [B, d_in] -> 1024 -> 512 -> 256 -> C, four layers, d_in a
- *                     multiple of 256 in 256..2560; w5, b5, h4, dw5, db5 are ignored (pass NULL)
- * C 1..64, B 1..65536; w_i [out, in] and b_i [out] as nn.Linear stores them; x, w_i, the hidden layers' b_i, h_i, ws, dx
- * and dw_i 16-byte aligned.
- * Forward (2 launches): writes the post-ReLU activations h_i [B, width_i], logits [B, C], probs [B, C] = sigmoid(z),
+ *                     multiple of 256 in 256..2560
+ * C 1..64, B 1..65536; the layers in the blocks above (n_layers 5 or 4, as the layout has them); ws and dx 16-byte aligned.
+ * Forward (2 launches): writes the post-ReLU activations h[i] [B, width_i], logits [B, C], probs [B, C] = sigmoid(z),
  * row_loss [B] = sum over c of max(z, 0) - z t + log1p(exp(-|z|)) (torch's form), the device scalar loss = sum(row_loss) /
  * (B C) (fp64 partial sums in a fixed tree, rounded once) and dz [B, C] = (sigmoid(z) - t) / (B C), formed as
  * ((1 - t) p - t (1 - p)) / (B C) with 1 - p from the exponential, never by subtraction.  Everything behind the fp32
  * logits is evaluated in fp64 and rounded to fp32 once per output.  At equal weights and C the logits of GWW_BIN_HEAD_ONE
- * are the bits of gww_det_head_forward_f32's.
+ * are the bits of gww_det_head_forward_f32's, and its backward is the detection head's own kernels.
  * Backward (2 launches): reads the upstream gradient of the loss from the device scalar dloss (NULL: 1), writes
  * dx [B, d_in] and every parameter gradient (not accumulated); ws: gww_bin_head_workspace_bytes(layout, B, C) bytes (0 for
  * an unknown layout), refused before any launch when ws_bytes is smaller.
  * Scores (1 launch, inference only): logits [B, C], bit for bit the forward's. */
 #define GWW_BIN_HEAD_ONE 1
 #define GWW_BIN_HEAD_TWO 2
-int gww_bin_head_forward_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                             const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                             const float* b5, const float* targets, int B, int d_in, int C, float* h1, float* h2, float* h3,
-                             float* h4, float* logits, float* probs, float* row_loss, float* dz, float* loss, void* stream);
+int gww_bin_head_forward_f32(int layout, const float* x, const gww_mlp_params* params, const float* targets, int B, int d_in,
+                             int C, const gww_mlp_acts* acts, float* probs, float* row_loss, float* dz, float* loss,
+                             void* stream);
 size_t gww_bin_head_workspace_bytes(int layout, int B, int C);
-int gww_bin_head_backward_f32(int layout, const float* x, const float* w1, const float* w2, const float* w3, const float* w4,
-                              const float* w5, const float* h1, const float* h2, const float* h3, const float* h4,
+int gww_bin_head_backward_f32(int layout, const float* x, const gww_mlp_params* params, const gww_mlp_acts* acts,
                               const float* dz, const float* dloss, int B, int d_in, int C, float* ws, size_t ws_bytes,
-                              float* dx, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dw4,
-                              float* db4, float* dw5, float* db5, void* stream);
-int gww_bin_head_scores_f32(int layout, const float* x, const float* w1, const float* b1, const float* w2, const float* b2,
-                            const float* w3, const float* b3, const float* w4, const float* b4, const float* w5,
-                            const float* b5, int B, int d_in, int C, float* logits, void* stream);
+                              float* dx, const gww_mlp_grads* grads, void* stream);
+int gww_bin_head_scores_f32(int layout, const float* x, const gww_mlp_params* params, int B, int d_in, int C, float* logits,
+                            void* stream);
 
 #ifdef __cplusplus
 }

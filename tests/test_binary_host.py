@@ -110,12 +110,30 @@ def test_workspace_bytes_and_argument_errors_without_gpu():
     assert lib.gww_bin_head_workspace_bytes(1, 3, 1) == 3 * (512 + 256 + 128 + 64 + 1) * 4
     assert lib.gww_bin_head_workspace_bytes(2, 33, 64) == 33 * (1024 + 512 + 256 + 64) * 4
     assert lib.gww_bin_head_workspace_bytes(3, 33, 64) == 0 and lib.gww_bin_head_workspace_bytes(1, 0, 1) == 0
-    nul = [None] * 11
-    assert lib.gww_bin_head_scores_f32(3, *nul, 1, 128, 1, None, None) == -1 and b"layout" in lib.gww_last_error()
-    assert lib.gww_bin_head_scores_f32(2, *nul, 1, 1408, 1, None, None) == -1 and b"256" in lib.gww_last_error()
-    assert lib.gww_bin_head_scores_f32(1, *nul, 1, 1408, 1, None, None) == -1 and b"128" in lib.gww_last_error()
-    assert lib.gww_bin_head_scores_f32(1, *nul, 1, 128, 65, None, None) == -1 and b"C=65" in lib.gww_last_error()
-    assert lib.gww_bin_head_scores_f32(1, *nul, 1, 128, 1, None, None) == -1 and b"NULL" in lib.gww_last_error()
+    from gw_whisper_amd import _lib
+    nul = _lib.C.byref(_lib.MlpParams(5))         # five layers, every pointer NULL
+    assert lib.gww_bin_head_scores_f32(3, None, nul, 1, 128, 1, None, None) == -1 and b"layout" in lib.gww_last_error()
+    assert lib.gww_bin_head_scores_f32(2, None, nul, 1, 1408, 1, None, None) == -1 and b"256" in lib.gww_last_error()
+    assert lib.gww_bin_head_scores_f32(1, None, nul, 1, 1408, 1, None, None) == -1 and b"128" in lib.gww_last_error()
+    assert lib.gww_bin_head_scores_f32(1, None, nul, 1, 128, 65, None, None) == -1 and b"C=65" in lib.gww_last_error()
+    assert lib.gww_bin_head_scores_f32(1, None, nul, 1, 128, 1, None, None) == -1 and b"NULL" in lib.gww_last_error()
+
+
+def test_a_block_of_the_wrong_layer_count_is_refused_without_gpu():
+    """The two-detector head has four layers: a five-layer block is refused, and the text names both counts."""
+    import gw_whisper_amd
+    from gw_whisper_amd import _lib
+    lib = gw_whisper_amd.lib()
+    p = 1 << 12                                   # non-NULL, 16-byte aligned stand-in: nothing is dereferenced before the checks
+    five = (_lib.C.c_void_p * 5)(*([p] * 5))
+    block = _lib.MlpParams(5, five, five)
+    assert lib.gww_bin_head_scores_f32(2, p, _lib.C.byref(block), 1, 256, 1, p, None) == -1
+    msg = lib.gww_last_error().decode()
+    assert "gww_bin_head_scores_f32" in msg and "n_layers=5" in msg and "4 layers" in msg
+    block.n_layers = 4
+    assert lib.gww_bin_head_scores_f32(1, p, _lib.C.byref(block), 1, 128, 1, p, None) == -1
+    msg = lib.gww_last_error().decode()
+    assert "n_layers=4" in msg and "5 layers" in msg
 
 
 def test_models_pooled_is_what_forward_feeds_the_classifier():

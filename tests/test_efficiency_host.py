@@ -212,17 +212,22 @@ def test_argument_errors_without_gpu():
     """Shape, mode and workspace checks come before any HIP call."""
     from gw_whisper_amd import lib
     L = lib()
+    from gw_whisper_amd import _lib
     p = [1 << 12] * 12          # non-NULL, 16-byte aligned stand-ins: nothing is dereferenced before the checks
-    assert L.gww_det_head_forward_f32(*p, 4, 100, 2, 1e-6, *p[:9], None) == -1 and b"d_in" in L.gww_last_error()
-    assert L.gww_det_head_forward_f32(*p, 4, 128, 1, 1e-6, *p[:9], None) == -1 and b"C=" in L.gww_last_error()
-    assert L.gww_det_head_forward_f32(*p, 4, 128, 2, 0.5, *p[:9], None) == -1 and b"epsilon" in L.gww_last_error()
-    assert L.gww_det_head_forward_f32(*p, 0, 128, 2, 1e-6, *p[:9], None) == -1 and b"B=" in L.gww_last_error()
+    five = (_lib.C.c_void_p * 5)(*p[:5])
+    P, A, G = (_lib.C.byref(b) for b in (_lib.MlpParams(5, five, five), _lib.MlpActs((_lib.C.c_void_p * 4)(*p[:4]), p[0]),
+                                         _lib.MlpGrads(five, five)))
+    assert L.gww_det_head_forward_f32(p[0], P, p[0], 4, 100, 2, 1e-6, A, *p[:4], None) == -1 and b"d_in" in L.gww_last_error()
+    assert L.gww_det_head_forward_f32(p[0], P, p[0], 4, 128, 1, 1e-6, A, *p[:4], None) == -1 and b"C=" in L.gww_last_error()
+    assert L.gww_det_head_forward_f32(p[0], P, p[0], 4, 128, 2, 0.5, A, *p[:4], None) == -1 and b"epsilon" in L.gww_last_error()
+    assert L.gww_det_head_forward_f32(p[0], P, p[0], 0, 128, 2, 1e-6, A, *p[:4], None) == -1 and b"B=" in L.gww_last_error()
     need = L.gww_det_head_workspace_bytes(4, 2)
     assert need == 4 * (512 + 256 + 128 + 64 + 2) * 4
-    assert L.gww_det_head_backward_f32(*p, 4, 128, 2, p[0], need - 1, *p[:11], None) == -1 and b"workspace" in L.gww_last_error()
-    assert L.gww_det_head_scores_f32(*p[:11], 4, 128, 3, 1, p[0], 1, None) == -1 and b"C = 2" in L.gww_last_error()
-    assert L.gww_det_head_scores_f32(*p[:11], 4, 128, 2, 2, p[0], 1, None) == -1 and b"mode" in L.gww_last_error()
-    assert L.gww_det_head_scores_f32(*p[:11], 4, 128, 2, 0, p[0], 0, None) == -1 and b"stride" in L.gww_last_error()
+    assert (L.gww_det_head_backward_f32(p[0], P, A, p[0], p[0], 4, 128, 2, p[0], need - 1, p[0], G, None) == -1
+            and b"workspace" in L.gww_last_error())
+    assert L.gww_det_head_scores_f32(p[0], P, 4, 128, 3, 1, p[0], 1, None) == -1 and b"C = 2" in L.gww_last_error()
+    assert L.gww_det_head_scores_f32(p[0], P, 4, 128, 2, 2, p[0], 1, None) == -1 and b"mode" in L.gww_last_error()
+    assert L.gww_det_head_scores_f32(p[0], P, 4, 128, 2, 0, p[0], 0, None) == -1 and b"stride" in L.gww_last_error()
     ws = L.gww_score_thresholds_workspace_bytes()
     assert L.gww_score_thresholds_f32(p[0], 10, p[0], 9, p[0], p[0], ws, None) == -1 and b"F=" in L.gww_last_error()
     assert L.gww_score_thresholds_f32(p[0], 10, p[0], 2, p[0], p[0], ws - 1, None) == -1 and b"workspace" in L.gww_last_error()

@@ -176,11 +176,11 @@ def test_cpu_tensors_and_bad_shapes_are_refused():
         glitch._head_parameters(torch.nn.Sequential(torch.nn.Linear(4, 4)))
     # the C ABI validates shapes before any HIP call
     lib = gw_whisper_amd.lib()
-    assert lib.gww_head_forward_f32(*([None] * 10), 4, 100, 4, 0.3, 0, 0, 0, *([None] * 9)) == -1
+    assert lib.gww_head_forward_f32(None, None, None, 4, 100, 4, 0.3, 0, 0, 0, *([None] * 6)) == -1
     assert b"d_in" in lib.gww_last_error()
-    assert lib.gww_head_forward_f32(*([None] * 10), 4, 128, 65, 0.3, 0, 0, 0, *([None] * 9)) == -1
-    assert lib.gww_head_forward_f32(*([None] * 10), 2000, 128, 4, 0.3, 0, 0, 0, *([None] * 9)) == -1
-    assert lib.gww_head_backward_f32(*([None] * 10), 4, 128, 0, 0.3, 0, *([None] * 11)) == -1
+    assert lib.gww_head_forward_f32(None, None, None, 4, 128, 65, 0.3, 0, 0, 0, *([None] * 6)) == -1
+    assert lib.gww_head_forward_f32(None, None, None, 2000, 128, 4, 0.3, 0, 0, 0, *([None] * 6)) == -1
+    assert lib.gww_head_backward_f32(*([None] * 5), 4, 128, 0, 0.3, 0, None, 0, None, None, None) == -1
     assert lib.gww_eval_accumulate(None, None, None, 4, 4, None, None, None, None) == -1
     assert lib.gww_head_workspace_bytes(32, 11) == 32 * (512 + 256 + 128 + 11) * 4
 

@@ -189,6 +189,26 @@ def test_one_detector_logits_are_the_detection_heads(T, gww):
         assert T.equal(ops.bin_head_scores(ops.BIN_HEAD_ONE, x, params), zdet)
 
 
+def test_one_detector_backward_is_the_detection_heads(T, gww):
+    """... and so is its backward: from the same dz and upstream gradient, dx and all ten gradients are the bits of
+    ops.det_head_backward's.  B = 17: one full 16-row block and a ragged one; d_in = 128: the smallest width; C = 2: below a
+    16-column tile."""
+    from gw_whisper_amd import ops, synth
+    d_in, B, C = 128, 17, 2
+    sd = synth.head_state_dict([d_in, 512, 256, 128, 64, C], seed=31)
+    params = [T.from_numpy(sd[k]).cuda() for k in bh.param_keys(bh.ONE)]
+    x, t = bh.case_inputs(d_in, C, B, 77)
+    x, t = T.from_numpy(x).cuda(), T.from_numpy(t).cuda()
+    ops.det_head_forward(x, params, t)
+    *_, (_, xs, ps, h, dz) = ops.bin_head_forward(ops.BIN_HEAD_ONE, x, params, t)
+    up = T.tensor([0.37], device="cuda")
+    dx_bin, g_bin = ops.bin_head_backward((ops.BIN_HEAD_ONE, xs, ps, h, dz), up)
+    dx_det, g_det = ops.det_head_backward((xs, ps, h, dz), up)
+    assert len(g_bin) == len(g_det) == 10
+    for a, b in zip([dx_bin, *g_bin], [dx_det, *g_det]):
+        assert T.equal(a.view(T.int32), b.view(T.int32))
+
+
 @pytest.mark.parametrize("ci", (2, 8))
 def test_binary_eval_accumulate_gives_the_forwards_loss(T, gww, golden, ci):
     """roc.BinaryEvalState on the kernel's logits against the forward's loss.  Both are fp64 evaluations of the same fp32

@@ -1423,8 +1423,9 @@ def test_training_workspace_is_scratch_between_forward_and_backward(T, gww, name
 def test_undersized_workspaces_are_refused_before_any_launch(T, gww):
     """Every *_bytes-sized argument one byte short: GWW_ERR_WORKSPACE (-3) from the host check, gww_last_error() naming the
     entry point.  Every buffer handed over has its full size all the same: nothing is ever launched on less.  (The
-    adapter-gradient scratch is optional by contract -- a short one makes the call use library-owned memory -- and
-    gww_head_backward_f32 takes no size: neither has such a check.)"""
+    adapter-gradient scratch is optional by contract -- a short one makes the call use library-owned memory -- and has no
+    such check.  gww_head_backward_f32 refuses as the detection and binary heads' backward do, through the argument check of
+    the shared host path: GWW_ERR_ARG (-1) and "workspace" in the text.)"""
     from gw_whisper_amd import _lib
     from gw_whisper_amd.qscan import QTransformAdapter
     L = _lib.lib()
@@ -1509,4 +1510,18 @@ def test_undersized_workspaces_are_refused_before_any_launch(T, gww):
                                              one.data_ptr(), one.data_ptr(), one.data_ptr(), f32(Bt, Hin, Win).data_ptr(),
                                              u8(need).data_ptr(), need - 1, one.data_ptr(), one.data_ptr(), one.data_ptr(),
                                              one.data_ptr(), st), "gww_qadapter_tail_backward_f32")
+    # glitch head backward
+    from gw_whisper_amd import ops
+    B, d_in, Cc = 5, 128, 3
+    dims = (d_in, *ops.HEAD_WIDTHS, Cc)
+    params = [f32(*s) for i in range(4) for s in ((dims[i + 1], dims[i]), (dims[i + 1],))]
+    *_, (x, ps, hs, dz, p, train) = ops.head_forward(f32(B, d_in), params, T.zeros((B,), dtype=T.int64, device="cuda"))
+    need = L.gww_head_workspace_bytes(B, Cc)
+    ws, dx, grads = u8(need), f32(B, d_in), [f32(*t.shape) for t in ps]
+    P, A, G = ops._mlp_blocks(ps, hs, None, grads)
+    for nbytes, rc in ((need - 1, -1), (need, 0)):
+        assert L.gww_head_backward_f32(x.data_ptr(), P, A, dz.data_ptr(), None, B, d_in, Cc, p, int(train), ws.data_ptr(), nbytes,
+                                       dx.data_ptr(), G, st) == rc
+        msg = L.gww_last_error().decode()
+        assert rc == 0 or ("gww_head_backward_f32" in msg and "workspace" in msg), msg
     T.cuda.synchronize()

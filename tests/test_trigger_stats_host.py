@@ -216,7 +216,10 @@ def test_c_entry_points_refuse_before_any_launch():
     assert b"workspace" in lib.gww_last_error()
     assert lib.gww_trig_steps_f64(p, p, 5000, p, p, 5000, 0.0, 1.0, 3.0, p, p, p, p, p, p, p, 1 << 30, None) == -1
     assert b"duration" in lib.gww_last_error()
-    assert lib.gww_det_head_scores2_f32(*([p] * 11), 4, 128, 2, 2, p, 2, None) == -1
+    from gw_whisper_amd import _lib
+    five = (_lib.C.c_void_p * 5)(*([p] * 5))
+    P = _lib.C.byref(_lib.MlpParams(5, five, five))
+    assert lib.gww_det_head_scores2_f32(p, P, 4, 128, 2, 2, p, 2, None) == -1
     assert b"mode" in lib.gww_last_error()
-    assert lib.gww_det_head_scores2_f32(*([p] * 11), 4, 128, 2, 0, p, 1, None) == -1
+    assert lib.gww_det_head_scores2_f32(p, P, 4, 128, 2, 0, p, 1, None) == -1
     assert b"out_stride" in lib.gww_last_error()
