@@ -320,6 +320,10 @@ SIGNATURES = {
     "gww_bin_head_backward_f32": (C.c_int, [C.c_int, C.c_void_p, _MLP_P, _MLP_A, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                             C.c_void_p, C.c_size_t, C.c_void_p, _MLP_G, C.c_void_p]),
     "gww_bin_head_scores_f32": (C.c_int, [C.c_int, C.c_void_p, _MLP_P, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gww_head_scan_f32": (C.c_int, [C.c_void_p, _MLP_P, C.c_int, C.c_int, C.c_int, C.c_long] + [C.c_void_p] * 4),
+    "gww_glitch_events_workspace_bytes": (C.c_size_t, [C.c_long]),
+    "gww_glitch_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_double, C.c_ulonglong, C.c_int]
+                          + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
 }
 
 ABI_VERSION = 108   # include/gww.h GWW_VERSION this binding was written against

@@ -1081,6 +1081,72 @@ def head_forward(x, params, labels, p: float = 0.3, train: bool = False, seed: i
     return loss, logits, row_loss, pred, (x, ps, h, dz, float(p), bool(train))
 
 
+def head_scan(x, params, cls=None, prob=None, probs=None, row_offset: int = 0, n_rows: int | None = None,
+              want_probs: bool = False):
+    """The glitch head in eval mode (``gww_head_scan_f32``, one launch, nothing saved): x fp32 [B, d_in], params as
+    ``head_forward`` takes them.  Row r of the batch writes element ``row_offset + r`` of ``cls`` (int32: the class, by
+    ``head_forward``'s argmax rule), ``prob`` (fp32: its softmax probability) and, if there, ``probs`` [., C].  Without
+    ``cls`` / ``prob`` they are allocated here with ``n_rows`` rows (default: ``row_offset + B``; ``probs`` with
+    ``want_probs``) -- a scan allocates them series-long with its first batch and hands them back with every later one.
+    Returns (cls, prob, probs or None)."""
+    x = _dev(x, torch.float32, "x")
+    ps, d_in, C = _mlp_params(params, HEAD_WIDTHS, "head", "glitch head")
+    if x.dim() != 2 or x.shape[1] != d_in:
+        raise _lib.GwwError(f"head_scan: x {tuple(x.shape)} does not fit d_in = {d_in}")
+    B, dev, row_offset = x.shape[0], x.device, int(row_offset)
+    if (cls is None) != (prob is None):
+        raise _lib.GwwError("head_scan: give both cls and prob, or neither")
+    if cls is None:
+        n_rows = row_offset + B if n_rows is None else int(n_rows)
+        cls = torch.empty((n_rows,), dtype=torch.int32, device=dev)
+        prob = torch.empty((n_rows,), dtype=torch.float32, device=dev)
+        if want_probs:
+            probs = torch.empty((n_rows, C), dtype=torch.float32, device=dev)
+    n_rows = int(cls.shape[0]) if cls.dim() == 1 else -1
+    _state(cls, torch.int32, (n_rows,), "head_scan", "cls")
+    _state(prob, torch.float32, (n_rows,), "head_scan", "prob")
+    if probs is not None:
+        _state(probs, torch.float32, (n_rows, C), "head_scan", "probs")
+    if row_offset < 0 or row_offset + B > n_rows:
+        raise _lib.GwwError(f"head_scan: rows {row_offset} .. {row_offset + B - 1} do not fit outputs of {n_rows} rows")
+    P, _, _ = _mlp_blocks(ps)
+    with torch.cuda.device(dev):
+        check(lib().gww_head_scan_f32(x.data_ptr(), P, B, d_in, C, row_offset, cls.data_ptr(), prob.data_ptr(),
+                                      None if probs is None else probs.data_ptr(), _stream()), "gww_head_scan_f32")
+    return cls, prob, probs
+
+
+def glitch_events(times, cls, prob, prob_threshold: float = 0.5, gap: float = 0.35, ignore: int = 0, cap: int | None = None):
+    """The events of every class from the per-window results of one series (``gww_glitch_events``, two launches, no host
+    sync): times fp64 [n], cls int32 [n], prob fp32 [n]; ``ignore``: bit c set skips class c.  Returns a dict of device
+    tensors of ``cap`` entries (default n, which cannot overflow) -- ``cls`` ``first`` ``n`` (int32), ``t_start`` ``t_end``
+    ``t_peak`` (fp64), ``p_peak`` (fp32) -- and ``count`` int32 [1], which counts on past ``cap``; the semantics are
+    ``glitch_scan.build_events_host``'s, bit for bit."""
+    times = _dev(times, torch.float64, "times")
+    cls = _dev(cls, torch.int32, "cls")
+    prob = _dev(prob, torch.float32, "prob")
+    if times.dim() != 1 or cls.shape != times.shape or prob.shape != times.shape:
+        raise _lib.GwwError(f"glitch_events: times {tuple(times.shape)}, cls {tuple(cls.shape)} and prob {tuple(prob.shape)} "
+                            "must be [n]")
+    n, dev = int(times.shape[0]), times.device
+    cap = n if cap is None else int(cap)
+    ignore = int(ignore)
+    if cap < 0 or not 0 <= ignore < 2 ** 64:
+        raise _lib.GwwError(f"glitch_events: cap={cap} must be >= 0 and ignore a 64-bit mask")
+    ev = {k: torch.empty((cap,), dtype=dt, device=dev)
+          for k, dt in (("cls", torch.int32), ("first", torch.int32), ("n", torch.int32), ("t_start", torch.float64),
+                        ("t_end", torch.float64), ("t_peak", torch.float64), ("p_peak", torch.float32))}
+    ev["count"] = torch.empty((1,), dtype=torch.int32, device=dev)
+    ws_bytes = lib().gww_glitch_events_workspace_bytes(n)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_glitch_events(times.data_ptr(), cls.data_ptr(), prob.data_ptr(), n, float(prob_threshold), float(gap),
+                                      ignore, cap, *[ev[k].data_ptr() for k in ("cls", "first", "n", "t_start", "t_end",
+                                                                                "t_peak", "p_peak", "count")],
+                                      ws.data_ptr(), ws_bytes, _stream()), "gww_glitch_events")
+    return ev
+
+
 def head_backward(saved, dloss=None):
     """(dx [B, d_in], [dw1, db1, ..., dw4, db4]) of ``head_forward``'s loss times the device scalar ``dloss``
     (``gww_head_backward_f32``, 2 launches; no host sync)."""

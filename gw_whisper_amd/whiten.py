@@ -135,6 +135,8 @@ def design_filter(psd_w: torch.Tensor, delta_f_w: float, n: int, delta_t: float,
     # test.  No K <= K_MAX passes both: return the frequency response instead and let the caller apply it with the
     # N-point transform.
     K = max(t0, 64)
+    if K > K_MAX:             # a filter that is too long before any doubling (4 s at 2048 Hz: 2 K + 1 = 8193 taps)
+        return None, wf
     total = h.abs().sum(dim=1)
     while True:
         rest = total - h[:, :K + 1].abs().sum(dim=1) - h[:, N - K:].abs().sum(dim=1)

@@ -970,6 +970,29 @@ int gww_bin_head_backward_f32(int layout, const float* x, const gww_mlp_params* 
                               float* dx, const gww_mlp_grads* grads, void* stream);
 int gww_bin_head_scores_f32(int layout, const float* x, const gww_mlp_params* params, int B, int d_in, int C, float* logits,
                             void* stream);
+/* ---- glitch scan (csrc/glitch_scan.hip) ----
+ * gww_head_scan_f32: the glitch head of gww_head_forward_f32 in eval mode (no dropout, no labels, nothing saved), ONE launch:
+ * x fp32 [B, d_in] -> for row r of the batch, at element row_offset + r of the caller's arrays, cls (int32: the argmax of
+ * the logits by gww_head_forward_f32's rule -- a NaN is the maximum, ties go to the lowest index), prob (fp32: the softmax
+ * probability of that class, 1 / sum_j expf(z_j - z_max)) and, when probs is not NULL, probs [., C] = expf(z_j - z_max) /
+ * sum.  The logits are the bits gww_head_forward_f32(train = 0) writes.  Shapes as there: d_in a multiple of 128 in
+ * 128..1280, C 1..64, B 1..1024; params holds four layers, acts are not needed.
+ * gww_glitch_events: the events of every class from the per-window results of one series, on the device, no host
+ * synchronisation: times fp64 [n] (the slicer's stamps), cls int32 [n], prob fp32 [n].  Window i triggers when
+ * 0 <= cls[i] < 64, bit cls[i] of ignore is clear and prob[i] > prob_threshold (a NaN never triggers).  The triggers of one
+ * class, in order, join the class's running event unless times[i] - (the event's last stamp) > gap (fp64, strict); classes
+ * do not see each other, so events of different classes may overlap.  Event e, ordered by its first window: ev_cls,
+ * ev_first (that window), ev_n (its windows), ev_t_start / ev_t_end (first / last stamp), ev_t_peak / ev_p_peak (stamp and
+ * probability of its FIRST maximum).  The arrays hold cap entries; *count = the events found and counts on past cap.
+ * ws: gww_glitch_events_workspace_bytes(n) bytes, 16-byte aligned, refused before any launch when smaller.  n 0..2^31-65.
+ * Two launches (one for n = 0); identical calls give identical bits. */
+int gww_head_scan_f32(const float* x, const gww_mlp_params* params, int B, int d_in, int C, long row_offset, int* cls,
+                      float* prob, float* probs, void* stream);
+size_t gww_glitch_events_workspace_bytes(long n);
+int gww_glitch_events(const double* times, const int* cls, const float* prob, long n, float prob_threshold, double gap,
+                      unsigned long long ignore, int cap, int* ev_cls, int* ev_first, int* ev_n, double* ev_t_start,
+                      double* ev_t_end, double* ev_t_peak, float* ev_p_peak, int* count, void* ws, size_t ws_bytes,
+                      void* stream);
 
 #ifdef __cplusplus
 }
