@@ -324,6 +324,12 @@ SIGNATURES = {
     "gww_glitch_events_workspace_bytes": (C.c_size_t, [C.c_long]),
     "gww_glitch_events": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_double, C.c_ulonglong, C.c_int]
                           + [C.c_void_p] * 9 + [C.c_size_t, C.c_void_p]),
+    "gww_coinc_blocks": (C.c_size_t, [C.c_long]),
+    "gww_coinc_count_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p,
+                                      C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gww_coinc_offsets": (C.c_int, [C.c_void_p, C.c_long, C.c_int, C.c_void_p, C.c_void_p]),
+    "gww_coinc_emit_f64": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_void_p, C.c_long,
+                                     C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_long] + [C.c_void_p] * 6),
 }
 
 ABI_VERSION = 108   # include/gww.h GWW_VERSION this binding was written against

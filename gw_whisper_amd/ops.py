@@ -1880,3 +1880,69 @@ def trig_steps(fp_sorted, n_fp, tp_sorted, n_tp, duration: float, prefactor: flo
                                        n_steps.data_ptr(), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
               "gww_trig_steps_f64")
     return (*outs, n_steps)
+
+
+# ---- coincidences of two detectors' events at zero lag and under time slides (csrc/coinc.hip) ----------------------------
+COINC_MAX_N, COINC_MAX_S = 1 << 27, 65535
+
+
+def _coinc_events(t, v, n, who, g):
+    """(t, v, capacity, address of the device's count or 0) of detector g's event list"""
+    t = _dev(t, torch.float64, f"t{g}")
+    v = _dev(v, torch.float32, f"v{g}")
+    if t.dim() != 1 or v.shape != t.shape or t.numel() > COINC_MAX_N:
+        raise _lib.GwwError(f"{who}: t{g} must be fp64 [cap <= 2^27] and v{g} fp32 of the same shape, got {tuple(t.shape)} and "
+                            f"{tuple(v.shape)}")
+    if torch.is_tensor(n):
+        _state(n, torch.int32, (1,), who, f"the device count n{g}")
+        return t, v, t.numel(), n.data_ptr()
+    n = int(n)
+    if not 0 <= n <= t.numel():
+        raise _lib.GwwError(f"{who}: n{g}={n} must be 0..{t.numel()}, the length of t{g}")
+    return t, v, n, 0
+
+
+def coinc_slides(t0, v0, n0, t1, v1, n1, shifts, window: float, cap_total: int | None = None):
+    """Coincidences of detector 0's events (``t0`` fp64 ascending, ``v0`` fp32) with detector 1's under every shift of
+    ``shifts`` fp64 [S] (seconds added to ``t1``; 0.0 is zero lag): ``gww_coinc_count_f64``, ``gww_coinc_offsets``,
+    ``gww_coinc_emit_f64``, three launches.  ``n0`` / ``n1``: python ints (the first n events count) or int32 [1] tensors on
+    the device (the count is read there, clamped to the length).  Events i, j are coincident iff
+    ``fabs((t1[j] + shift) - t0[i]) <= window``; i's partner is the coincident j of the largest ``v1``, then the smallest
+    ``fabs(dt)``, then the smallest j.  Returns a dict of device tensors: ``offsets`` int64 [S + 1] (slide s owns entries
+    ``offsets[s] .. offsets[s + 1] - 1``, in ascending i) and ``time`` = t0[i], ``stat`` = double(v0[i]) + double(v1[j]),
+    ``dt`` fp64, ``idx0`` = i, ``idx1`` = j int32.
+    ``cap_total=None``: the 8-byte total ``offsets[S]`` is read back -- ONE host synchronisation -- and the result has exactly
+    that many entries.  With ``cap_total`` nothing is read: the buffers have ``cap_total`` entries, the first
+    ``min(offsets[S], cap_total)`` are written, and ``offsets`` holds the true totals whether or not the list was cut."""
+    who = "coinc_slides"
+    t0, v0, cap0, n0_dev = _coinc_events(t0, v0, n0, who, 0)
+    t1, v1, cap1, n1_dev = _coinc_events(t1, v1, n1, who, 1)
+    shifts = _dev(shifts, torch.float64, "shifts")
+    S = shifts.numel()
+    if shifts.dim() != 1 or not 1 <= S <= COINC_MAX_S:
+        raise _lib.GwwError(f"{who}: shifts must be fp64 [S] with 1 <= S <= {COINC_MAX_S}, got {tuple(shifts.shape)}")
+    window = float(window)
+    if not window >= 0.0:
+        raise _lib.GwwError(f"{who}: window={window} must not be negative")
+    if cap_total is not None and int(cap_total) < 0:
+        raise _lib.GwwError(f"{who}: cap_total={cap_total} must not be negative")
+    dev = t0.device
+    nb = int(lib().gww_coinc_blocks(cap0))
+    partner = torch.empty((S, cap0), dtype=torch.int32, device=dev)
+    blocks = torch.empty((S * nb,), dtype=torch.int64, device=dev)
+    offsets = torch.empty((S + 1,), dtype=torch.int64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().gww_coinc_count_f64(t0.data_ptr(), n0_dev, cap0, t1.data_ptr(), v1.data_ptr(), n1_dev, cap1,
+                                        shifts.data_ptr(), S, window, partner.data_ptr(), blocks.data_ptr(), _stream()),
+              "gww_coinc_count_f64")
+        check(lib().gww_coinc_offsets(blocks.data_ptr(), cap0, S, offsets.data_ptr(), _stream()), "gww_coinc_offsets")
+        cap = int(offsets[S].item()) if cap_total is None else int(cap_total)     # the one host read
+        f64, i32 = torch.float64, torch.int32
+        r = {"time": torch.empty((cap,), dtype=f64, device=dev), "stat": torch.empty((cap,), dtype=f64, device=dev),
+             "dt": torch.empty((cap,), dtype=f64, device=dev), "idx0": torch.empty((cap,), dtype=i32, device=dev),
+             "idx1": torch.empty((cap,), dtype=i32, device=dev), "offsets": offsets}
+        check(lib().gww_coinc_emit_f64(t0.data_ptr(), v0.data_ptr(), n0_dev, cap0, t1.data_ptr(), v1.data_ptr(), n1_dev, cap1,
+                                       shifts.data_ptr(), S, partner.data_ptr(), blocks.data_ptr(), cap, r["time"].data_ptr(),
+                                       r["stat"].data_ptr(), r["dt"].data_ptr(), r["idx0"].data_ptr(), r["idx1"].data_ptr(),
+                                       _stream()), "gww_coinc_emit_f64")
+    return r

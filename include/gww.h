@@ -911,6 +911,28 @@ int gww_trig_steps_f64(const double* fp_sorted, const int* n_fp, long cap, const
                        long cap_tp, double duration, double prefactor, double Ninj, double* ranking, double* far,
                        double* sens_frac, double* sens_vol, double* sens_vol_err, int* n_steps, void* ws, size_t ws_bytes,
                        void* stream);
+/* Coincidences of two detectors' event lists at zero lag and under time slides (coinc.hip).  t0 fp64
+ * ascending / v0 fp32: detector 0's events, n0 of them, or -- n0_dev != NULL, an int32 on the device -- the first
+ * clamp(n0_dev[0], 0, n0); t1 / v1 / n1 / n1_dev likewise (t1 ascending over the events that count).  shifts fp64 [S] on
+ * the device.  Events i and j are coincident in slide s iff fabs(d) <= window, d = (t1[j] + shifts[s]) - t0[i] in fp64, one
+ * addition then one subtraction; i's partner is, of its coincident j, the one of the largest v1, then of the smallest
+ * fabs(d), then the smallest j.  n0, n1 0..2^27 (0 is legal: no coincidences), S 1..65535, window >= 0.  Plain launches,
+ * no atomics, no synchronisation, identical calls give identical bits.
+ *   gww_coinc_blocks   the workgroups per slide, max(1, ceil(n0 / 256)): blocks is int64 [S * gww_coinc_blocks(n0)]
+ *   gww_coinc_count    partner int32 [S, n0] = the partner of every detector-0 event (-1: none; rows behind the device's
+ *                      count too); blocks = the coincidences of every (slide, workgroup)
+ *   gww_coinc_offsets  blocks becomes its own exclusive scan in (slide, workgroup) order; offsets int64 [S + 1] = where
+ *                      slide s starts in the ragged result, offsets[S] = the total
+ *   gww_coinc_emit     per coincidence, slide after slide and in ascending i within a slide: time = t0[i], stat =
+ *                      double(v0[i]) + double(v1[j]), dt = d(i, j), idx0 = i, idx1 = j, each [cap_total].  Nothing is
+ *                      written at or beyond cap_total; offsets keeps the true totals, so a cut list is seen. */
+size_t gww_coinc_blocks(long n0);
+int gww_coinc_count_f64(const double* t0, const int* n0_dev, long n0, const double* t1, const float* v1, const int* n1_dev,
+                        long n1, const double* shifts, int S, double window, int* partner, long long* blocks, void* stream);
+int gww_coinc_offsets(long long* blocks, long n0, int S, long long* offsets, void* stream);
+int gww_coinc_emit_f64(const double* t0, const float* v0, const int* n0_dev, long n0, const double* t1, const float* v1,
+                       const int* n1_dev, long n1, const double* shifts, int S, const int* partner, const long long* blocks,
+                       long cap_total, double* time, double* stat, double* dt, int* idx0, int* idx1, void* stream);
 /* Both outputs of the detection head per row, inference only, one launch (test_network.py): out [B, C] fp32 with row
  * pitch out_stride >= C.  mode 0: the softmax, the bits of gww_det_head_forward_f32's probs; mode 1 (C = 2): (z0 - z1,
  * z1 - z0), the reference's --remove-softmax layer.  Operands as gww_det_head_scores_f32. */
