@@ -1,5 +1,6 @@
-// Device primitives shared by the evaluation kernels (roc.hip, score.hip, detect.hip, logmel.hip): the order-preserving
-// integer image of a float, an inclusive block scan, and a stable LSD radix sort of (key, index) pairs.
+// Device primitives shared by the evaluation kernels (roc.hip, coinc.hip, detect.hip, glitch_scan.hip, logmel.hip,
+// logmel_any.hip, and through device_compact.h score.hip and trigger_stats.hip): the order-preserving integer image of a
+// float, an inclusive block scan, and a stable LSD radix sort of (key, index) pairs.
 #pragma once
 
 // ---- order-preserving integer images --------------------------------------------------------------------------------------

@@ -9,23 +9,24 @@
 //                    radix_scatter on 64-bit keys).  The element count may live on the device (n_dev): the grid covers
 //                    the capacity, the kernels read the count
 //   k_sc_closest     find_closest_index for plain values
-//   k_sc_match       per time-sorted event: the gathered event, the closest injection, |dt|, the per-block (TP, FP) counts
-//   k_sc_offsets     one workgroup: the exclusive scan of the per-block count pairs, the two totals
-//   k_sc_compact_ev  ordered compaction of the true and the false positives: a block scan behind the block's offset
+//   k_sc_match       per time-sorted event: the gathered event, the closest injection, |dt|, the per-block (TP, FP) counts:
+//                    the count pass of the events' ordered compaction (device_compact.h: k_pair_offsets scans the counts)
+//   k_sc_compact_ev  its put pass: a block scan behind the block's offset
 //   k_sc_best        one wave per injection: its run of events by two binary searches, the best true-positive statistic
-//   k_sc_inj_count / k_sc_compact_inj   ordered compaction of the found and the missed injections
+//   ScInjections     ordered compaction of the found and the missed injections (compact_launch)
+// An event is a true positive iff sc_true_positive(|dt|, var): the one place that rule is written.
 //   k_sc_far         (n - k - 1) / duration
 //   k_sc_suffix      one workgroup: suffix sums of the found injections' chirp-mass weights in found-statistic order
 //   k_sc_volume      per background statistic: nfound by a binary search, the fraction, the volume and its error
 // This file is compiled with -ffp-contract=off (Makefile): a fused multiply-add in p - p * p would lose the bit match
 // with numpy.
 #include "common.h"
-#include "device_sort.h"
+#include "device_compact.h"
 
 namespace gww {
 
 constexpr long SC_NMAX = 1L << 27;
-constexpr int SC_THREADS = 1024;
+constexpr int SC_THREADS = COMPACT_THREADS;
 constexpr int SC_WAVES = SC_THREADS / 64;
 
 // ascending key = ascending value; -0.0 and +0.0 are one value; every NaN gets the last key (counted by the caller)
@@ -33,10 +34,6 @@ __device__ __forceinline__ unsigned long long sc_key(double v) {
   if (v != v) return ~0ull;
   if (v == 0.0) v = 0.0;
   return ordered_u64(v);
-}
-
-__global__ __launch_bounds__(64) void k_sc_zero(int* __restrict__ v, int n) {
-  if ((int)threadIdx.x < n) v[threadIdx.x] = 0;
 }
 
 __global__ __launch_bounds__(256) void k_sc_keys(const double* __restrict__ keys, const int* __restrict__ n_dev, int cap,
@@ -89,10 +86,8 @@ __global__ __launch_bounds__(256) void k_sc_closest(const double* __restrict__ t
 }
 
 // ---- events -----------------------------------------------------------------------------------------------------------
-// a count pair travels as one 64-bit word: (first << 32) | second, each at most 2^27
-__device__ __forceinline__ unsigned long long sc_pair(bool first, bool second) {
-  return first ? 1ull << 32 : (second ? 1ull : 0ull);
-}
+// a true positive lies within its own var of the closest injection; equality counts (evaluate.py:161)
+__device__ __forceinline__ bool sc_true_positive(double diff, double var) { return diff <= var; }
 
 __global__ __launch_bounds__(SC_THREADS) void k_sc_match(const double* __restrict__ time, const double* __restrict__ stat,
                                                          const double* __restrict__ var, const int* __restrict__ order, int E,
@@ -112,32 +107,14 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_match(const double* __restric
     double d;
     found_idx[p] = sc_closest(tc, N, t, &d);
     diff[p] = d;
-    tp = d <= v;                              // equality counts (evaluate.py:161)
+    tp = sc_true_positive(d, v);
     if (t != t || s != s || v != v) atomicAdd(n_nan, 1);
   }
-  unsigned long long tot;
-  block_scan<unsigned long long, SC_WAVES>(sc_pair(p < E && tp, p < E), part, &tot);
+  const unsigned long long tot = block_pair_total(pair_word(p < E && tp, p < E), part);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
-// one workgroup: blk[b] becomes the pair of counts in front of block b; counts[0], counts[1] = the two totals
-__global__ __launch_bounds__(SC_THREADS) void k_sc_offsets(unsigned long long* __restrict__ blk, int nb, int* __restrict__ counts) {
-  __shared__ unsigned long long part[SC_WAVES];
-  unsigned long long carry = 0ull;
-  for (int b0 = 0; b0 < nb; b0 += SC_THREADS) {
-    const int b = b0 + threadIdx.x;
-    const unsigned long long v = b < nb ? blk[b] : 0ull;
-    unsigned long long tot;
-    const unsigned long long incl = block_scan<unsigned long long, SC_WAVES>(v, part, &tot);
-    if (b < nb) blk[b] = carry + incl - v;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) {
-    counts[0] = (int)(carry >> 32);
-    counts[1] = (int)(carry & 0xFFFFFFFFull);
-  }
-}
-
+// the put pass behind k_sc_match: the true positives (first list) and the false positives of the time-sorted events
 __global__ __launch_bounds__(SC_THREADS) void k_sc_compact_ev(const double* __restrict__ fgs, const double* __restrict__ diff,
                                                               int E, const unsigned long long* __restrict__ blk,
                                                               int* __restrict__ tp_idx, int* __restrict__ fp_idx,
@@ -153,18 +130,14 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_compact_ev(const double* __re
     v = fgs[2 * (size_t)E + p];
     d = diff[p];
   }
-  const bool tp = active && d <= v;
-  const unsigned long long mine = sc_pair(tp, active);
-  unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, SC_WAVES>(mine, part, &tot) - mine;
+  const bool tp = active && sc_true_positive(d, v);
+  const unsigned long long excl = block_pair_before(blk[blockIdx.x], pair_word(tp, active), part);
   if (!active) return;
-  const unsigned j = tp ? (unsigned)(excl >> 32) : (unsigned)(excl & 0xFFFFFFFFull);
+  const unsigned j = tp ? pair_first(excl) : pair_second(excl);
   if (j >= (unsigned)E) return;              // always false for consistent counts; never store outside the buffers
-  int* oi = tp ? tp_idx : fp_idx;
-  double* od = tp ? tp_diff : fp_diff;
   double* oe = tp ? tp_ev : fp_ev;
-  oi[j] = (int)p;
-  od[j] = d;
+  (tp ? tp_idx : fp_idx)[j] = (int)p;
+  (tp ? tp_diff : fp_diff)[j] = d;
   oe[j] = t;
   oe[(size_t)E + j] = s;
   oe[2 * (size_t)E + j] = v;
@@ -195,7 +168,7 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_best(const int* __restrict__ 
   double m = 0.0;
   int has = 0;
   for (int p = L + lane; p < R; p += 64) {
-    if (diff[p] <= fgs[2 * (size_t)E + p]) {
+    if (sc_true_positive(diff[p], fgs[2 * (size_t)E + p])) {
       const double s = fgs[(size_t)E + p];
       if (!has || s > m) m = s;
       has = 1;
@@ -214,37 +187,25 @@ __global__ __launch_bounds__(SC_THREADS) void k_sc_best(const int* __restrict__ 
   }
 }
 
-__global__ __launch_bounds__(SC_THREADS) void k_sc_inj_count(const unsigned char* __restrict__ flag, int N,
-                                                             unsigned long long* __restrict__ blk) {
-  __shared__ unsigned long long part[SC_WAVES];
-  const long i = (long)blockIdx.x * SC_THREADS + threadIdx.x;
-  const int f = i < N ? flag[i] : 0;
-  unsigned long long tot;
-  block_scan<unsigned long long, SC_WAVES>(sc_pair(f == 1, f == 2), part, &tot);
-  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(SC_THREADS) void k_sc_compact_inj(const unsigned char* __restrict__ flag, const double* __restrict__ best,
-                                                               int N, const unsigned long long* __restrict__ blk,
-                                                               int* __restrict__ found_inj, double* __restrict__ found_stat,
-                                                               int* __restrict__ missed) {
-  __shared__ unsigned long long part[SC_WAVES];
-  const long i = (long)blockIdx.x * SC_THREADS + threadIdx.x;
-  const int f = i < N ? flag[i] : 0;
-  const unsigned long long mine = sc_pair(f == 1, f == 2);
-  unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, SC_WAVES>(mine, part, &tot) - mine;
-  if (f == 1) {
-    const unsigned j = (unsigned)(excl >> 32);
-    if (j < (unsigned)N) {
-      found_inj[j] = (int)i;
-      found_stat[j] = best[i];
-    }
-  } else if (f == 2) {
-    const unsigned j = (unsigned)(excl & 0xFFFFFFFFull);
-    if (j < (unsigned)N) missed[j] = (int)i;
+// the found injections with their best statistic (first list) and the missed ones
+struct ScInjections {
+  const unsigned char* flag;
+  const double* best;
+  int N;
+  int* found_inj;
+  double* found_stat;
+  int* missed;
+  __device__ int count() const { return N; }
+  __device__ unsigned capacity() const { return (unsigned)N; }
+  __device__ int side(long i) const {
+    const int f = flag[i];
+    return f == 1 || f == 2 ? f : 0;
   }
-}
+  __device__ void put(long i, int side, unsigned j) const {
+    (side == 1 ? found_inj : missed)[j] = (int)i;
+    if (side == 1) found_stat[j] = best[i];
+  }
+};
 
 // ---- rates and volumes ----------------------------------------------------------------------------------------------------
 // far[k] = (n - k - 1) / duration over n ascending noise statistics (evaluate.py:185-186): an exact integer, one division
@@ -365,7 +326,7 @@ extern "C" int gww_score_sort_f64(const double* keys, long n, const int* n_dev, 
   hipStream_t s = (hipStream_t)stream;
   const int cap = (int)n;
   const unsigned b256 = (unsigned)cdiv(n, 256);
-  hipLaunchKernelGGL(k_sc_zero, dim3(1), dim3(64), 0, s, n_nan, 1);
+  hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, n_nan, 1);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sc_keys, dim3(b256), dim3(256), 0, s, keys, n_dev, cap, w.key_a, w.idx_a, n_nan);
   GWW_LAUNCH_CHECK();
@@ -407,12 +368,12 @@ extern "C" int gww_score_match_f64(const double* events, const int* order, long 
   hipStream_t s = (hipStream_t)stream;
   const int e = (int)E, n = (int)N;
   const unsigned be = (unsigned)cdiv(E, SC_THREADS), bn = (unsigned)cdiv(N, SC_THREADS);
-  hipLaunchKernelGGL(k_sc_zero, dim3(1), dim3(64), 0, s, counts, 5);
+  hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, counts, 5);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sc_match, dim3(be), dim3(SC_THREADS), 0, s, events, events + E, events + 2 * E, order, e, tc, n, fg_sorted,
                      found_idx, w.diff, w.blk_e, counts + 4);
   GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sc_offsets, dim3(1), dim3(SC_THREADS), 0, s, w.blk_e, (int)be, counts);
+  hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(SC_THREADS), 0, s, w.blk_e, (int)be, counts, counts + 1);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_sc_compact_ev, dim3(be), dim3(SC_THREADS), 0, s, (const double*)fg_sorted, (const double*)w.diff, e,
                      (const unsigned long long*)w.blk_e, tp_idx, fp_idx, tp_diff, fp_diff, tp_events, fp_events);
@@ -420,14 +381,7 @@ extern "C" int gww_score_match_f64(const double* events, const int* order, long 
   hipLaunchKernelGGL(k_sc_best, dim3((unsigned)cdiv(N, SC_WAVES)), dim3(SC_THREADS), 0, s, (const int*)found_idx,
                      (const double*)fg_sorted, (const double*)w.diff, e, n, w.best, w.flag);
   GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sc_inj_count, dim3(bn), dim3(SC_THREADS), 0, s, (const unsigned char*)w.flag, n, w.blk_n);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sc_offsets, dim3(1), dim3(SC_THREADS), 0, s, w.blk_n, (int)bn, counts + 2);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_sc_compact_inj, dim3(bn), dim3(SC_THREADS), 0, s, (const unsigned char*)w.flag, (const double*)w.best, n,
-                     (const unsigned long long*)w.blk_n, found_inj, found_stat, missed);
-  GWW_LAUNCH_CHECK();
-  return GWW_OK;
+  return compact_launch(ScInjections{w.flag, w.best, n, found_inj, found_stat, missed}, bn, w.blk_n, counts + 2, counts + 3, s);
 }
 
 extern "C" int gww_score_far_f64(const int* n_dev, long n, double duration, double* far, void* stream) {

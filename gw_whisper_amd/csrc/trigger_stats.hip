@@ -5,64 +5,39 @@
 // equals numpy's operation for operation.  No atomics on data (two integer NaN counters only), no
 // cross-workgroup flags, nothing here synchronises.  Every count lives on the device (device_sort.h: device_count): the
 // grids cover the capacity, the kernels read the clamped count.
-//   k_ts_trig_count / k_ts_offsets / k_ts_trig_compact   ordered compaction of (time, value) of the samples above the
-//                    threshold: per-block counts, a one-workgroup exclusive scan of them, a block scan behind the block's
-//                    offset.  TS_ITEMS consecutive samples per thread.  time = double(i) * delta_t + epoch, rounded twice
+// The three ordered compactions share device_compact.h: per-block count pairs, k_pair_offsets (a one-workgroup exclusive
+// scan of them), a block scan behind the block's offset; each predicate is one function, used by both passes.
+//   k_ts_trig_count / k_ts_trig_compact   (time, value) of the samples above the threshold (ts_is_trigger).  TS_ITEMS
+//                    consecutive samples per thread.  time = double(i) * delta_t + epoch, rounded twice
 //   k_ts_ev_partial / k_ts_ev_carry / k_ts_ev_emit   clusters and events: trigger j opens a cluster iff j == 0 or
 //                    t[j] - t[j-1] >= tolerance; a segmented inclusive scan with the (value, first index) maximum as
 //                    operator -- in the block, then over the blocks' aggregates by one workgroup, then again in the block
 //                    behind the carry -- leaves at the last trigger of every cluster np.argmax of its run; the cluster's
 //                    number is the scan of the opening flags
-//   k_ts_split_count / k_ts_split_compact   true positive iff the distance to the nearest injection <= tolerance; ordered
-//                    compaction of the two groups' values
-//   k_ts_step_count / k_ts_step_starts / k_ts_step_stats   one ranking step per run of equal ascending false-positive
-//                    values: the starts are compacted, then one thread per step
+//   k_ts_split_count / k_ts_split_compact   true positive iff the distance to the nearest injection <= tolerance
+//                    (ts_true_positive): the two groups' values
+//   TsStepStarts / k_ts_step_stats   one ranking step per run of equal ascending false-positive values: the starts are
+//                    compacted by the generic kernel pair (compact_launch), then one thread per step
 // This file is compiled with -ffp-contract=off (Makefile): a fused multiply-add in double(i) * delta_t + epoch or in
 // q - q * q would lose the bit match with numpy, and the first decides on which side of the cluster tolerance a gap falls.
 #include "common.h"
-#include "device_sort.h"
+#include "device_compact.h"
 
 namespace gww {
 
 constexpr long TS_NMAX = 1L << 27;
-constexpr int TS_THREADS = 1024;
+constexpr int TS_THREADS = COMPACT_THREADS;
 constexpr int TS_WAVES = TS_THREADS / 64;
 constexpr int TS_ITEMS = 4;                       // consecutive samples of one thread of the trigger kernels
 constexpr int TS_CARRY = 256;                     // threads of the one-workgroup carry scan of the event kernels
 constexpr int TS_TILE = TS_THREADS * TS_ITEMS;    // samples of one workgroup of the trigger kernels
 constexpr double TS_SEC_PER_MONTH = 2592000.0;    // 30 * 24 * 60 * 60 (evaluate_test_data.py:18)
 
-__global__ __launch_bounds__(64) void k_ts_zero(int* __restrict__ v, int n) {
-  if ((int)threadIdx.x < n) v[threadIdx.x] = 0;
-}
-
-// a count pair travels as one 64-bit word: (first << 32) | second, each at most 2^27
-__device__ __forceinline__ unsigned long long ts_pair(bool first, bool second) {
-  return first ? 1ull << 32 : (second ? 1ull : 0ull);
-}
-
-// one workgroup: blk[b] becomes the pair of counts in front of block b; *first, *second (either may be NULL) = the totals
-__global__ __launch_bounds__(TS_THREADS) void k_ts_offsets(unsigned long long* __restrict__ blk, int nb, int* __restrict__ first,
-                                                           int* __restrict__ second) {
-  __shared__ unsigned long long part[TS_WAVES];
-  unsigned long long carry = 0ull;
-  for (int b0 = 0; b0 < nb; b0 += TS_THREADS) {
-    const int b = b0 + threadIdx.x;
-    const unsigned long long v = b < nb ? blk[b] : 0ull;
-    unsigned long long tot;
-    const unsigned long long incl = block_scan<unsigned long long, TS_WAVES>(v, part, &tot);
-    if (b < nb) blk[b] = carry + incl - v;
-    carry += tot;
-  }
-  if (threadIdx.x == 0) {
-    if (first) first[0] = (int)(carry >> 32);
-    if (second) second[0] = (int)(carry & 0xFFFFFFFFull);
-  }
-}
-
 // ---- triggers -----------------------------------------------------------------------------------------------------------
 // get_triggers (bnslib.py:216-240): the samples with series[i] > threshold, compared in fp64 (an fp32 sample widens
 // exactly); equality is no trigger and a NaN never is (counted: the caller refuses the series)
+__device__ __forceinline__ bool ts_is_trigger(double v, double thr) { return v > thr; }
+
 template <typename T>
 __global__ __launch_bounds__(TS_THREADS) void k_ts_trig_count(const T* __restrict__ series, int n, double thr,
                                                               unsigned long long* __restrict__ blk, int* __restrict__ n_nan) {
@@ -74,13 +49,12 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_trig_count(const T* __restric
   for (int k = 0; k < TS_ITEMS; ++k) {
     if (i0 + k < n) {
       const double v = (double)series[i0 + k];
-      c += v > thr ? 1ull : 0ull;
+      c += ts_is_trigger(v, thr) ? 1ull : 0ull;
       bad += v != v ? 1 : 0;
     }
   }
   if (bad) atomicAdd(n_nan, bad);               // an integer count: the order of the adds does not matter
-  unsigned long long tot;
-  block_scan<unsigned long long, TS_WAVES>(c << 32, part, &tot);
+  const unsigned long long tot = block_pair_total(c << 32, part);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -95,14 +69,12 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_trig_compact(const T* __restr
 #pragma unroll
   for (int k = 0; k < TS_ITEMS; ++k) {
     v[k] = i0 + k < n ? (double)series[i0 + k] : 0.0;
-    c += (i0 + k < n && v[k] > thr) ? 1ull : 0ull;
+    c += (i0 + k < n && ts_is_trigger(v[k], thr)) ? 1ull : 0ull;
   }
-  unsigned long long tot;
-  const unsigned long long incl = block_scan<unsigned long long, TS_WAVES>(c << 32, part, &tot);
-  unsigned j = (unsigned)((blk[blockIdx.x] + incl - (c << 32)) >> 32);
+  unsigned j = pair_first(block_pair_before(blk[blockIdx.x], c << 32, part));
 #pragma unroll
   for (int k = 0; k < TS_ITEMS; ++k) {
-    if (i0 + k < n && v[k] > thr) {
+    if (i0 + k < n && ts_is_trigger(v[k], thr)) {
       if (j < (unsigned)cap) {                    // more triggers than the capacity: counted, not stored (the caller refuses)
         const double prod = (double)(i0 + k) * delta_t;   // sample_times = arange(n) * delta_t + epoch: two roundings
         times[j] = prod + epoch;
@@ -196,7 +168,7 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_ev_partial(const double* __re
     if (s.v != s.v) atomicAdd(n_nan, 1);
   }
   unsigned long long tot;
-  block_scan<unsigned long long, TS_WAVES>(ts_pair(s.f != 0, false), part, &tot);
+  block_scan<unsigned long long, TS_WAVES>(pair_word(s.f != 0, false), part, &tot);
   TsSeg all;
   ts_block_seg_scan(s, spart, &all);
   if (threadIdx.x == 0) {
@@ -241,7 +213,7 @@ __global__ __launch_bounds__(TS_CARRY) void k_ts_ev_carry(TsBlocks B, int nb, in
     carry += tot;
     scarry = ts_seg_join(scarry, all);
   }
-  if (threadIdx.x == 0) n_events[0] = (int)(carry >> 32);
+  if (threadIdx.x == 0) n_events[0] = (int)pair_first(carry);
 }
 
 __global__ __launch_bounds__(TS_THREADS) void k_ts_ev_emit(const double* __restrict__ times, const double* __restrict__ values,
@@ -254,14 +226,14 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_ev_emit(const double* __restr
   TsSeg s = ts_seg_none();
   if (j < n) s = TsSeg{values[j], (int)j, ts_opens(times, (int)j, tol) ? 1 : 0};
   unsigned long long tot;
-  const unsigned long long incl = B.cnt[blockIdx.x] + block_scan<unsigned long long, TS_WAVES>(ts_pair(s.f != 0, false), part, &tot);
+  const unsigned long long incl = B.cnt[blockIdx.x] + block_scan<unsigned long long, TS_WAVES>(pair_word(s.f != 0, false), part, &tot);
   TsSeg all;
   const TsSeg in{B.v[blockIdx.x], B.i[blockIdx.x], 0};
   const TsSeg best = ts_seg_join(in, ts_block_seg_scan(s, spart, &all));
   if (j >= n) return;
   const bool last = j == n - 1 || times[j + 1] - times[j] >= tol;
   if (!last) return;
-  const unsigned c = (unsigned)(incl >> 32) - 1u;   // the cluster's number: the clusters opened up to j, less one
+  const unsigned c = pair_first(incl) - 1u;   // the cluster's number: the clusters opened up to j, less one
   if (c >= (unsigned)cap || (unsigned)best.i >= (unsigned)n) return;   // never true; never store or load outside the buffers
   ev_times[c] = times[best.i];
   ev_values[c] = best.v;
@@ -270,6 +242,8 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_ev_emit(const double* __restr
 // ---- true and false positives ---------------------------------------------------------------------------------------------
 // split_true_and_false_positives (evaluate_test_data.py:28-87): diff = the distance to the nearest injection; a true positive
 // iff diff <= tolerance (equality counts)
+__device__ __forceinline__ bool ts_true_positive(double diff, double tol) { return diff <= tol; }
+
 __global__ __launch_bounds__(TS_THREADS) void k_ts_split_count(const double* __restrict__ values, const double* __restrict__ diff,
                                                                const int* __restrict__ n_dev, int cap, double tol,
                                                                unsigned long long* __restrict__ blk, int* __restrict__ n_nan) {
@@ -278,12 +252,11 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_split_count(const double* __r
   const long j = (long)blockIdx.x * TS_THREADS + threadIdx.x;
   bool tp = false;
   if (j < n) {
-    tp = diff[j] <= tol;
+    tp = ts_true_positive(diff[j], tol);
     const double v = values[j];
     if (v != v) atomicAdd(n_nan, 1);
   }
-  unsigned long long tot;
-  block_scan<unsigned long long, TS_WAVES>(ts_pair(j < n && tp, j < n), part, &tot);
+  const unsigned long long tot = block_pair_total(pair_word(j < n && tp, j < n), part);
   if (threadIdx.x == 0) blk[blockIdx.x] = tot;
 }
 
@@ -295,42 +268,27 @@ __global__ __launch_bounds__(TS_THREADS) void k_ts_split_compact(const double* _
   const int n = device_count(n_dev, cap);
   const long j = (long)blockIdx.x * TS_THREADS + threadIdx.x;
   const bool active = j < n;
-  const bool tp = active && diff[j] <= tol;
-  const unsigned long long mine = ts_pair(tp, active);
-  unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, TS_WAVES>(mine, part, &tot) - mine;
+  const bool tp = active && ts_true_positive(diff[j], tol);
+  const unsigned long long excl = block_pair_before(blk[blockIdx.x], pair_word(tp, active), part);
   if (!active) return;
-  const unsigned p = tp ? (unsigned)(excl >> 32) : (unsigned)(excl & 0xFFFFFFFFull);
+  const unsigned p = tp ? pair_first(excl) : pair_second(excl);
   if (p >= (unsigned)cap) return;                 // always false for consistent counts; never store outside the buffers
   (tp ? tp_values : fp_values)[p] = values[j];
 }
 
 // ---- ranking steps --------------------------------------------------------------------------------------------------------
-// evaluate_test_data.py:555-583 over the ascending false-positive values v[0 .. n): one step per run of equal values
-__device__ __forceinline__ bool ts_starts(const double* __restrict__ v, int a) { return a == 0 || v[a] != v[a - 1]; }
-
-__global__ __launch_bounds__(TS_THREADS) void k_ts_step_count(const double* __restrict__ v, const int* __restrict__ n_dev, int cap,
-                                                              unsigned long long* __restrict__ blk) {
-  __shared__ unsigned long long part[TS_WAVES];
-  const int n = device_count(n_dev, cap);
-  const long a = (long)blockIdx.x * TS_THREADS + threadIdx.x;
-  unsigned long long tot;
-  block_scan<unsigned long long, TS_WAVES>(ts_pair(a < n && ts_starts(v, (int)a), false), part, &tot);
-  if (threadIdx.x == 0) blk[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(TS_THREADS) void k_ts_step_starts(const double* __restrict__ v, const int* __restrict__ n_dev, int cap,
-                                                               const unsigned long long* __restrict__ blk, int* __restrict__ starts) {
-  __shared__ unsigned long long part[TS_WAVES];
-  const int n = device_count(n_dev, cap);
-  const long a = (long)blockIdx.x * TS_THREADS + threadIdx.x;
-  const bool st = a < n && ts_starts(v, (int)a);
-  const unsigned long long mine = ts_pair(st, false);
-  unsigned long long tot;
-  const unsigned long long excl = blk[blockIdx.x] + block_scan<unsigned long long, TS_WAVES>(mine, part, &tot) - mine;
-  const unsigned s = (unsigned)(excl >> 32);
-  if (st && s < (unsigned)cap) starts[s] = (int)a;
-}
+// evaluate_test_data.py:555-583 over the ascending false-positive values v[0 .. n): one step per run of equal values,
+// starts[s] = the position where run s begins
+struct TsStepStarts {
+  const double* v;
+  const int* n_dev;
+  int cap;
+  int* starts;
+  __device__ int count() const { return device_count(n_dev, cap); }
+  __device__ unsigned capacity() const { return (unsigned)cap; }
+  __device__ int side(long a) const { return a == 0 || v[a] != v[a - 1] ? 1 : 0; }
+  __device__ void put(long a, int, unsigned s) const { starts[s] = (int)a; }
+};
 
 struct TsStats {
   double *ranking, *far, *frac, *vol, *vol_err;
@@ -407,12 +365,12 @@ static TsStepWs ts_step_carve(void* ws, long n) {
 template <typename T>
 static int ts_triggers(const T* series, long n, long cap, double delta_t, double epoch, double threshold, double* times,
                        double* values, int* counts, unsigned long long* blk, hipStream_t s) {
-  const unsigned nb = (unsigned)ts_blocks(n, TS_TILE);
-  hipLaunchKernelGGL(k_ts_zero, dim3(1), dim3(64), 0, s, counts, 2);
+  hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, counts, 2);
   GWW_LAUNCH_CHECK();
+  const unsigned nb = (unsigned)ts_blocks(n, TS_TILE);
   hipLaunchKernelGGL(k_ts_trig_count<T>, dim3(nb), dim3(TS_THREADS), 0, s, series, (int)n, threshold, blk, counts + 1);
   GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ts_offsets, dim3(1), dim3(TS_THREADS), 0, s, blk, (int)nb, counts, (int*)nullptr);
+  hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(TS_THREADS), 0, s, blk, (int)nb, counts, (int*)nullptr);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ts_trig_compact<T>, dim3(nb), dim3(TS_THREADS), 0, s, series, (int)n, threshold, delta_t, epoch,
                      (const unsigned long long*)blk, (int)cap, times, values);
@@ -464,7 +422,7 @@ extern "C" int gww_trig_events_f64(const double* times, const double* values, co
   const TsEvWs w = ts_ev_carve(ws, cap);
   hipStream_t s = (hipStream_t)stream;
   const unsigned nb = (unsigned)ts_blocks(cap, TS_THREADS);
-  hipLaunchKernelGGL(k_ts_zero, dim3(1), dim3(64), 0, s, counts, 2);
+  hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, counts, 2);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ts_ev_partial, dim3(nb), dim3(TS_THREADS), 0, s, times, values, n_dev, (int)cap, tolerance, w.B, counts + 1);
   GWW_LAUNCH_CHECK();
@@ -492,12 +450,12 @@ extern "C" int gww_trig_split_f64(const double* values, const double* diff, cons
   GWW_REQUIRE(aligned(ws, 16), "gww_trig_split_f64: workspace must be 16-byte aligned");
   unsigned long long* blk = reinterpret_cast<unsigned long long*>(ws);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = (unsigned)ts_blocks(cap, TS_THREADS);
-  hipLaunchKernelGGL(k_ts_zero, dim3(1), dim3(64), 0, s, counts, 3);
+  hipLaunchKernelGGL(k_zero_i32, dim3(1), dim3(64), 0, s, counts, 3);
   GWW_LAUNCH_CHECK();
+  const unsigned nb = (unsigned)ts_blocks(cap, TS_THREADS);
   hipLaunchKernelGGL(k_ts_split_count, dim3(nb), dim3(TS_THREADS), 0, s, values, diff, n_dev, (int)cap, tolerance, blk, counts + 2);
   GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ts_offsets, dim3(1), dim3(TS_THREADS), 0, s, blk, (int)nb, counts, counts + 1);
+  hipLaunchKernelGGL(k_pair_offsets, dim3(1), dim3(TS_THREADS), 0, s, blk, (int)nb, counts, counts + 1);
   GWW_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_ts_split_compact, dim3(nb), dim3(TS_THREADS), 0, s, values, diff, n_dev, (int)cap, tolerance,
                      (const unsigned long long*)blk, tp_values, fp_values);
@@ -524,14 +482,8 @@ extern "C" int gww_trig_steps_f64(const double* fp_sorted, const int* n_fp, long
   GWW_REQUIRE(aligned(ws, 16), "gww_trig_steps_f64: workspace must be 16-byte aligned");
   const TsStepWs w = ts_step_carve(ws, cap);
   hipStream_t s = (hipStream_t)stream;
-  const unsigned nb = (unsigned)ts_blocks(cap, TS_THREADS);
-  hipLaunchKernelGGL(k_ts_step_count, dim3(nb), dim3(TS_THREADS), 0, s, fp_sorted, n_fp, (int)cap, w.blk);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ts_offsets, dim3(1), dim3(TS_THREADS), 0, s, w.blk, (int)nb, n_steps, (int*)nullptr);
-  GWW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(k_ts_step_starts, dim3(nb), dim3(TS_THREADS), 0, s, fp_sorted, n_fp, (int)cap,
-                     (const unsigned long long*)w.blk, w.starts);
-  GWW_LAUNCH_CHECK();
+  GWW_TRY(compact_launch(TsStepStarts{fp_sorted, n_fp, (int)cap, w.starts}, (unsigned)ts_blocks(cap, TS_THREADS), w.blk, n_steps,
+                         nullptr, s));
   const TsStats O{ranking, far, sens_frac, sens_vol, sens_vol_err};
   hipLaunchKernelGGL(k_ts_step_stats, dim3((unsigned)cdiv(cap, 256)), dim3(256), 0, s, fp_sorted, n_fp, (int)cap,
                      (const int*)w.starts, (const int*)n_steps, tp_sorted, n_tp, (int)cap_tp, duration, prefactor, Ninj, O);
